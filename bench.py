@@ -2,25 +2,32 @@
 """bench.py — headline benchmark of the batched env step path (BASELINE.json metric: env-steps/sec and agent-steps/sec
 at 8192 envs x 16 agents on 1/2/4/8 MI355X).
 
-    python bench.py                                   # N=1, configs[2] (8192 envs x 16 agents, full step)
+    python bench.py                                   # N=1, configs[2] (8192 envs x 16 agents, full step): the headline only
+    python bench.py --full                            # ... plus the secondary operating points and the CPU baselines
     python bench.py --gpus N --steps K --warmup W     # N>1: starts one rank per GPU itself (no torchrun needed) ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # ... or runs as a rank of an existing launcher
     python bench.py --config 5                        # configs[4]: 8192 envs x 32 agents + 64x64x3 birdview raster
     python bench.py --config 2                        # configs[1]: 1024 envs x 8 agents, kinematics + collision only
+    python bench.py --dump-outputs DIR                # also writes what the last timed step computed as DIR/<name>.npy
 
 A "step" is ONE timestep of the whole batch held by a GPU.  State, world tables and the ego-action buffer are resident
 in HBM when the timed region starts; steps are driven through the C-ABI (tde_env_rollout: up to 250 consecutive
 timesteps per call, no host round trip in between).
 
-Timing protocol (what makes a short driver invocation such as `--steps 20 --warmup 5` report the steady state):
-  * un-timed: `--warmup` steps, and in any case at least one full 250-step launch and >= 50 ms of launches;
-  * timed: `repeats` back-to-back copies of the `--steps` block, repeats chosen so that the region lasts >= 0.25 s;
-    the steps*repeats consecutive timesteps are issued in launches of up to 250 steps (the rollout call's operating
-    point); `steps` / `warmup` echo the command line, `ms_per_step` = wall / (steps * repeats);
+Timing protocol:
+  * un-timed: `--warmup` steps (at least one full 250-step launch), then >= 50 ms of launches that only ramp the clocks:
+    the state is put back to where the `--warmup` steps left it, so the timed region starts from a state that depends on
+    the command line alone and `--dump-outputs` gives the same arrays from run to run;
+  * timed: exactly `--steps` consecutive timesteps, issued in launches of up to 250 steps (the rollout call's operating
+    point); `steps` / `warmup` echo the command line, `ms_per_step` = wall / steps;
   * the region is bracketed by barrier + torch.cuda.synchronize() on both sides, MAX over ranks;
   * every timed launch is also bracketed by HIP events on the launch stream: `roofline` is computed from those
     (algorithmic bytes of the launches actually made / their summed duration), with min / median per launch.
+
+A plain run measures the headline alone.  `--full` adds, for N = 1, the secondary operating points (other configs, closed
+loop, lights, town map, the Python boundary; config 3 rollout only) and the CPU baselines (the oracle and batched torch on
+the host), each timed in runs of their own after the headline region.
 
 Multi-GPU: envs are independent, so the global batch (configs[3] = 65536 envs at N=8) is cut into contiguous shards of
 8192 envs, one rank per GPU (weak scaling), with the reset RNG keyed by the GLOBAL env index (tde_config.env_base via
@@ -42,7 +49,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s spec
 CH = 250                          # timesteps per tde_env_rollout call (rows of the resident action buffer)
-MIN_WARM_S, MIN_REGION_S = 0.05, 0.25
+MIN_WARM_S = 0.05
+DUMP_BUDGET = 60 * 10**6         # bytes of array data --dump-outputs may write: under 64 MB with the .npy headers
 
 # SURVEY §8(d) algorithmic bytes: per agent-step 46 B (state r/w 32, attrs 12, 2 flag bytes), per NPC agent-step 16 B
 # (controller target + index), per env-step 38 B (action, target, counters, reward, done flags); config 2 (kinematics +
@@ -385,6 +393,35 @@ def fixed_sums(reward, done, x):
     return [bits(reward), int(done.to(torch.int64).sum().item()) % FIXED_MOD, bits(x)]
 
 
+NOT_OUTPUTS = ("action", "slot_cache", "env_cache", "act_cache")   # the step's input and its lookup caches
+
+
+def dump_outputs(out_dir, st, last):
+    """--dump-outputs: `last` = {name: tensor} of what the timed path returned for its last step, and every array of the state it
+    updated in place (NOT_OUTPUTS left out), as out_dir/<name>.npy.  float64 and 32-bit integers are written as float64, the
+    rest (float32, flag bytes, pixels) as float32: exact either way.  Every array is env-major ([B, ...] or [B * A]); when all of
+    them together would exceed DUMP_BUDGET they are cut to the same fixed, seeded sample of envs, listed in sampled_envs.npy."""
+    import numpy as np
+    import torch
+
+    B = st.B
+    arrays = dict(last)
+    arrays.update({k: v for k, v in st.arrays.items() if v is not None and k not in NOT_OUTPUTS})
+    wide = lambda t: t.dtype in (torch.float64, torch.int32, torch.int64)              # noqa: E731
+    per_env = sum(t.numel() // B * (8 if wide(t) else 4) for t in arrays.values())
+    n = min(B, DUMP_BUDGET // per_env)
+    envs = None if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, t in arrays.items():
+        assert t.shape[0] % B == 0, (k, tuple(t.shape))
+        a = t.detach().cpu().numpy()
+        if envs is not None:
+            a = a.reshape((B, -1) + a.shape[1:])[envs].reshape((-1,) + a.shape[1:])
+        np.save(os.path.join(out_dir, f"{k}.npy"), a.astype(np.float64 if wide(t) else np.float32))
+    if envs is not None:
+        np.save(os.path.join(out_dir, "sampled_envs.npy"), envs.astype(np.float64))
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -470,10 +507,17 @@ def main():
                     help="BASELINE.json config, 1-based: 3 = the headline (default), 2 = kinematics + collision only, "
                          "5 = 32 agents + birdview raster")
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default: the config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure (N = 1) the secondary operating points and the CPU baselines, each in "
+                         "runs of their own; a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary operating points (config 5, closed loop, config 2, lights, long episodes) that a "
-                         "default N = 1 headline run reports under `secondary`")
+                    help="with --full: skip the secondary operating points (config 5, closed loop, config 2, lights, long "
+                         "episodes) that an N = 1 headline run reports under `secondary`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region (not timed): write what its last step computed - the rollout's reward and done "
+                         "rows, the birdviews of config 5, and the state arrays the step updates - as DIR/<name>.npy in float32 or "
+                         "float64, at most 64 MB in all (a fixed sample of envs beyond that); rank 0's shard when N > 1")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group of the N>1 barrier / timing reduce (nccl = RCCL, one rank per GPU; gloo for "
                          "tests that put several ranks on one GPU)")
@@ -501,6 +545,8 @@ def main():
     ap.add_argument("--step-kernel", default=None, choices=["solo", "trio"],
                     help="force a form of the one-step kernel (A/B runs; default: the library's choice by batch size)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     t_start = time.perf_counter()
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -623,26 +669,23 @@ def main():
             left -= k
             row += k
 
-    # ---- un-timed: the CLI's warm-up, at least one full-length launch, at least MIN_WARM_S of launches --------------
+    # ---- un-timed: the CLI's warm-up (at least one full-length launch), then at least MIN_WARM_S of launches ----------
     t0 = time.perf_counter()
     startup_s = t0 - t_start                        # process start (after argument parsing) -> first launch: imports, world, uploads
     run(max(args.warmup, CH))
     torch.cuda.synchronize()
     warm_steps = max(args.warmup, CH)
+    # how many steps the clock ramp takes depends on the host's clock: the state it leaves is discarded (caches included, so
+    # the device is exactly where the warm-up left it) and the timed region starts from a state fixed by the command line
+    saved = {k: v.clone() for k, v in st.arrays.items() if v is not None}
     while time.perf_counter() - t0 < MIN_WARM_S:
         run(CH)
         torch.cuda.synchronize()
         warm_steps += CH
-    t1 = time.perf_counter()
-    run(CH)
-    torch.cuda.synchronize()
-    est = (time.perf_counter() - t1) / CH                             # s per step, warm
-    repeats = max(1, int(-(-MIN_REGION_S // max(est * args.steps, 1e-9))))
-    if dist is not None:                                              # every rank must time the same number of steps
-        rr = torch.tensor([repeats], dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(rr, op=dist.ReduceOp.MAX)
-        repeats = int(rr[0])
-    total = args.steps * repeats
+    for k, v in saved.items():
+        st.arrays[k].copy_(v)
+    del saved
+    total = args.steps
 
     # ---- timed region ---------------------------------------------------------------------------------------------
     events = []
@@ -678,6 +721,13 @@ def main():
         ts = torch.tensor([built], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(ts, op=dist.ReduceOp.SUM)
         built = float(ts[0])
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the rollout's rows of that step (the last launch filled rows
+        # 0 .. (total - 1) % CH), the birdviews of config 5, and the state the step updated in place
+        last = {} if stepwise else {"reward": reward[(total - 1) % CH], "done": done[(total - 1) % CH]}
+        if img is not None:
+            last["birdview"] = img
+        dump_outputs(args.dump_outputs, st, last)
 
     # sanity of what was just computed (not timed): finite rewards, episodes progressing
     chk = dict(reward_sum=float((st["reward"] if stepwise else reward).double().sum()),
@@ -760,7 +810,7 @@ def main():
         out = {
             "metric": "env-steps/sec", "value": env_steps / wall, "unit": "env-steps/s",
             "agent_steps_per_sec": env_steps * A / wall,
-            "n_gpus": n, "steps": args.steps, "warmup": args.warmup, "repeats": repeats,
+            "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": wall * 1e3 / total,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{C['name']}: {B} envs x {A} agents per GPU, {C['what']}" +
@@ -768,7 +818,7 @@ def main():
                        "world": args.world,
                        "envs_per_gpu": B, "agents_per_env": A, "global_envs": B * n, "mode": args.mode,
                        "binding": args.binding,
-                       "streams": max(1, n_streams), "steps_per_call": spl, "timed_steps": total, "untimed_warmup_steps": warm_steps + CH,
+                       "streams": max(1, n_streams), "steps_per_call": spl, "timed_steps": total, "untimed_warmup_steps": warm_steps,
                        "sharding": f"{n} contiguous shard(s) of one global batch (env_base = rank * {B}), "
                                    "no data-path collective",
                        "timing_backend": (args.backend if dist is not None else None)},
@@ -796,7 +846,7 @@ def main():
             # tables are built once per machine (by the parent of `--gpus N`, else by the first rank to ask) and loaded by the rest
             "startup": {"to_first_launch_s": startup_s, "world_tables_s": world_s, "ranks_that_built_the_world": int(built)},
         }
-        if n == 1 and args.config == 3 and not stepwise and not args.no_secondary and not args.force_dist:
+        if args.full and n == 1 and args.config == 3 and not stepwise and not args.no_secondary and not args.force_dist:
             out["secondary"] = secondary(dev)
             # the other operating points, compact, INSIDE `roofline` (what the driver's record keeps): us per timestep and the
             # algorithmic-bytes fraction of the 8 TB/s peak, same definition as roofline.frac.  All with the default flags (NPCs
@@ -823,7 +873,7 @@ def main():
                 out["secondary"]["python_boundary"] = python_boundary()
             except Exception as exc:                                   # pragma: no cover
                 out["secondary"]["python_boundary"] = {"error": repr(exc)}
-        if n == 1 and not args.no_cpu_baseline:
+        if args.full and n == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(world, base_cfg, A)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-r02b}
 O=gpurun_out/$TAG; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_shape.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_shape.json 2>> $O/bench.err
 python bench.py --mode step --steps 4000 --warmup 500 --no-cpu-baseline > $O/bench_stepmode.json 2>> $O/bench.err
 python bench.py --mode step --binding ctypes --steps 4000 --warmup 500 --no-cpu-baseline > $O/bench_stepmode_ctypes.json 2>> $O/bench.err
 python bench.py --mode step --envs 1024 --steps 4000 --warmup 500 --no-cpu-baseline > $O/bench_stepmode_1024envs.json 2>> $O/bench.err
@@ -30,7 +30,7 @@ cat $O/rollout_matrix.txt
 python scripts/ab_render.py torchdriveenv_amd/libtde_hip.so > $O/render.txt 2>/dev/null; python scripts/ab_render.py --stack 3 torchdriveenv_amd/libtde_hip.so >> $O/render.txt 2>/dev/null; python scripts/ab_render.py --lights torchdriveenv_amd/libtde_hip.so >> $O/render.txt 2>/dev/null
 python scripts/ablate.py > $O/ablation.txt 2>/dev/null
 python scripts/scale_envs.py > $O/scale_envs.txt 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o st -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o st -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/stats.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_config5 -o st -- python3 bench.py --config 5 --steps 300 --warmup 30 --no-cpu-baseline > $O/stats5.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_step -o st -- python3 bench.py --mode step --steps 2000 --warmup 200 --no-cpu-baseline > $O/stats_step.log 2>&1
 sleep 3

@@ -5,7 +5,7 @@ TAG=${1:-r03m}
 exec < /dev/null
 O=gpurun_out/$TAG; mkdir -p $O
 ( time timeout 1500 python -m pytest tests -m gpu -x -q ) > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_driver_shape.json 2>> $O/bench.err
 python bench.py --config 5 --steps 500 --warmup 50 --no-cpu-baseline > $O/bench_config5.json 2>> $O/bench.err
 python bench.py --config 5 --streams 1 --steps 500 --warmup 50 --no-cpu-baseline > $O/bench_config5_1stream.json 2>> $O/bench.err

@@ -5,7 +5,7 @@ TAG=${1:-r05m}
 exec < /dev/null
 O=gpurun_out/$TAG; mkdir -p $O
 ( time timeout 1800 python -m pytest tests -m gpu -q ) > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
 python bench.py --config 5 --steps 500 --warmup 50 --no-cpu-baseline > $O/bench_config5.json 2>> $O/bench.err
 python bench.py --mode step --steps 4000 --warmup 500 --no-cpu-baseline > $O/bench_stepmode.json 2>> $O/bench.err
 python bench.py --world town --no-secondary --no-cpu-baseline > $O/bench_town.json 2>> $O/bench.err

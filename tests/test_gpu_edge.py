@@ -168,7 +168,7 @@ def test_bench_two_ranks_on_one_gpu(launcher):
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["steps"] == 500 and j["scaling"] == "weak" and j["higher_is_better"] is True
     assert j["metric"] == "env-steps/sec" and j["value"] > 0 and len(j["check"]) == 2
-    timed = j["steps"] * j["repeats"]
+    timed = j["steps"]                                       # --steps is the number of timed steps
     assert j["config"]["timed_steps"] == timed
     assert abs(j["value"] - 2 * 2048 * timed / (j["ms_per_step"] * 1e-3 * timed)) / j["value"] < 1e-6
     # the two ranks are shards of ONE global batch: global env index bases 0 and 2048
@@ -204,6 +204,53 @@ def test_bench_one_rank_over_rccl():
     assert j["n_gpus"] == 1 and j["config"]["timing_backend"] == "nccl" and j["value"] > 0
     assert isinstance(j["check"], list) and len(j["check"]) == 1 and j["check"][0]["env_base"] == 0     # the gathered form
     assert "secondary" not in j
+
+
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: exactly --steps timed steps, and the arrays written are those of the last of them - two runs
+    write identical files, equal to a fresh reset stepped through the warm-up and the timed launches in this process"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    B, A, W, K = 2048, 16, 250, 300                          # timed: one launch of 250 steps and one of 50
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    env["TDE_WORLD_CACHE"] = str(tmp_path / "worlds")
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                            "--envs", str(B), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=root, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert j["steps"] == K and j["config"]["timed_steps"] == K and j["ms_per_step"] > 0
+        assert "secondary" not in j and "cpu_baseline" not in j                # (behind --full)
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    assert dumps[0].keys() == dumps[1].keys() and {"reward", "done", "x", "episode"} <= dumps[0].keys()
+    for k, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][k]), k
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 * 10**6
+    world, _, _ = bench.bench_world("junctions", A)
+    cfg = _abi.default_config(seed=1000, distance_cutoff=0.25, flags=_abi.F_ALL)
+    dw = world.to_device(DEV)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    actions = torch.stack([torch.rand(bench.CH, B, generator=g) * 2 - 1, torch.rand(bench.CH, B, generator=g) * 0.6 - 0.3], -1)
+    actions = actions.to(torch.float32).contiguous().to(DEV)
+    st = EnvState(B, A, device=DEV, with_info=False)
+    ops.env_reset(cfg, dw, st)
+    for k in (W, 250, K - 250):                              # the launches bench.py makes: warm-up, then the timed ones
+        reward, done = ops.env_rollout(cfg, dw, st, actions[:k])
+    torch.cuda.synchronize()
+    assert np.array_equal(dumps[0]["reward"], reward[-1].cpu().numpy())
+    assert np.array_equal(dumps[0]["done"], done[-1].cpu().numpy().astype(np.float32))
+    for k in ("x", "y", "psi", "v", "steps", "episode", "terminated"):
+        assert np.array_equal(dumps[0][k], st[k].cpu().numpy().astype(dumps[0][k].dtype)), k
 
 
 def test_bench_nccl_refuses_ranks_sharing_a_gpu():

@@ -9,12 +9,11 @@ from torchdriveenv_amd import _abi
 from torchdriveenv_amd.state import EnvState
 
 
-def test_batched_torch_step_tracks_the_c_oracle(small_world):
+def test_batched_torch_step_tracks_the_c_oracle(small_world, tmp_path):
     """the CPU twin of tests/test_gpu_torch_witness.py (oracle bits = HIP bits), held to the same bounds: state per element within
     1e-5 * max(1, |ref|), rewards within 1e-4, collision / offroad masks equal on every slot farther than 1e-4 m from its decision
     threshold (tests/witness_util.py); the slots inside the band are counted"""
     import os
-    import tempfile
 
     from tests.witness_util import BAND, Observed, collision_margin, offroad_margin
 
@@ -54,5 +53,5 @@ def test_batched_torch_step_tracks_the_c_oracle(small_world):
         assert (done == (b["terminated"] | b["truncated"]).astype(bool))[~ego_band].all(), t
     assert a["episode"].max() > 1
     assert obs.rec["collided_in_band"] + obs.rec["offroad_in_band"] < 0.001 * obs.rec["slot_steps"]
-    obs.write(os.environ.get("TDE_WITNESS_OUT") or os.path.join(tempfile.gettempdir(), "tde_witness_cpu.json"),
+    obs.write(os.environ.get("TDE_WITNESS_OUT") or str(tmp_path / "tde_witness_cpu.json"),
               what="oracle/tde_oracle.c vs oracle/torch_step.py, 64 envs x 16 agents x 120 teacher-forced steps")

@@ -78,12 +78,13 @@ def test_shard_ranges_partition_the_batch():
     assert shard_range(3, 8, 65536) == (3 * 8192, 4 * 8192)
 
 
-REF_DATA = "/root/reference/torchdriveenv/data"
+# the reference's own data files, committed as fixtures (oracle/gen_reference_data_fixture.py)
+REF_DATA = os.path.join(ROOT, "tests", "golden", "reference_data")
 
 
 def test_reference_suites_load_and_step_with_the_oracle(tmp_path):
     """the reference's own validation suite (its DATA, committed as tests/golden/validation_suite.json) goes through the
-    loaders and the world builder unchanged; runs anywhere (no /root/reference)"""
+    loaders and the world builder unchanged"""
     from oracle import oracle
     from tests.golden_util import write_validation_suite_yaml
     from torchdriveenv_amd.env import world_from_waypoint_suite
@@ -109,8 +110,6 @@ def test_reference_suites_load_and_step_with_the_oracle(tmp_path):
         assert abs(st["x"][e * 8 + 1] - (-55.70970916748047)) < 1e-4 and st["v"][e * 8 + 1] == 0.0
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_DATA, "validation_cases.yml")),
-                    reason="reference data files are only present in the build container")
 def test_committed_validation_fixture_equals_the_reference_file(tmp_path):
     """the committed fixture is the reference's data, value for value (and the 100-case training suite still loads)"""
     from tests.golden_util import write_validation_suite_yaml
@@ -258,12 +257,22 @@ def test_world_save_load_round_trip(tmp_path):
         assert a.dtype == w2.arrays[k].dtype and a.tobytes() == w2.arrays[k].tobytes(), k
 
 
-REF_BG = "/root/reference/torchdriveenv/resources/background_traffic"
+def _reference_background_traffic(dst):
+    """the reference's background-traffic directory written back file by file from tests/golden/reference_background_traffic.json.gz
+    (each document without the recurrent states, which load_background_traffic drops)"""
+    import gzip
+    import json
+
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "reference_background_traffic.json.gz"), "rt") as f:
+        docs = json.load(f)
+    os.makedirs(dst)
+    for n, doc in docs.items():
+        with open(os.path.join(dst, n), "w") as f:
+            json.dump(doc, f)
+    return dst
 
 
-@pytest.mark.skipif(not (os.path.isdir(REF_BG) and os.path.exists(os.path.join(REF_DATA, "validation_cases.yml"))),
-                    reason="reference data not present (GPU box)")
-def test_reference_background_traffic_files_populate_the_world():
+def test_reference_background_traffic_files_populate_the_world(tmp_path):
     """the reference's own 75 background-traffic files parse, and validation case 2 (Town03) gets its free slots
     filled with agents that are > 100 m from the ego start"""
     import random
@@ -272,6 +281,7 @@ def test_reference_background_traffic_files_populate_the_world():
     from torchdriveenv_amd.env import world_from_waypoint_suite
     from torchdriveenv_amd.loaders import load_background_traffic, load_waypoint_suite_data, pick_background_traffic
 
+    REF_BG = _reference_background_traffic(str(tmp_path / "background_traffic"))
     files = sorted(os.listdir(REF_BG))
     assert len(files) == 75
     for n in files[::9]:
