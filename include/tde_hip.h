@@ -105,6 +105,25 @@ TDE_API int tde_env_rollout(const tde_config *cfg, const tde_world *world, const
 TDE_API int tde_render_ego(const tde_config *cfg, const tde_world *world, const tde_state *state,
                            const tde_render *render, void *stream);
 
+/* Camera pose of one tde_render_scene view, world coordinates: the view of env `env` is centred on (x, y), image rows up along
+ * heading psi. */
+typedef struct tde_scene_view {
+    int32_t env;
+    float x, y, psi;
+} tde_scene_view;
+
+/* BirdviewRecordingWrapper(res=(H, W), fov) frames (render_mode="video", gym_env.py:295-297; GymEnv.close writes them,
+ * :172-176): views[i] (DEVICE [n_views]) -> out[i] = uint8 [3][H][W] (DEVICE [n_views][3][H][W]), any H, W in [1, 4096], any
+ * camera pose.  Pixels are tde_render_ego's specification (tde_abi.h, oracle tde_render_env) with the camera pose in place of the
+ * ego's: u = (H/2 - 0.5) - r, v = (W/2 - 0.5) - c, world = cam + u (ax, ay) + v (bx, by), res = fov / W; layers, palette,
+ * waypoint discs (the env's target_idx), stop-line colours (the env's steps), agent draw order and flags (TDE_RENDER_*) as there;
+ * slot 0 is painted as the ego whatever the camera.  A view whose env is outside [0, B) is written as zeros.  n_views == 0 is a
+ * no-op.  Rejected: H or W outside [1, 4096], fov not finite or <= 0, n_views < 0, views or out NULL with n_views > 0.
+ * One wavefront per 32 x 128 tile of a view. */
+TDE_API int tde_render_scene(const tde_config *cfg, const tde_world *world, const tde_state *state,
+                             const tde_scene_view *views, int32_t n_views, int32_t H, int32_t W, float fov, int32_t flags,
+                             uint8_t *out, void *stream);
+
 /* The re-spawn of the envs an SB3-style auto-reset has just seen finish, and their first observation, in ONE call: tde_env_reset
  * for the envs with mask[e] != 0 (uint8 [B], required) followed by tde_render_ego of exactly those views - their newest frame
  * rendered again in place, their older stack frames blanked (render->fresh and render->only are set to `mask` by the call, so its entries must be 0 or 1: the rasteriser reads bits 0-1 of a fresh byte; phase

@@ -120,6 +120,11 @@ class TdeRender(C.Structure):
                 ("layers", _p), ("phase", C.c_int32), ("flags", C.c_int32), ("fresh", _p), ("only", _p)]
 
 
+class TdeSceneView(C.Structure):
+    """tde_scene_view (tde_hip.h): camera pose of one tde_render_scene view"""
+    _fields_ = [("env", C.c_int32), ("x", C.c_float), ("y", C.c_float), ("psi", C.c_float)]
+
+
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7
 RENDER_LEFT_HANDED, RENDER_PLAIN_EGO = 1 << 0, 1 << 1

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("TDE_HIP_LIB") or os.path.join(_PKG, "libtde_hip.so") 
 # every symbol include/tde_hip.h declares
 SYMBOLS = ["tde_abi_version", "tde_last_error", "tde_kernel_override", "tde_kinematics_step", "tde_compute_collision",
            "tde_compute_offroad", "tde_kin_collide_step", "tde_waypoint_reward", "tde_env_reset", "tde_env_step",
-           "tde_env_rollout", "tde_render_ego", "tde_env_reset_render", "tde_env_step_render", "tde_state_obs", "tde_ego_infractions", "tde_env_post_step", "tde_first_gaps", "tde_grid_build", "tde_grid_free"]
+           "tde_env_rollout", "tde_render_ego", "tde_render_scene", "tde_env_reset_render", "tde_env_step_render", "tde_state_obs", "tde_ego_infractions", "tde_env_post_step", "tde_first_gaps", "tde_grid_build", "tde_grid_free"]
 
 _lib = None
 
@@ -49,6 +49,7 @@ def load():
     L.tde_env_step.argtypes = [cfgp, wp, sp, vp]
     L.tde_env_rollout.argtypes = [cfgp, wp, sp, C.POINTER(_abi.TdeRollout), vp]
     L.tde_render_ego.argtypes = [cfgp, wp, sp, C.POINTER(_abi.TdeRender), vp]
+    L.tde_render_scene.argtypes = [cfgp, wp, sp, vp, i32, i32, i32, f32, i32, vp, vp]
     L.tde_env_step_render.argtypes = [cfgp, wp, sp, C.POINTER(_abi.TdeRender), C.POINTER(vp), i32]
     L.tde_env_reset_render.argtypes = [cfgp, wp, sp, vp, C.POINTER(_abi.TdeRender), vp]
     L.tde_state_obs.argtypes = [wp, sp, vp, vp]

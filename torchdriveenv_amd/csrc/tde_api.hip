@@ -3,6 +3,7 @@
 // units (tde_step_*.hip, tde_rollout_*.hip: tde_host.h lists their launchers).  No torch types anywhere: plain device pointers,
 // sizes and a hipStream_t.
 #define TDE_TU_API 1
+#include <cfloat>
 #include <mutex>
 #include <vector>
 #include "tde_kernels.h"
@@ -440,6 +441,21 @@ int tde_render_ego(const tde_config *cfg, const tde_world *world, const tde_stat
     else tde::render_views_kernel<0><<<ng, tde::kWave * tde::kViewsPerGroup, 0, (hipStream_t)stream>>>(ra, st->B);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail("tde_render_ego", e);
+}
+
+int tde_render_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_scene_view *views,
+                     int32_t n_views, int32_t H, int32_t W, float fov, int32_t flags, uint8_t *out, void *stream)
+{
+    int rc = check_env_args("tde_render_scene", cfg, world, st);
+    if (rc) return rc;
+    if (H < 1 || H > 4096 || W < 1 || W > 4096) return bad("tde_render_scene: H and W must be in [1, 4096]");
+    if (!(fov > 0.0f) || !(fov <= FLT_MAX)) return bad("tde_render_scene: fov must be finite and positive");
+    if (n_views < 0) return bad("tde_render_scene: n_views must be >= 0");
+    if (n_views > 0 && (!views || !out)) return bad("tde_render_scene: views or out is NULL");
+    if (!world->cell_cls2 || !world->cell_sub || !world->cell_word || !world->cell_tri || !world->cell_coarse)
+        return bad("tde_render_scene: the world has no grid index tables");
+    if (n_views == 0) return 0;
+    return tde_host::launch_render_scene(cfg, world, st, views, n_views, H, W, fov, flags, out, stream);
 }
 
 int tde_env_reset_render(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask,

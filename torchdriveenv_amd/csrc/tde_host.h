@@ -95,6 +95,9 @@ int launch_rollout_wide(const tde::StepArgs *args, const tde_config *cfg, const 
 int launch_rollout_duo(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, void *stream);
 // tde_rollout_solo.hip: env_rollout_kernel<A <= 128, LIGHTS>
 int launch_rollout_solo(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, void *stream);
+// tde_render_scene.hip: render_scene_kernel (tde_render_scene; arguments checked by the caller)
+int launch_render_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_scene_view *views,
+                        int32_t n_views, int32_t H, int32_t W, float fov, int32_t flags, uint8_t *out, void *stream);
 
 }  // namespace tde_host
 

@@ -20,4 +20,5 @@
 #include "tde_rollout_trio.hip"
 #include "tde_rollout_duo.hip"
 #include "tde_rollout_solo.hip"
+#include "tde_render_scene.hip"
 #endif

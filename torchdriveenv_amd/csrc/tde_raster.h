@@ -108,6 +108,22 @@ TDE_DEV void wave_phase() { asm volatile("" ::: "memory"); }
 
 // (lane_prefix: tde_device.h)
 
+// A tile of a larger view (tde_render_scene: tde_render_scene.hip).  raster_view<.., TILE = true> renders kSceneTileH x kSceneTileW
+// pixels - one 128-byte line per plane row - of a view of any size: the same stages on a plane of the tile's size, with
+//   * u = hu - r, v = hv - c for tile pixel (r, c), hu = (H/2 - 0.5) - r0 and hv = (W/2 - 0.5) - c0 of the WHOLE view (small
+//     half-integers: u is exactly the specification's u of pixel (r0 + r, c0 + c), so the pixels are those of the full view);
+//   * objects culled to the tile's circumscribed circle instead of the view circle;
+//   * the colours stored at the tile's place in the view, masked to the view's rows and columns (edge tiles).
+constexpr int kSceneTileH = 32, kSceneTileW = 128;
+static_assert(kSceneTileH * kSceneTileW == kRasterMaxPix, "a tile fills the LDS plane");
+struct RasterTile {
+    float hu, hv;                                // u = hu - r, v = hv - c
+    int vh, vw;                                  // rows / columns of the tile inside the view
+    int ld;                                      // row stride of the view (= its W)
+    int64_t plane;                               // channel stride of the view (= H * W)
+    bool vec;                                    // rows of the view are 16-byte aligned: whole chunks in one 16-byte store
+};
+
 // per-view pixel maps
 struct RasterView {
     float ex, ey, ax, ay, bx, by;                // (u, v) -> world (the specification)
@@ -280,21 +296,69 @@ TDE_DEV void raster_expand(const uint4 &v, uint8_t *frame, int plane, int i)
     }
 }
 
+// 16 layer bytes -> 16 colour bytes of channel ch (the palette of raster_expand)
+TDE_DEV uint4 raster_rgb16(const uint4 &v, int ch)
+{
+    const uint32_t BG[3] = {TDE_RGB_BACKGROUND}, ROAD[3] = {TDE_RGB_ROAD}, WP[3] = {TDE_RGB_WAYPOINT},
+                   NPC[3] = {TDE_RGB_NPC}, EGO[3] = {TDE_RGB_EGO}, SRED[3] = {TDE_RGB_STOP_RED}, SGO[3] = {TDE_RGB_STOP_GO};
+    const uint32_t lo = BG[ch] | (ROAD[ch] << 8) | (WP[ch] << 16) | (NPC[ch] << 24);
+    const uint32_t hi = EGO[ch] | (SRED[ch] << 16) | (SGO[ch] << 24);
+    return make_uint4(__builtin_amdgcn_perm(hi, lo, v.x), __builtin_amdgcn_perm(hi, lo, v.y), __builtin_amdgcn_perm(hi, lo, v.z),
+                      __builtin_amdgcn_perm(hi, lo, v.w));
+}
+
+// a tile's colours -> its place in the view (`out` = the view's pixel (r0, c0) of channel 0), from the layer plane in LDS or, with
+// plane == nullptr, zeros.  Lane l stores chunks l + 64 k: 16 pixels of tile row i / 8, so eight consecutive lanes write one
+// 128-byte line of a plane row.  Chunks that cross the view's last column (or a view whose rows are not 16-byte aligned) go byte
+// by byte.
+TDE_DEV void raster_tile_out(const RasterTile &T, uint8_t *out, const uint32_t *plane, int lane)
+{
+#pragma unroll
+    for (int k = 0; k < kSceneTileH * kSceneTileW / 16 / 64; ++k) {
+        const int i = lane + 64 * k, r = i >> 3, c = (i & 7) << 4;
+        if (r >= T.vh || c >= T.vw) continue;
+        const uint4 v = plane ? reinterpret_cast<const uint4 *>(plane)[i] : make_uint4(0u, 0u, 0u, 0u);
+        uint8_t *dst = out + (int64_t)r * T.ld + c;
+        const bool whole = T.vec && c + 16 <= T.vw;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const uint4 o = plane ? raster_rgb16(v, ch) : v;
+            uint8_t *d = dst + ch * T.plane;
+            if (whole) {
+                u32x4_t t;
+                t.x = o.x; t.y = o.y; t.z = o.z; t.w = o.w;
+                __builtin_nontemporal_store(t, reinterpret_cast<u32x4_t *>(d));
+            } else {
+                for (int b = 0; b < 16 && c + b < T.vw; ++b) {
+                    const uint32_t w = b < 8 ? (b < 4 ? o.x : o.y) : (b < 12 ? o.z : o.w);
+                    d[b] = (uint8_t)(w >> (8 * (b & 3)));
+                }
+            }
+        }
+    }
+}
+
 // One view by one wavefront; every lane of the wavefront calls it, converged.  `agent.fetch(j)` -> Raw (the loads of slot j of
 // the env, slot 0 = the ego), `agent.unpack(raw, x, y, c, s, hl, hw)` -> present: its pose and half extents.
 // SIZE: 64 = the image is 64 x 64 (the reference's observation, every stride a constant); 0 = J.H x J.W.
-template <int SIZE, typename AgentSrc>
-TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent, int *dbg = nullptr)
+// TILE: the kSceneTileH x kSceneTileW tile `T` of a larger view (RasterTile; J.H x J.W = the tile, J.out = the view's pixel at
+// the tile's corner).
+template <int SIZE, typename AgentSrc, bool TILE = false>
+TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent, int *dbg = nullptr, const RasterTile &T = RasterTile{})
 {
     const int lane = (int)(threadIdx.x & 63u);
-    const int H = SIZE ? SIZE : J.H, W = SIZE ? SIZE : J.W, plane = H * W;
+    const int H = TILE ? kSceneTileH : (SIZE ? SIZE : J.H), W = TILE ? kSceneTileW : (SIZE ? SIZE : J.W), plane = H * W;
     // the block pyramid covers the image rounded up to multiples of 8 (tde_render_ego checks that it fits the plane); the
     // pixels of the padding are computed like any other and never leave LDS
     const int Wp = (W + 7) & ~7, Hp = (H + 7) & ~7;
-    const RasterView V = raster_view_maps(J);
+    RasterView V = raster_view_maps(J);
+    if (TILE) { V.hu = T.hu; V.hv = T.hv; }
     uint8_t *p8 = reinterpret_cast<uint8_t *>(S.plane);
     const int ego_layer = (J.flags & TDE_RENDER_PLAIN_EGO) ? TDE_LAYER_NPC : TDE_LAYER_EGO;
     const float rview = 0.75f * J.res * (float)(H > W ? H : W) + 1.0f;        // view circle: the culled lists are supersets
+    // centre of the cull circle: the ego, or the centre of the tile (its radius rview covers the tile's half diagonal)
+    float ccx = J.ex, ccy = J.ey;
+    if (TILE) raster_world(V, V.hu - 0.5f * (float)(H - 1), V.hv - 0.5f * (float)(W - 1), ccx, ccy);
 
     // the first 64 candidates of every kind of object (stop lines, waypoints, agent slots) are fetched together (one memory round
     // trip instead of three).  (Issued earlier - ahead of the last MIXED-pixel resolution - their ten registers spill: 21 VGPR
@@ -488,7 +552,7 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
                     la = reinterpret_cast<const float4 *>(J.stoplines + q)[0];
                     lb = reinterpret_cast<const float4 *>(J.stoplines + q)[1];
                 }
-                const float dx = la.x - J.ex, dy = la.y - J.ey, rr = rview + (lb.x + lb.y);
+                const float dx = la.x - ccx, dy = la.y - ccy, rr = rview + (lb.x + lb.y);
                 keep = dx * dx + dy * dy <= rr * rr;
                 box_coeffs(V, la.x, la.y, la.z, la.w, P, Q);
                 P.w = lb.x; Q.w = lb.y;
@@ -507,7 +571,7 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
             double2 t = wp0;
             if (k0 > J.ti) t = reinterpret_cast<const double2 *>(J.wp)[k];
             const float tx = (float)t.x, ty = (float)t.y;
-            const float dx = tx - J.ex, dy = ty - J.ey, rr = rview + TDE_WAYPOINT_RADIUS;
+            const float dx = tx - ccx, dy = ty - ccy, rr = rview + TDE_WAYPOINT_RADIUS;
             keep = dx * dx + dy * dy <= rr * rr;
             dx0 = V.ex - tx; dy0 = V.ey - ty;
             span = raster_span(J, V, tx, ty, TDE_WAYPOINT_RADIUS, TDE_WAYPOINT_RADIUS);
@@ -546,7 +610,7 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
             const bool ego = j0 == 0 && lane == 0;
             bool keep = ego && pres;                                          // (an absent ego is not painted: the oracle skips it)
             if (pres && !ego) {
-                const float dx = x - J.ex, dy = y - J.ey, rr = rview + (hl + hw);
+                const float dx = x - ccx, dy = y - ccy, rr = rview + (hl + hw);
                 keep = dx * dx + dy * dy <= rr * rr;
             }
             float4 P, Q;
@@ -561,6 +625,10 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
 
     // ---- layers -> colours, streamed out --------------------------------------------------------------------------
     wave_phase();
+    if (TILE) {
+        if (!(TDE_RASTER_SKIP & 8)) raster_tile_out(T, J.out, S.plane, lane);
+        return;
+    }
     // 16 layer bytes of flat pixel chunk i: one 16-byte read when the plane is not padded, else four 4-byte reads (W is
     // a multiple of 4, so a dword never straddles two image rows)
     auto chunk = [&](int i) -> uint4 {

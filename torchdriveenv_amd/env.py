@@ -8,6 +8,7 @@
 
 What stays in Python is only argument marshalling; every number comes from libtde_hip.so.  There is no CPU fallback.
 """
+import dataclasses
 import math
 import warnings
 
@@ -17,6 +18,7 @@ import torch
 from . import _abi, ops
 from .config import EnvConfig, WaypointSuite, render_flags, to_tde_config, validate
 from .state import EnvState
+from .video import VideoRecorder
 from .world import World, assemble_world, check_threshold, corridor_mesh, effective_offroad_distance
 
 try:  # optional: neither gymnasium nor SB3 ships in this image
@@ -649,6 +651,14 @@ class BatchedWaypointEnv:
         on first access (a training loop that never reads `psi_smoothness` does not pay for it)"""
         return _LazyInfo(self.state, self.num_envs, self.A, magnitudes=self._mag)
 
+    def render_scene(self, envs=None, H=1024, W=1024, fov=500.0, camera="map", out=None):
+        """uint8 [n, 3, H, W] on the device: view i of env envs[i] (default: every env) at any H, W in [1, 4096] from `camera` ("map":
+        the centre of the env's map, heading pi/2 - an UNPINNED reading of torchdrivesim's default camera; "ego": slot 0's pose; or a
+        float32 tensor [n, 3] of (x, y, psi)), with this env's render flags, on the current stream: the frames of the reference's
+        render_mode="video" (BirdviewRecordingWrapper, ref gym_env.py:295-297), which this batched API does not take as a mode
+        (ops.render_scene)."""
+        return ops.render_scene(self.tde_cfg, self.dworld, self.state, envs, H, W, fov, camera, out, flags=self._rflags)
+
     def render(self):
         """(B, H, W, 3) uint8 of the current ego views (ref gym_env.py:152-155)"""
         img = ops.render_ego(self.tde_cfg, self.dworld, self.state, self._res, self._res, self._fov, 1, flags=self._rflags)
@@ -1013,15 +1023,36 @@ class WaypointSuiteEnv(_GymEnvBase):
 
     metadata = {"render_modes": ["video", "rgb_array"], "render_fps": 10}
 
-    def __init__(self, cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None):
+    def __init__(self, cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None,
+                 video_camera="map"):
+        """render_mode="video": every reset() and step() records a video_res x video_res frame at video_fov metres across (the
+        reference's BirdviewRecordingWrapper, gym_env.py:295-297) from `video_camera` ("map": the centre of the map, heading pi/2;
+        "ego"; or (x, y, psi)); get_birdviews() returns them, close() writes video_filename (video.save_video)."""
         self.config = cfg
+        if cfg.render_mode == "video":               # the batched env renders rgb_array; the frames are recorded here
+            cfg = dataclasses.replace(cfg, render_mode="rgb_array")
         # info["offroad"] / info["collision"] carry the MAGNITUDES of compute_offroad() / compute_collision(), as the reference's
         # get_info reports them (ref gym_env.py:427-428; Monitor logs them, examples/rl_training.py:128)
         self._env = BatchedWaypointEnv(cfg, data, num_envs=1, agents_per_env=agents_per_env, obs_mode="birdview",
                                        frame_stack=1, auto_reset=False, info_magnitudes=True, road_meshes=road_meshes,
                                        traffic_lights=traffic_lights, start_headings=start_headings)
         self.torch_device = self._env.torch_device
-        self.render_mode = cfg.render_mode
+        self.render_mode = self.config.render_mode
+        self._video = None
+        if self.render_mode == "video":
+            res = int(self.config.video_res)
+            self._video = VideoRecorder(self.config.video_filename, fps=self.metadata["render_fps"])
+            self._video_res, self._video_fov = res, float(self.config.video_fov)
+            if isinstance(video_camera, str):
+                if video_camera not in ("map", "ego"):
+                    raise ValueError("video_camera must be 'map', 'ego' or (x, y, psi)")
+                self._video_cam = video_camera
+            else:
+                self._video_cam = torch.tensor([list(video_camera)], dtype=torch.float32, device=self.torch_device).reshape(1, 3)
+            self._video_envs = torch.zeros(1, dtype=torch.int32, device=self.torch_device)
+            self._video_views = None
+            self._video_dev = torch.empty((1, 3, res, res), dtype=torch.uint8, device=self.torch_device)
+            self._video_pin = torch.empty((1, 3, res, res), dtype=torch.uint8, pin_memory=True)
         self.max_environment_steps = cfg.max_environment_steps
         self.action_space = _box(ACTION_LOW, ACTION_HIGH)
         self.observation_space = _box(0, 255, (3, 64, 64), np.uint8)
@@ -1044,7 +1075,29 @@ class WaypointSuiteEnv(_GymEnvBase):
 
     def reset(self, seed=None, options=None):                       # ref gym_env.py:319-349
         obs = self._env.reset()
-        return obs.cpu().numpy().reshape(1, 1, 3, 64, 64).astype(np.uint8), {}
+        if self._video is not None:
+            self._video.start()                                      # (the reference builds a new recording wrapper per reset)
+            self._video_views = None                                 # (the env's map may have changed)
+            self._record_frame()
+        obs = obs.cpu().numpy().reshape(1, 1, 3, 64, 64).astype(np.uint8)
+        if self._video is not None:
+            self._video.append(self._video_pin.clone())
+        return obs, {}
+
+    def _record_frame(self):
+        """queue this state's video frame and its copy to the pinned staging buffer (the caller's synchronisation completes it)"""
+        e = self._env
+        v = self._video_views
+        if v is None or (isinstance(self._video_cam, str) and self._video_cam == "ego"):
+            v = ops.scene_views(e.dworld, e.state, self._video_envs, self._video_cam)
+            self._video_views = v                                    # (a map or fixed camera holds until the next reset)
+        ops.render_scene_views(e.tde_cfg, e.dworld, e.state, v, self._video_res, self._video_res, self._video_fov, self._video_dev,
+                               flags=e._rflags)
+        self._video_pin.copy_(self._video_dev, non_blocking=True)
+
+    def get_birdviews(self):
+        """the frames recorded since the last reset (render_mode="video"): uint8 CPU tensors [1, 3, video_res, video_res]"""
+        return self._video.frames if self._video is not None else []
 
     def step(self, action):                                         # ref gym_env.py:369-389
         """one timestep.  Everything the reference's step returns crosses the bus in TWO asynchronous copies - the observation
@@ -1057,7 +1110,11 @@ class WaypointSuiteEnv(_GymEnvBase):
         if self._obs_pin is None:
             self._obs_pin = torch.empty((1, 3, 64, 64), dtype=torch.uint8, pin_memory=True)
         self._obs_pin.copy_(obs, non_blocking=True)
+        if self._video is not None:
+            self._record_frame()                                     # (its copy is ahead of the synchronisation too)
         out = st.fetch_outputs()                                     # (the one synchronisation: the observation copy is ahead of it)
+        if self._video is not None:
+            self._video.append(self._video_pin.clone())
         mag = out["magnitudes"][0]
         t11 = lambda v: torch.tensor([[v]], dtype=torch.float32)    # noqa: E731
         trunc = bool(out["truncated"][0])
@@ -1075,7 +1132,10 @@ class WaypointSuiteEnv(_GymEnvBase):
         raise NotImplementedError
 
     def close(self):
-        pass
+        """render_mode="video": writes video_filename from the frames of the current episode when there are more than one (ref
+        gym_env.py:172-176; video.VideoRecorder for the one-frame case)"""
+        if self._video is not None:
+            self._video.close()
 
     def seed(self, seed=None):
         pass
@@ -1121,13 +1181,14 @@ class SingleAgentWrapper(_GymWrapperBase):
         self.env.close()
 
 
-def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None):
+def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None, video_camera="map"):
     """what gym.make('torchdriveenv-v0', args={'cfg': cfg, 'data': data}) returns in the reference (ref __init__.py:10).
     `road_meshes`, `traffic_lights`, `start_headings`: what the reference takes from torchdrivesim's map config of the location
     (`find_map_config`: road mesh ref gym_env.py:184, stop lines + light controller :181-189, lanelet directions :359) - see
-    world_from_waypoint_suite"""
+    world_from_waypoint_suite.  `video_camera`: the camera of render_mode="video" frames (WaypointSuiteEnv)"""
     return SingleAgentWrapper(WaypointSuiteEnv(cfg=cfg, data=data, agents_per_env=agents_per_env, road_meshes=road_meshes,
-                                               traffic_lights=traffic_lights, start_headings=start_headings))
+                                               traffic_lights=traffic_lights, start_headings=start_headings,
+                                               video_camera=video_camera))
 
 
 if gym is not None:  # pragma: no cover

@@ -238,6 +238,73 @@ def render_ego(cfg, dworld, state, H=64, W=64, fov=35.0, n_stack=1, out=None, la
     return out
 
 
+def scene_views(dworld, state, envs, camera="map"):
+    """int32 [n, 4] device tensor of tde_scene_view records (env, x, y, psi; the pose as float32 bits) of the views of envs `envs`
+    (int64 / int32 device tensor [n]) - see render_scene for `camera`.  No host synchronisation."""
+    dev = state.device
+    n = envs.numel()
+    v = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    v[:, 0] = envs
+    pose = v[:, 1:].view(torch.float32)
+    if isinstance(camera, str) and camera == "map":
+        if dworld.scene_camera is None:
+            raise ValueError("camera='map' needs a DeviceWorld made by World.to_device (its scene_camera table)")
+        pose.copy_(dworld.scene_camera[state["scn"][envs.long()].long()])
+    elif isinstance(camera, str) and camera == "ego":
+        g0 = envs.long() * state.A                     # slot 0 of each env: the state's own bits
+        pose[:, 0] = state["x"][g0]
+        pose[:, 1] = state["y"][g0]
+        pose[:, 2] = state["psi"][g0]
+    elif torch.is_tensor(camera):
+        if camera.dtype != torch.float32 or tuple(camera.shape) != (n, 3):
+            raise ValueError(f"camera must be 'map', 'ego' or a float32 tensor [{n}, 3] of (x, y, psi)")
+        pose.copy_(camera.to(dev))
+    else:
+        raise ValueError(f"camera must be 'map', 'ego' or a float32 tensor [{n}, 3] of (x, y, psi)")
+    return v
+
+
+def render_scene(cfg, dworld, state, envs=None, H=1024, W=1024, fov=500.0, camera="map", out=None, flags=0, check_envs=True):
+    """BirdviewRecordingWrapper-style frames (render_mode="video", ref gym_env.py:295-297): uint8 [n, 3, H, W] on device, view i of
+    env envs[i] (default: every env, in order) seen from `camera`, any H, W in [1, 4096] (tde_render_scene), on the current stream.
+    camera: "map" - the centre of the bounding box of the env's map mesh, heading pi/2 (our reading of torchdrivesim, whose
+    camera_xy defaults to the world centre and camera_psi to pi/2: UNPINNED, that package is not available here); "ego" - slot 0's
+    pose, gathered on the device; or a float32 tensor [n, 3] of (x, y, psi).  The pixels are render_ego's specification with the
+    camera pose in place of the ego's; slot 0 is painted as the ego whatever the camera.  flags: _abi.RENDER_*.
+    `envs` out of [0, B) raise (check_envs=False skips that check - it reads `envs` on the host - for indices known to be valid;
+    the kernel then writes such a view as zeros)."""
+    dev = state.device
+    if envs is None:
+        envs = torch.arange(state.B, dtype=torch.int32, device=dev)
+    envs = torch.as_tensor(envs, dtype=torch.int32).reshape(-1)
+    if check_envs and envs.numel() and not bool(((envs >= 0) & (envs < state.B)).all()):
+        raise ValueError(f"envs must be in [0, {state.B})")
+    envs = envs.to(dev)
+    n = envs.numel()
+    if not (1 <= int(H) <= 4096 and 1 <= int(W) <= 4096):
+        raise ValueError("H and W must be in [1, 4096]")
+    if not (np.isfinite(fov) and fov > 0):
+        raise ValueError("fov must be finite and positive")
+    if out is None:
+        out = torch.empty((n, 3, int(H), int(W)), dtype=torch.uint8, device=dev)
+    _chk(out, torch.uint8, n * 3 * int(H) * int(W), "out")
+    if n == 0:
+        return out
+    return render_scene_views(cfg, dworld, state, scene_views(dworld, state, envs, camera), H, W, fov, out, flags)
+
+
+def render_scene_views(cfg, dworld, state, views, H, W, fov, out, flags=0):
+    """tde_render_scene of prepared views (scene_views: int32 [n, 4] device tensor) into `out` (uint8 [n, 3, H, W]): the launch
+    alone, for callers that keep their views across calls (WaypointSuiteEnv's video frames)"""
+    n = views.shape[0]
+    po = _chk(out, torch.uint8, n * 3 * int(H) * int(W), "out")
+    pv = _chk(views, torch.int32, n * 4, "views")
+    dev = state.device
+    _lib.check(_call(dev, _lib.load().tde_render_scene, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), pv, n,
+                     int(H), int(W), float(fov), int(flags), po, _lib.current_stream(dev)), "tde_render_scene")
+    return out
+
+
 def fork_streams(streams, device=None):
     """order `streams` (torch.cuda.Stream) after the work already queued on the current stream (before the first
     env_step_render call / after the action tensor was produced)"""

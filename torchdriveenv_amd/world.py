@@ -238,6 +238,20 @@ def corridor_mesh(polylines, width=12.0, seg_len=6.0, joint_radius=None):
 # ------------------------------------------------------------------------------------------------
 # World container
 # ------------------------------------------------------------------------------------------------
+def map_centres(maps, tri):
+    """float32 [n_maps, 2]: the centre of the bounding box of every map's mesh (the default camera of render_scene: our reading of
+    torchdrivesim, whose `camera_xy` defaults to the world centre - UNPINNED, that package is not available here); (0, 0) for a map
+    without triangles.  Light-group descriptors share their mesh's triangles, so they share its centre."""
+    maps = np.asarray(maps)
+    tri = np.asarray(tri, np.float32).reshape(-1, 3, 2)
+    out = np.zeros((len(maps), 2), np.float32)
+    for m in range(len(maps)):
+        t = tri[int(maps["tri_base"][m]):int(maps["tri_base"][m]) + int(maps["n_tri"][m])].reshape(-1, 2).astype(np.float64)
+        if len(t):
+            out[m] = 0.5 * (t.min(0) + t.max(0))
+    return out
+
+
 class World:
     """Host copy of every static table the step path reads (numpy, dtypes of _abi.WORLD_DTYPES)."""
 
@@ -249,6 +263,7 @@ class World:
         # check_threshold() wherever a threshold meets a World.  None: unknown (tables assembled by hand).
         self.threshold = None if threshold is None else float(threshold)
         self.has_lights = bool(np.asarray(arrays["maps"])["cycle_steps"].max() > 0)
+        self.map_centre = map_centres(self.arrays["maps"], self.arrays["tri"])
         # zero-length tables still need a valid pointer
         for k, a in self.arrays.items():
             if a.size == 0:
@@ -284,10 +299,20 @@ class World:
             else:
                 t = torch.from_numpy(a.copy())
             tens[k] = t.to(device)
-        return DeviceWorld(tens, self.ints, self.threshold)
+        dw = DeviceWorld(tens, self.ints, self.threshold)
+        dw.scene_camera_host = self.scene_cameras()       # (uploaded at the first render_scene(camera="map"), not here)
+        return dw
 
     def map_of_scn(self):
         return np.ascontiguousarray(self.arrays["scn"]["map"])
+
+    def scene_cameras(self):
+        """float32 [n_scn, 3]: the "map" camera of every scenario's map (render_scene): the centre of the bounding box of its mesh,
+        heading pi/2"""
+        cam = np.empty((self.n_scn, 3), np.float32)
+        cam[:, :2] = self.map_centre[self.map_of_scn()]
+        cam[:, 2] = np.float32(math.pi / 2)
+        return cam
 
     def save(self, path):
         """cache the assembled tables (grid indexes of town-sized meshes take seconds per scenario to build)"""
@@ -373,6 +398,18 @@ class DeviceWorld:
         self.ints = dict(ints)
         self.threshold = threshold
         self.struct = _abi.fill_world_struct(tensors, ints)
+        self.scene_camera_host = None   # float32 [n_scn, 3] "map" camera of every scenario (World.scene_cameras; render_scene)
+        self._scene_camera = None
+
+    @property
+    def scene_camera(self):
+        """the "map" cameras on the device, uploaded on first use: a world that never renders a scene view allocates nothing more
+        than its tables"""
+        if self._scene_camera is None and self.scene_camera_host is not None:
+            import torch
+
+            self._scene_camera = torch.from_numpy(self.scene_camera_host).to(self.tensors["maps"].device)
+        return self._scene_camera
 
 
 def assemble_world(meshes, scenarios, A, threshold=0.5, cell=0.5, lights=None, light_groups=None, near_range=NEAR_RANGE):
