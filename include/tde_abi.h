@@ -418,6 +418,40 @@ typedef struct tde_render {
 } tde_render;
 #define TDE_LAYER_BLANK 5       /* palette entry (0, 0, 0): a frame that has not been rendered yet */
 
+/* Near-field spawner (tde_near_field_spawn, include/tde_hip.h): the stand-in for the reference's iai_conditional_initialize, which
+ * tops every episode up with traffic within INITIALIZE_FOV = 120 m of the ego (gym_env.py:232-238, iai.py:6-60).  Per scenario a
+ * table of candidate spawn poses built once on the host, every candidate on the drivable surface; two conflict structures make the
+ * per-episode work integer set arithmetic plus one distance to the ego per candidate:
+ *   nbr / nbr_n   the other candidates of the scenario whose boxes, each inflated by margin / 2, overlap its own (exact float64 SAT)
+ *   fixed         1: it overlaps a present spawn agent of the scenario (scenario agents, kept background) at its spawn pose */
+#define TDE_NF_MAX_CAND 1024    /* candidates per scenario */
+#define TDE_NF_MAX_NBR  32      /* neighbours per candidate */
+#define TDE_NF_TAG      0x4E46u /* fourth Philox counter word of the spawner's draws (the reset's is 0x7DE) */
+
+typedef struct tde_nf_cand {    /* 48 bytes: three 16-byte loads */
+    float x, y, psi;            /* pose (box centre, heading) */
+    float c, s;                 /* cos / sin of psi (float64 values rounded once) */
+    float len, wid, lr;         /* attributes: len 4.8-5.5, wid 1.8-2.2, lr 0.82-0.97 (gym_env.py:193-195) */
+    float vdes;                 /* desired speed; the spawn speed is a uniform fraction of it */
+    float _pad[3];
+} tde_nf_cand;
+
+typedef struct tde_near_field {
+    const tde_nf_cand *cand;    /* [S][NC] candidates of scenario s at s * NC, the first n_cand[s] used */
+    const uint16_t *nbr;        /* [S][NC][K] neighbour indices (scenario-local), the first nbr_n of each row used */
+    const uint8_t *nbr_n;       /* [S][NC] */
+    const uint8_t *fixed;       /* [S][NC] 1: conflicts with a present spawn agent of the scenario */
+    const int32_t *n_cand;      /* [S] in [0, NC] */
+    int32_t S;                  /* = tde_world.n_scn */
+    int32_t A;                  /* = tde_state.A */
+    int32_t NC;                 /* candidate row pitch, 1 .. TDE_NF_MAX_CAND */
+    int32_t K;                  /* neighbour row pitch, 1 .. TDE_NF_MAX_NBR */
+    float radius;               /* 120 m: INITIALIZE_FOV (iai.py:8) */
+    float clear_ego;            /* no candidate closer than this to the ego (centre to centre) */
+    int32_t count;              /* 95 (gym_env.py:237: max(95 - n, agent_density)) */
+    int32_t density;            /* the background file's agent_density, else 0 */
+} tde_near_field;
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,21 @@ TDE_API int tde_env_post_step(const tde_config *config, const tde_world *world, 
  * stream capture).  One launch of n_scn * A lanes; up to 64 agent slots per env (the 128-slot kernels do not use the cache: no-op). */
 TDE_API int tde_first_gaps(const tde_config *config, const tde_world *world, void *stream);
 
+/* Near-field traffic at reset (the stand-in for iai_conditional_initialize, gym_env.py:232-238, iai.py:6-60): fills the free slots of
+ * every env with mask[e] != 0 (uint8 [B]; NULL: all envs) from the candidate table `nf` (tde_abi.h: tde_near_field), on the state
+ * as the preceding tde_env_reset / in-place re-spawn left it.  For env e (scenario s = state.scn[e], counter c = state.episode[e],
+ * g = config.env_base + e): free slots = slots 1..A-1 whose spawn record has present == 0, ascending; n_present = present slots,
+ * n_in = those with d2 < radius^2 from the ego; T = max(0, min(free, max(count - n_present, density) - n_in)).  Candidate i has
+ * priority word (i & 3) of philox(seed, g, c, i >> 2, TDE_NF_TAG) and is visited by ascending (priority, i); it is accepted when
+ * it is not fixed, clear_ego^2 <= d2 <= radius^2, no neighbour of it is accepted and fewer than T are.  d2 = dx*dx + dy*dy in
+ * float64 of the float32 positions.  The k-th accepted candidate goes to the k-th free slot: pose, attributes, vdes, v = (float)
+ * (u01(word (i & 3) of philox(seed, g, c, 512 + (i >> 2), TDE_NF_TAG)) * vdes), route_wp = 0, present = 1, collided = offroad = 0;
+ * the env's act_cache key (if any) and the written slots' slot_cache entries are invalidated.  One wavefront per env.
+ * Rejected: NULL cfg / world / state / nf or nf tables, nf.S != world.n_scn, nf.A != state.A (a power of two <= 128), NC or K out
+ * of range.  No allocation, no synchronisation (graph-capturable). */
+TDE_API int tde_near_field_spawn(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_near_field *nf,
+                                 const uint8_t *mask, void *stream);
+
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 
 /* Offroad grid index of ONE drivable mesh - what the simulator prepares once per map from the road mesh it is constructed

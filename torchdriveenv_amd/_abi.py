@@ -125,6 +125,19 @@ class TdeSceneView(C.Structure):
     _fields_ = [("env", C.c_int32), ("x", C.c_float), ("y", C.c_float), ("psi", C.c_float)]
 
 
+class TdeNearField(C.Structure):
+    """tde_near_field (tde_abi.h): the candidate table of tde_near_field_spawn"""
+    _fields_ = [("cand", _p), ("nbr", _p), ("nbr_n", _p), ("fixed", _p), ("n_cand", _p), ("S", C.c_int32), ("A", C.c_int32),
+                ("NC", C.c_int32), ("K", C.c_int32), ("radius", C.c_float), ("clear_ego", C.c_float), ("count", C.c_int32),
+                ("density", C.c_int32)]
+
+
+NF_MAX_CAND, NF_MAX_NBR, NF_TAG = 1024, 32, 0x4E46
+# tde_nf_cand: x, y, psi, c, s, len, wid, lr, vdes + 3 pad words
+NF_CAND_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("psi", "f4"), ("c", "f4"), ("s", "f4"), ("len", "f4"), ("wid", "f4"),
+                          ("lr", "f4"), ("vdes", "f4"), ("_pad0", "f4"), ("_pad1", "f4"), ("_pad2", "f4")])
+assert NF_CAND_DTYPE.itemsize == 48
+
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7
 RENDER_LEFT_HANDED, RENDER_PLAIN_EGO = 1 << 0, 1 << 1

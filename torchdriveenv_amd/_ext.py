@@ -73,6 +73,17 @@ def world_of(dworld):
     return w
 
 
+def near_field_of(dnf):
+    """ext.NearField over the device tensors of a world.DeviceNearField (cached on it)"""
+    h = getattr(dnf, "_ext_nf", None)
+    if h is None:
+        st = dnf.struct
+        dev = dnf.tensors["cand"].device
+        h = load().NearField(dict(dnf.tensors), st.S, st.A, st.NC, st.K, st.radius, st.clear_ego, st.count, st.density, dev.index or 0)
+        dnf._ext_nf = h
+    return h
+
+
 def env_handle(cfg, dworld, state):
     """ext.EnvHandle for (tde_config, DeviceWorld, device EnvState): named tensors in, validated in C++"""
     tens = {k: v for k, v in state.arrays.items() if v is not None}

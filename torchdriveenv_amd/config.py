@@ -124,3 +124,50 @@ def to_tde_config(cfg: EnvConfig, seed: int, flags: int):
         npc_lane_half=sim.npc_lane_half, npc_reach=sim.npc_reach, npc_max_accel=sim.npc_max_accel,
         npc_max_steer=sim.npc_max_steer, flags=flags,
         offroad_threshold_squared=int(bool(sim.offroad_threshold_squared)))
+
+
+@dataclass
+class NearField:
+    """Near-field traffic around the ego at every reset: the local stand-in for the reference's iai_conditional_initialize
+    (ref gym_env.py:232-238, iai.py:6-60), which tops the scene up to max(95 - n, agent_density) agents within INITIALIZE_FOV = 120 m
+    of the ego.  Candidate poses are tabled once per scenario (world.build_near_field); tde_near_field_spawn draws from them per
+    episode.  Not a field of EnvConfig, which mirrors the reference's class name for name: pass it as `near_field=`.
+
+      radius     the spawn radius around the ego [m] (INITIALIZE_FOV)
+      count      the agent count the scene is topped up to (95)
+      density    the lower bound of the agents to add (agent_density); None: the background file's when `background=` is given,
+                 else 0
+      pitch      spacing of the candidate poses along polylines / on the lattice [m]
+      margin     minimum gap between a candidate and any other agent's box [m]
+      clear_ego  minimum centre distance of a candidate from the ego [m]
+      speed      (low, high) range of the candidates' desired speeds [m/s]; the spawn speed is a uniform fraction of it
+      candidates optional hook (location, scenario_index) -> array [n, 3] of (x, y, psi), e.g. lane centrelines"""
+    radius: float = 120.0
+    count: int = 95
+    density: Optional[int] = None
+    pitch: float = 6.0
+    margin: float = 0.5
+    clear_ego: float = 10.0
+    speed: tuple = (5.0, 12.0)
+    candidates: Optional[object] = None
+
+
+def check_near_field(nf, cfg: Optional[EnvConfig] = None):
+    """validate a NearField (and its combination with `cfg`); returns it (a dict is accepted as NearField(**dict))"""
+    if isinstance(nf, dict):
+        nf = NearField(**nf)
+    if not isinstance(nf, NearField):
+        raise TypeError("near_field must be a NearField (or a dict of its fields)")
+    if cfg is not None and cfg.ego_only:
+        raise ValueError("near_field with ego_only=True: the reference spawns no traffic in ego-only mode (gym_env.py:192-198)")
+    if not (nf.radius > 0 and nf.pitch > 0 and nf.margin > 0 and nf.clear_ego >= 0) or not all(
+            map(lambda v: v == v and abs(v) != float("inf"), (nf.radius, nf.pitch, nf.margin, nf.clear_ego))):
+        raise ValueError("near_field: radius, pitch and margin must be finite and > 0, clear_ego finite and >= 0")
+    if int(nf.count) < 0 or (nf.density is not None and int(nf.density) < 0):
+        raise ValueError("near_field: count and density must be >= 0")
+    lo, hi = (float(v) for v in nf.speed)
+    if not (0 <= lo <= hi) or hi == float("inf"):
+        raise ValueError("near_field.speed must be a finite range (low, high) with 0 <= low <= high")
+    if nf.candidates is not None and not callable(nf.candidates):
+        raise ValueError("near_field.candidates must be a callable (location, scenario_index) -> array [n, 3] of (x, y, psi)")
+    return nf

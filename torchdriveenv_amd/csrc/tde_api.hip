@@ -458,6 +458,30 @@ int tde_render_scene(const tde_config *cfg, const tde_world *world, const tde_st
     return tde_host::launch_render_scene(cfg, world, st, views, n_views, H, W, fov, flags, out, stream);
 }
 
+int tde_near_field_spawn(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_near_field *nf,
+                         const uint8_t *mask, void *stream)
+{
+    int rc = check_env_args("tde_near_field_spawn", cfg, world, st);
+    if (rc) return rc;
+    if (!nf) return bad("tde_near_field_spawn: NULL argument");
+    if (!nf->cand || !nf->nbr || !nf->nbr_n || !nf->fixed || !nf->n_cand) return bad("tde_near_field_spawn: a near-field table is NULL");
+    if (nf->S != world->n_scn) {
+        snprintf(g_err, sizeof(g_err), "tde_near_field_spawn: near_field.S (%d) != world.n_scn (%d)", nf->S, world->n_scn);
+        return (int)hipErrorInvalidValue;
+    }
+    if (nf->A != st->A) {
+        snprintf(g_err, sizeof(g_err), "tde_near_field_spawn: near_field.A (%d) != state.A (%d)", nf->A, st->A);
+        return (int)hipErrorInvalidValue;
+    }
+    if (nf->NC < 1 || nf->NC > TDE_NF_MAX_CAND) return bad("tde_near_field_spawn: near_field.NC must be in [1, TDE_NF_MAX_CAND]");
+    if (nf->K < 1 || nf->K > TDE_NF_MAX_NBR) return bad("tde_near_field_spawn: near_field.K must be in [1, TDE_NF_MAX_NBR]");
+    if (!(nf->radius >= 0.0f && nf->radius <= FLT_MAX) || !(nf->clear_ego >= 0.0f && nf->clear_ego <= FLT_MAX))
+        return bad("tde_near_field_spawn: radius and clear_ego must be finite and >= 0");
+    if (!world->spawn) return bad("tde_near_field_spawn: world.spawn is NULL");
+    if (st->B <= 0) return 0;
+    return tde_host::launch_near_field(cfg, world, st, nf, mask, stream);
+}
+
 int tde_env_reset_render(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask,
                          const tde_render *rd, void *stream)
 {

@@ -98,6 +98,9 @@ int launch_rollout_solo(const tde_config *cfg, const tde_world *world, const tde
 // tde_render_scene.hip: render_scene_kernel (tde_render_scene; arguments checked by the caller)
 int launch_render_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_scene_view *views,
                         int32_t n_views, int32_t H, int32_t W, float fov, int32_t flags, uint8_t *out, void *stream);
+// tde_near_field.hip: near_field_kernel (tde_near_field_spawn; arguments checked by the caller)
+int launch_near_field(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_near_field *nf,
+                      const uint8_t *mask, void *stream);
 
 }  // namespace tde_host
 

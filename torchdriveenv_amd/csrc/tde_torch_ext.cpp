@@ -67,7 +67,8 @@ enum { K_ANY = 0, K_AGENT, K_ENV, K_ENV2, K_ENV4, K_ENV8, K_SLOT8, K_ACT };
 const Field kWorldFields[] = {WF(maps, at::kByte), WF(tri, at::kFloat), WF(cell_word, at::kUInt32), WF(cell_tri, at::kFloat),
                               WF(cell_cls2, at::kUInt32), WF(cell_sub, at::kUInt32), WF(cell_coarse, at::kByte), WF(tile_near, at::kUInt32), WF(scn, at::kByte),
                               WF(wp_xy, at::kDouble), WF(spawn, at::kByte), WF(route_xy, at::kFloat), WF(replay_states, at::kFloat),
-                              WF(stoplines, at::kByte), WF(phases, at::kByte), WF(start_psi, at::kFloat), WF(first_gap, at::kUInt32)};
+                              WF(stoplines, at::kByte), WF(phases, at::kByte), WF(start_psi, at::kFloat),
+                              {"first_gap", offsetof(tde_world, first_gap), at::kUInt32, K_ANY, false}};
 #undef WF
 #define SF(n, dt, k, req) {#n, offsetof(tde_state, n), dt, k, req}
 const Field kStateFields[] = {
@@ -146,9 +147,37 @@ class World {
         TORCH_CHECK(bytes_of("route_xy") >= (int64_t)w.n_routes * w.RW * 8, "world.route_xy: smaller than [n_routes][RW][2] float32");
         TORCH_CHECK(bytes_of("replay_states") >= (int64_t)w.n_replay * w.RT * 16, "world.replay_states: smaller than [n_replay][RT][4] float32");
         TORCH_CHECK(w.NH >= 0 && bytes_of("start_psi") >= (int64_t)w.n_scn * w.NH * 4, "world.start_psi: smaller than [n_scn][NH] float32");
-        TORCH_CHECK(bytes_of("first_gap") == (int64_t)w.n_scn * w.A * (int64_t)sizeof(tde_first_gap), "world.first_gap: expected n_scn * A * sizeof(tde_first_gap) bytes");
+        // (first_gap may be absent: a world without the first-step gap cache, as near-field envs use it)
+        TORCH_CHECK(!w.first_gap || bytes_of("first_gap") == (int64_t)w.n_scn * w.A * (int64_t)sizeof(tde_first_gap), "world.first_gap: expected n_scn * A * sizeof(tde_first_gap) bytes");
     }
     tde_world w;
+    at::Device dev;
+
+  private:
+    std::vector<at::Tensor> keep_;
+};
+
+// tde_near_field over named device tensors (kept alive) and its scalar parameters
+#define NF(n, dt) {#n, offsetof(tde_near_field, n), dt, K_ANY, true}
+const Field kNearFieldFields[] = {NF(cand, at::kFloat), NF(nbr, at::kShort), NF(nbr_n, at::kByte), NF(fixed, at::kByte), NF(n_cand, at::kInt)};
+#undef NF
+class NearField {
+  public:
+    NearField(const py::dict &tensors, int64_t S, int64_t A, int64_t NC, int64_t K, double radius, double clear_ego, int64_t count,
+              int64_t density, int64_t device_index)
+        : dev(at::kCUDA, static_cast<c10::DeviceIndex>(device_index))
+    {
+        std::memset(&nf, 0, sizeof(nf));
+        fill_struct(&nf, kNearFieldFields, tensors, 0, 0, dev, keep_, "near_field");
+        TORCH_CHECK(S >= 1 && NC >= 1 && NC <= TDE_NF_MAX_CAND && K >= 1 && K <= TDE_NF_MAX_NBR, "near_field sizes out of range");
+        auto numel = [&](const char *k) { return (int64_t)py::cast<at::Tensor>(tensors[k]).numel(); };
+        TORCH_CHECK(numel("cand") == S * NC * (int64_t)(sizeof(tde_nf_cand) / 4), "near_field.cand: expected [S][NC] tde_nf_cand");
+        TORCH_CHECK(numel("nbr") == S * NC * K, "near_field.nbr: expected [S][NC][K]");
+        TORCH_CHECK(numel("nbr_n") == S * NC && numel("fixed") == S * NC && numel("n_cand") == S, "near_field: nbr_n / fixed [S][NC], n_cand [S]");
+        nf.S = (int32_t)S; nf.A = (int32_t)A; nf.NC = (int32_t)NC; nf.K = (int32_t)K;
+        nf.radius = (float)radius; nf.clear_ego = (float)clear_ego; nf.count = (int32_t)count; nf.density = (int32_t)density;
+    }
+    tde_near_field nf;
     at::Device dev;
 
   private:
@@ -294,6 +323,17 @@ class EnvHandle {
         check_rc(tde_env_post_step(&cfg_, &world_, &state_, p, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_env_post_step");
     }
 
+    // tde_near_field_spawn: near-field traffic in the free slots of the masked envs (all without a mask)
+    void near_field_spawn(const NearField &nf, const std::optional<at::Tensor> &mask, int64_t flags)
+    {
+        cfg_.flags = static_cast<uint32_t>(flags);
+        TORCH_CHECK(nf.dev == dev_, "near_field is on ", nf.dev, ", expected ", dev_);
+        const uint8_t *m = mask ? static_cast<const uint8_t *>(dev_ptr(*mask, at::kByte, state_.B, "mask", dev_)) : nullptr;
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_near_field_spawn(&cfg_, &world_, &state_, &nf.nf, m, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                 "tde_near_field_spawn");
+    }
+
     int64_t flags() const { return cfg_.flags; }
     int64_t num_envs() const { return state_.B; }
     int64_t agents_per_env() const { return state_.A; }
@@ -412,6 +452,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     py::class_<Config>(m, "Config", "tde_config by value, from its bytes").def(py::init<const py::bytes &>(), py::arg("raw"));
     py::class_<World, std::shared_ptr<World>>(m, "World", "tde_world over named device tensors (kept alive)")
         .def(py::init<const py::dict &, const py::dict &, int64_t>(), py::arg("tensors"), py::arg("ints"), py::arg("device_index"));
+    py::class_<NearField>(m, "NearField", "tde_near_field over named device tensors (kept alive)")
+        .def(py::init<const py::dict &, int64_t, int64_t, int64_t, int64_t, double, double, int64_t, int64_t, int64_t>(), py::arg("tensors"),
+             py::arg("S"), py::arg("A"), py::arg("NC"), py::arg("K"), py::arg("radius"), py::arg("clear_ego"), py::arg("count"),
+             py::arg("density"), py::arg("device_index"));
     py::class_<EnvHandle>(m, "EnvHandle")
         .def(py::init<const Config &, std::shared_ptr<World>, const py::dict &, int64_t, int64_t>(), py::arg("cfg"), py::arg("world"),
              py::arg("state"), py::arg("B"), py::arg("A"))
@@ -427,6 +471,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         .def("state_obs", &EnvHandle::state_obs)
         .def("ego_infractions", &EnvHandle::ego_infractions, py::arg("out"), py::arg("flags"))
         .def("post_step", &EnvHandle::post_step, py::arg("magnitudes"), py::arg("flags"))
+        .def("near_field_spawn", &EnvHandle::near_field_spawn, py::arg("nf"), py::arg("mask"), py::arg("flags"))
         .def_property_readonly("flags", &EnvHandle::flags)
         .def_property_readonly("num_envs", &EnvHandle::num_envs)
         .def_property_readonly("agents_per_env", &EnvHandle::agents_per_env);

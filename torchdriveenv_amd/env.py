@@ -16,10 +16,11 @@ import numpy as np
 import torch
 
 from . import _abi, ops
-from .config import EnvConfig, WaypointSuite, render_flags, to_tde_config, validate
+from .config import EnvConfig, NearField, WaypointSuite, check_near_field, render_flags, to_tde_config, validate
 from .state import EnvState
 from .video import VideoRecorder
-from .world import World, assemble_world, check_threshold, corridor_mesh, effective_offroad_distance
+from .world import (NearFieldTable, World, assemble_world, build_near_field, check_threshold, corridor_mesh,
+                    effective_offroad_distance, mesh_distance)
 
 try:  # optional: neither gymnasium nor SB3 ships in this image
     import gymnasium as gym
@@ -209,10 +210,94 @@ def _heading_table(start_headings, loc, p0, p1, n):
     return out
 
 
+def _heading_field(start_headings, loc):
+    """the caller's lane-direction field of a location as a callable (x, y) -> psi or None, or None"""
+    if start_headings is None or loc is None:
+        return None
+    f = start_headings
+    if isinstance(f, dict):
+        f = f.get(loc)
+        if f is None:
+            return None
+        return f if callable(f) else (lambda x, y, c=float(f): c)
+    return lambda x, y: start_headings(loc, x, y)
+
+
+def _resample_polyline(pl, pitch):
+    """(x, y, psi) every `pitch` metres of arc length along a polyline, psi = the direction of the segment"""
+    p = np.asarray(pl, np.float64).reshape(-1, 2)
+    out = []
+    carry = 0.0
+    for a, b in zip(p[:-1], p[1:]):
+        d = float(np.hypot(*(b - a)))
+        if d <= 0:
+            continue
+        psi = math.atan2(b[1] - a[1], b[0] - a[0])
+        t = carry
+        while t <= d:
+            out.append((a[0] + (b[0] - a[0]) * t / d, a[1] + (b[1] - a[1]) * t / d, psi))
+            t += pitch
+        carry = t - d
+    return np.asarray(out, np.float64).reshape(-1, 3)
+
+
+def near_field_positions(world, nf, scn_polylines, locations, start_headings=None):
+    """candidate positions [m, 3] of (x, y, psi) per scenario, from the first source that applies: the `nf.candidates` hook
+    (location, scenario_index) -> [n, 3]; the location's lane-direction field (`start_headings`) on a lattice of pitch `nf.pitch`
+    over the scenario's drivable mesh, where the field gives a heading; the scenario's polylines (waypoints, NPC routes, replay
+    paths) every `nf.pitch` metres with the segment's direction.  -> (positions, source names)"""
+    thr = 0.5 if world.threshold is None else float(world.threshold)
+    tri_all = world.arrays["tri"].reshape(-1, 3, 2).astype(np.float64)
+    pos, src = [], []
+    for si in range(world.n_scn):
+        loc = locations[si]
+        if nf.candidates is not None:
+            try:
+                P = np.asarray(nf.candidates(loc, si), np.float64)
+            except (TypeError, ValueError) as ex:
+                raise ValueError(f"near_field.candidates({loc!r}, {si}) failed: {ex}") from ex
+            if P.size == 0:
+                P = P.reshape(0, 3)
+            if P.ndim != 2 or P.shape[1] != 3:
+                raise ValueError(f"near_field.candidates({loc!r}, {si}) must return an array [n, 3] of (x, y, psi), got shape {P.shape}")
+            pos.append(P)
+            src.append("candidates")
+            continue
+        field = _heading_field(start_headings, loc)
+        if field is not None:
+            p0, p1 = world.arrays["wp_xy"][si, 0], world.arrays["wp_xy"][si, 1]
+            reach = float(nf.radius) + float(np.hypot(*(p1 - p0)))
+            g = float(nf.pitch)
+            xs = np.arange(math.floor((p0[0] - reach) / g), math.ceil((p0[0] + reach) / g) + 1) * g
+            ys = np.arange(math.floor((p0[1] - reach) / g), math.ceil((p0[1] + reach) / g) + 1) * g
+            X, Y = np.meshgrid(xs, ys, indexing="xy")
+            pts = np.stack([X.reshape(-1), Y.reshape(-1)], -1)
+            pts = pts[np.hypot(pts[:, 0] - p0[0], pts[:, 1] - p0[1]) <= reach]
+            md = world.arrays["maps"][int(world.arrays["scn"]["map"][si])]
+            mesh = tri_all[int(md["tri_base"]):int(md["tri_base"]) + int(md["n_tri"])]
+            pts = pts[mesh_distance(pts, mesh, thr) <= thr]
+            P = []
+            for x, y in pts:
+                psi = field(float(x), float(y))
+                if psi is None:
+                    continue
+                psi = float(np.asarray(psi, np.float64).reshape(-1)[0])
+                if np.isfinite(psi):
+                    P.append((x, y, psi))
+            pos.append(np.asarray(P, np.float64).reshape(-1, 3))
+            src.append("lattice")
+            continue
+        pls = [_resample_polyline(pl, float(nf.pitch)) for pl in scn_polylines[si]]
+        pos.append(np.concatenate(pls, 0) if pls else np.zeros((0, 3)))
+        src.append("polylines")
+    return pos, src
+
+
 def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=12.0, threshold=0.5,
                               background=None, background_radius=250.0, ego_only=False, road_meshes=None, near_range=None,
-                              traffic_lights=None, light_radius=150.0, start_headings=None, heading_samples=16):
-    """WaypointSuite -> World.  Agent ordering follows the reference: slot 0 ego, then the scenario's agents
+                              traffic_lights=None, light_radius=150.0, start_headings=None, heading_samples=16,
+                              near_field=None, near_field_seed=0):
+    """WaypointSuite -> World, or (World, NearFieldTable) with `near_field`.  Agent ordering follows the reference: slot 0 ego, then the scenario's agents
     (ref gym_env.py:219-228); `car_sequence_suite[i][k]` replays slot k (ref gym_env.py:275-283).
     The CARLA town meshes the reference takes from torchdrivesim's package data are not available, so each scenario
     gets a synthetic drivable corridor around its waypoints, scenario agents and replay paths; non-replayed scenario
@@ -221,7 +306,7 @@ def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=
     `background`: directory of background-traffic JSON files (ref gym_env.py:200-235), or a callable
     location -> dict from `loaders.load_background_traffic`.  As in the reference the ego takes the attributes of the
     file's first agent (:223) and the file's agents farther than 100 m from the ego start are kept (:227-231); the
-    near field, which the reference fills through a remote INITIALIZE call (:232-235), stays empty.  Of the kept
+    near field, which the reference fills through a remote INITIALIZE call (:232-235), stays empty unless `near_field` is given.  Of the kept
     agents the nearest ones (within `background_radius`, so the synthetic corridor mesh stays local) fill the free
     slots after the scenario's own agents.  `ego_only`: the ego alone, no scenario / replay / background agents
     (ref gym_env.py:192-198).
@@ -253,8 +338,20 @@ def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=
     which the MAGNITUDE of the offroad infraction (info["offroad"], ref gym_env.py:427) is two table look-ups; a corner farther out
     is still exact but found by scanning the grid, and beyond the reach where that square would hold more cells than the map has
     triangles by a walk over all the map's triangles (tens of microseconds per such ego and step).  Raise it (it costs table memory:
-    a few records per square metre of the band) for `terminated_at_infraction=False` runs whose egos keep driving off the road."""
+    a few records per square metre of the band) for `terminated_at_infraction=False` runs whose egos keep driving off the road.
+
+    `near_field` (config.NearField): traffic within `radius` of the ego at every reset, the local stand-in for the reference's
+    iai_conditional_initialize (ref gym_env.py:232-238, iai.py:6-60).  The candidate table (world.build_near_field) is built here
+    from the first source that applies per scenario: the `candidates` hook, the location's `start_headings` field on a lattice over
+    its mesh, or the scenario's polylines (near_field_positions); attributes from a generator seeded by (`near_field_seed`,
+    scenario).  `density` None: the background file's agent_density (the largest over the scenarios) with `background`, else 0.
+    Returns (world, table); tde_near_field_spawn (BatchedWaypointEnv(near_field=...)) draws from the table per episode."""
     from . import loaders
+    if near_field is not None:
+        near_field = check_near_field(near_field)
+        if ego_only:
+            raise ValueError("near_field with ego_only=True: the reference spawns no traffic in ego-only mode (gym_env.py:192-198)")
+    scn_polylines, scn_locations, densities = [], [], []
     meshes, scenarios = [], []
     map_of_location = {}
     light_groups, group_of = [], {}                  # (map id, kept stop lines) -> index into light_groups
@@ -289,6 +386,8 @@ def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=
         if background is not None and not ego_only:
             loc = data.locations[i] if data.locations else ""
             bt = background(loc) if callable(background) else loaders.pick_background_traffic(loc, background)
+            if bt is not None:
+                densities.append(int(bt.get("agent_density") or 0))
             if bt is not None and bt["agent_states"]:
                 ego_attr = tuple(float(t) for t in bt["agent_attributes"][0][:3])
                 far = [(math.dist(wps[0], s[:2]), k) for k, s in enumerate(bt["agent_states"])]
@@ -332,12 +431,21 @@ def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=
         if table is not None:
             scn["start_headings"] = table
         scenarios.append(scn)
+        scn_polylines.append(polylines)
+        scn_locations.append(loc)
     if any("start_headings" in sc for sc in scenarios):      # one table size per world: the others repeat their segment's direction
         for sc in scenarios:
             sc.setdefault("start_headings", [sc["start_heading"]] * int(heading_samples))
     from .world import NEAR_RANGE
-    return assemble_world(meshes, scenarios, agents_per_env, threshold=threshold, light_groups=light_groups,
-                          near_range=NEAR_RANGE if near_range is None else float(near_range))
+    world = assemble_world(meshes, scenarios, agents_per_env, threshold=threshold, light_groups=light_groups,
+                           near_range=NEAR_RANGE if near_range is None else float(near_range))
+    if near_field is None:
+        return world
+    positions, sources = near_field_positions(world, near_field, scn_polylines, scn_locations, start_headings)
+    density = int(near_field.density) if near_field.density is not None else max(densities, default=0)
+    table = build_near_field(world, positions, near_field, near_field_seed, density)
+    table.sources = sources
+    return world, table
 
 
 class _LazyInfo(dict):
@@ -430,7 +538,7 @@ class BatchedWaypointEnv:
     def __init__(self, cfg: EnvConfig, data, num_envs, agents_per_env=16, device=None, obs_mode="birdview",
                  frame_stack=1, auto_reset=True, with_info=True, background=None, env_base=0, binding="ext",
                  info_magnitudes=True, road_meshes=None, near_range=None, traffic_lights=None, start_headings=None, light_radius=150.0,
-                 heading_samples=16):
+                 heading_samples=16, near_field=None):
         """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp), "ctypes" = through
         the ctypes binding of the same C-ABI (ops.py); both call the very same entry points of libtde_hip.so.
         info_magnitudes (default): info["offroad"] / info["collision"] hold the MAGNITUDES the reference reports there (ref
@@ -442,8 +550,22 @@ class BatchedWaypointEnv:
         road_meshes / near_range: the drivable mesh per location and the reach of the grid index's near lists when `data` is a
         WaypointSuite (world_from_waypoint_suite).  With `terminated_at_infraction=False` an ego may drive far off the road, where
         the exact offroad magnitude is found by a scan of the grid or a walk over the map's triangles (tens of microseconds per such
-        ego and step; `near_range` moves that point outwards, info_magnitudes=False skips the work)."""
+        ego and step; `near_range` moves that point outwards, info_magnitudes=False skips the work).
+        near_field: traffic around the ego at every reset and re-spawn (tde_near_field_spawn, the stand-in for the reference's
+        iai_conditional_initialize, ref gym_env.py:232-238): a config.NearField (or a dict of its fields) when `data` is a
+        WaypointSuite, or a world.NearFieldTable built for the World `data` is (world_from_waypoint_suite(..., near_field=)).  Every
+        (re)spawn - reset(), auto-reset in step(), the VecEnv's re-spawn - then runs the spawner before the state is observed;
+        rollout() and the multi-stream step raise.  None (default): no near field, every path as it was."""
         validate(cfg)
+        if near_field is not None and not isinstance(near_field, NearFieldTable):
+            near_field = check_near_field(near_field, cfg)
+        if near_field is not None and cfg.ego_only:
+            raise ValueError("near_field with ego_only=True: the reference spawns no traffic in ego-only mode (gym_env.py:192-198)")
+        if isinstance(near_field, NearField) and isinstance(data, World):
+            raise ValueError("near_field=NearField(...) needs a WaypointSuite as `data`; with a prebuilt World pass the NearFieldTable "
+                             "that world_from_waypoint_suite(..., near_field=) returned with it")
+        if isinstance(near_field, NearFieldTable) and not isinstance(data, World):
+            raise ValueError("a NearFieldTable belongs to the World it was built for: pass that World as `data`")
         if binding not in ("ext", "ctypes"):
             raise ValueError("binding must be 'ext' or 'ctypes'")                                              # ref gym_env.py:79-80 and the fields this path rejects
         if obs_mode not in ("birdview", "state"):
@@ -457,17 +579,24 @@ class BatchedWaypointEnv:
             from .loaders import pick_background_traffic
             background = pick_background_traffic                     # (searched under TORCHDRIVEENV_DATA; None if absent)
         sim = cfg.simulator
+        seed = cfg.seed if cfg.seed is not None else int(np.random.randint(0, 2**31 - 1))  # ref helpers.py:39-41
         self.world = data if isinstance(data, World) else world_from_waypoint_suite(
             data, agents_per_env,
             threshold=effective_offroad_distance(sim.offroad_threshold, sim.offroad_threshold_squared),
             background=background if cfg.use_background_traffic else None, ego_only=cfg.ego_only, road_meshes=road_meshes,
             near_range=near_range, traffic_lights=traffic_lights, light_radius=light_radius, start_headings=start_headings,
-            heading_samples=heading_samples)
+            heading_samples=heading_samples, near_field=near_field if isinstance(near_field, NearField) else None,
+            near_field_seed=seed)
+        if isinstance(near_field, NearField):
+            self.world, near_field = self.world
+        if near_field is not None and (near_field.S != self.world.n_scn or near_field.A != self.world.A):
+            raise ValueError(f"the near-field table is for {near_field.S} scenarios x {near_field.A} slots, the world has "
+                             f"{self.world.n_scn} x {self.world.A}")
+        self.near_field = near_field                                 # world.NearFieldTable or None
         check_threshold(self.world, sim.offroad_threshold, sim.offroad_threshold_squared,
                         "EnvConfig.simulator.offroad_threshold")   # a prebuilt World bakes its threshold into the grid
         self.A = self.world.A
         self.num_envs = int(num_envs)
-        seed = cfg.seed if cfg.seed is not None else int(np.random.randint(0, 2**31 - 1))  # ref helpers.py:39-41
         self.seed_value = seed
         flags = _abi.F_NPC | _abi.F_REPLAY | _abi.F_OFFROAD | _abi.F_REWARD
         if auto_reset:
@@ -480,7 +609,13 @@ class BatchedWaypointEnv:
             flags |= _abi.F_NPC_FIRST_STEP
         self.tde_cfg = to_tde_config(cfg, seed, flags)
         self.tde_cfg.env_base = int(env_base)                        # shard of a larger batch: sharding.ShardedBatchedEnv
-        self.dworld = self.world.to_device(self.torch_device)
+        # near-field envs run without the first-step gap cache (tde_world.first_gap = NULL): it assumes the NPCs sit exactly at the
+        # scenario's spawn records on the first step, which the spawner's agents make untrue
+        self.dworld = self.world.to_device(self.torch_device, first_gap=near_field is None)
+        self.dnf = None
+        if near_field is not None:
+            self.dnf = near_field.to_device(self.torch_device)
+            self.dworld.near_field = self.dnf                        # (ops.env_rollout / env_step_render refuse such a world)
         # obs_mode "state": tde_env_step writes the compact observation itself (no second launch per step)
         self.info_magnitudes = bool(info_magnitudes)
         self.state = EnvState(self.num_envs, self.A, device=self.torch_device, with_info=with_info,
@@ -497,11 +632,16 @@ class BatchedWaypointEnv:
         self._vec = None
         self._h = None
         self._mag = self.state["magnitudes"]                         # float32 [B, 4] written by the step (None: indicators)
+        self._hnf = None
+        self._nf_mask = None
         if binding == "ext":
             from . import _ext
             self._h = _ext.env_handle(self.tde_cfg, self.dworld, self.state)
-        # the world's first-step gap cache for this configuration, now - not inside the first step() (which may be under a stream capture)
-        ops.first_gaps(self.tde_cfg, self.dworld)
+            if self.dnf is not None:
+                self._hnf = _ext.near_field_of(self.dnf)
+        if self.dnf is None:
+            # the world's first-step gap cache for this configuration, now - not inside the first step() (which may be under a stream capture)
+            ops.first_gaps(self.tde_cfg, self.dworld)
 
     @property
     def auto_reset(self):
@@ -518,7 +658,7 @@ class BatchedWaypointEnv:
             # 0 / 1 bytes: the rasteriser reads bits 0-1 of a `fresh` byte (tde_render.fresh), so a mask like done_bits with only
             # infraction bits set must not re-spawn an env and leave its older stack frames un-blanked
             m = (torch.as_tensor(mask, device=self.torch_device) != 0).to(torch.uint8).contiguous()
-        if m is not None and self.obs_mode == "birdview" and self._obs is not None:
+        if m is not None and self.obs_mode == "birdview" and self._obs is not None and self.dnf is None:
             # the SB3-style auto-reset: the re-spawn and the re-spawned views' first observation in ONE C-ABI call
             if self._stack is not None:
                 self._obs = self._stack.reset_rerender(self.tde_cfg, self.dworld, self.state, m, self._fov)
@@ -532,6 +672,7 @@ class BatchedWaypointEnv:
             self._h.reset(m, int(self.tde_cfg.flags))
         else:
             ops.env_reset(self.tde_cfg, self.dworld, self.state, m)
+        self._spawn_near_field(m)                                    # (near-field envs: reset -> spawn -> render)
         if self.obs_mode == "state" or m is None or self._obs is None:
             if self._stack is not None:
                 self._stack.clear()                                  # VecFrameStack clears the stack on reset
@@ -541,6 +682,21 @@ class BatchedWaypointEnv:
         else:
             self._render1(self._obs, only=m)
         return self._obs
+
+    def _spawn_near_field(self, mask=None, done=False):
+        """tde_near_field_spawn on the envs in `mask` (all: None), or - done=True - on the envs the last step finished (the
+        terminated / truncated flags it left: their in-place re-spawn just happened).  No-op without a near field."""
+        if self.dnf is None:
+            return
+        if done:
+            st = self.state
+            if self._nf_mask is None:
+                self._nf_mask = torch.empty(self.num_envs, dtype=torch.uint8, device=self.torch_device)
+            mask = torch.bitwise_or(st["terminated"], st["truncated"], out=self._nf_mask)
+        if self._h is not None:
+            self._h.near_field_spawn(self._hnf, mask, int(self.tde_cfg.flags))
+        else:
+            ops.near_field_spawn(self.tde_cfg, self.dworld, self.state, self.dnf, mask)
 
     def _flag_views(self):
         """the state's terminated / truncated bytes seen as bool (no copy), formed once: the buffers never move"""
@@ -560,6 +716,8 @@ class BatchedWaypointEnv:
             self._h.step(a, int(self.tde_cfg.flags))
         else:
             ops.env_step(self.tde_cfg, self.dworld, self.state, action=a)
+        if self.dnf is not None and self.auto_reset:
+            self._spawn_near_field(done=True)                        # the envs the step re-spawned, before they are observed
         st = self.state
         if self.obs_mode == "state":
             obs = st["obs"]
@@ -596,6 +754,8 @@ class BatchedWaypointEnv:
                 ops.env_post_step(self.tde_cfg, self.dworld, st, self._mag)
         finally:
             self.tde_cfg.flags = full
+        if full & _abi.F_AUTORESET:
+            self._spawn_near_field(done=True)
         term, trunc = self._flag_views()
         info = _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
         if self.obs_mode == "state":
@@ -612,6 +772,9 @@ class BatchedWaypointEnv:
         """K open-loop steps from a resident [K,B,2] action tensor -> (reward [K,B], done bits [K,B]).  (The Monitor-style
         episode statistics of the closed-loop API are not maintained across a rollout: they follow from the returned
         arrays.)"""
+        if self.dnf is not None:
+            raise NotImplementedError("rollout() with near_field: the rollout kernels re-spawn finished envs inside one launch, where "
+                                      "the near-field spawner cannot run; step() the envs instead")
         a = torch.as_tensor(actions, dtype=torch.float32, device=self.torch_device).contiguous()
         if self._h is not None:
             reward = torch.empty(a.shape[:2], dtype=torch.float32, device=self.torch_device)
@@ -915,6 +1078,7 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
             pre.copy_(obs, non_blocking=True)
             st.copy_outputs_async(ring=3)                            # ONE copy of every per-env output, queued (no synchronisation yet)
             env._h.post_step(None, int(env.tde_cfg.flags))
+            env._spawn_near_field(done=True)                         # (near field: the re-spawned envs' traffic, still one synchronisation)
             buf = self._obs_to_host(st["obs"])
         else:
             buf = self._obs_to_host(obs)
@@ -1024,10 +1188,12 @@ class WaypointSuiteEnv(_GymEnvBase):
     metadata = {"render_modes": ["video", "rgb_array"], "render_fps": 10}
 
     def __init__(self, cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None,
-                 video_camera="map"):
+                 video_camera="map", background=None, near_field=None):
         """render_mode="video": every reset() and step() records a video_res x video_res frame at video_fov metres across (the
         reference's BirdviewRecordingWrapper, gym_env.py:295-297) from `video_camera` ("map": the centre of the map, heading pi/2;
-        "ego"; or (x, y, psi)); get_birdviews() returns them, close() writes video_filename (video.save_video)."""
+        "ego"; or (x, y, psi)); get_birdviews() returns them, close() writes video_filename (video.save_video).
+        background / near_field: the background-traffic files and the near-field traffic of every reset, as BatchedWaypointEnv
+        takes them (the reference's background mode: gym_env.py:200-238)."""
         self.config = cfg
         if cfg.render_mode == "video":               # the batched env renders rgb_array; the frames are recorded here
             cfg = dataclasses.replace(cfg, render_mode="rgb_array")
@@ -1035,7 +1201,8 @@ class WaypointSuiteEnv(_GymEnvBase):
         # get_info reports them (ref gym_env.py:427-428; Monitor logs them, examples/rl_training.py:128)
         self._env = BatchedWaypointEnv(cfg, data, num_envs=1, agents_per_env=agents_per_env, obs_mode="birdview",
                                        frame_stack=1, auto_reset=False, info_magnitudes=True, road_meshes=road_meshes,
-                                       traffic_lights=traffic_lights, start_headings=start_headings)
+                                       traffic_lights=traffic_lights, start_headings=start_headings, background=background,
+                                       near_field=near_field)
         self.torch_device = self._env.torch_device
         self.render_mode = self.config.render_mode
         self._video = None
@@ -1181,14 +1348,17 @@ class SingleAgentWrapper(_GymWrapperBase):
         self.env.close()
 
 
-def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None, video_camera="map"):
+def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None, video_camera="map",
+         background=None, near_field=None):
     """what gym.make('torchdriveenv-v0', args={'cfg': cfg, 'data': data}) returns in the reference (ref __init__.py:10).
     `road_meshes`, `traffic_lights`, `start_headings`: what the reference takes from torchdrivesim's map config of the location
     (`find_map_config`: road mesh ref gym_env.py:184, stop lines + light controller :181-189, lanelet directions :359) - see
-    world_from_waypoint_suite.  `video_camera`: the camera of render_mode="video" frames (WaypointSuiteEnv)"""
+    world_from_waypoint_suite.  `video_camera`: the camera of render_mode="video" frames (WaypointSuiteEnv).  `background`: the
+    background-traffic files (ref gym_env.py:200-231; default: the packaged directory when cfg.use_background_traffic);
+    `near_field`: a config.NearField - traffic around the ego at every reset (ref gym_env.py:232-238; BatchedWaypointEnv)"""
     return SingleAgentWrapper(WaypointSuiteEnv(cfg=cfg, data=data, agents_per_env=agents_per_env, road_meshes=road_meshes,
                                                traffic_lights=traffic_lights, start_headings=start_headings,
-                                               video_camera=video_camera))
+                                               video_camera=video_camera, background=background, near_field=near_field))
 
 
 if gym is not None:  # pragma: no cover

@@ -136,6 +136,22 @@ def env_reset(cfg, dworld, state, mask=None):
                                _lib.current_stream(state.device)), "tde_env_reset")
 
 
+def _no_near_field(dworld, what):
+    if getattr(dworld, "near_field", None) is not None:
+        raise NotImplementedError(f"{what} re-spawns finished envs inside one launch, where the near-field spawner cannot run: "
+                                  "step the envs of a near-field world with env_step + near_field_spawn")
+
+
+def near_field_spawn(cfg, dworld, state, nf, mask=None):
+    """tde_near_field_spawn: fill the free slots of the envs in `mask` (uint8 [B] on the device; None: all) with near-field traffic
+    from the candidate table `nf` (world.DeviceNearField), on the state the preceding reset / re-spawn left.  Asynchronous."""
+    L = _lib.load()
+    dev = state.device
+    pm = _chk(mask, torch.uint8, state.B, "mask", torch.device(dev), optional=True)
+    _lib.check(_call(dev, L.tde_near_field_spawn, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(nf.struct),
+                     pm, _lib.current_stream(dev)), "tde_near_field_spawn")
+
+
 def first_gaps(cfg, dworld):
     """tde_first_gaps: fill the device world's first-step gap cache for `cfg` now (tde_env_step / tde_env_rollout do it themselves
     on first use: only needed to choose when the launch happens)"""
@@ -158,6 +174,7 @@ def env_step(cfg, dworld, state, action=None):
 
 def env_rollout(cfg, dworld, state, actions, reward=None, done=None):
     """actions float32 [K,B,2] on device -> (reward [K,B] f32, done [K,B] u8)"""
+    _no_near_field(dworld, "env_rollout")
     L = _lib.load()
     K, B = actions.shape[0], actions.shape[1]
     dev = actions.device
@@ -340,6 +357,7 @@ def env_step_render(cfg, dworld, state, streams, action=None, out=None, H=64, W=
     its own HIP stream, so that the step of one sub-batch overlaps the rasteriser of another.  Same results as env_step +
     render_ego.  `streams`: torch.cuda.Stream objects; the caller orders them against the current stream (fork_streams /
     join_streams) - open-loop drivers join once, at the end.  Returns `out` (None without render)."""
+    _no_near_field(dworld, "env_step_render")
     L = _lib.load()
     dev = state.device
     st = state.struct

@@ -104,9 +104,12 @@ class ShardedBatchedEnv:
     buffers (observations, rewards, dones) - the host gather - and the caller gets VecEnv-shaped numpy results for the
     whole batch: step(actions [total, 2]) -> (obs, rewards, dones, infos)."""
 
-    def __init__(self, cfg, world, total_envs, n_shards=None, devices=None, copy_obs=True, **env_kw):
+    def __init__(self, cfg, world, total_envs, n_shards=None, devices=None, copy_obs=True, near_field=None, **env_kw):
         """copy_obs=False: reset / step hand out VIEWS of the gathered host buffers (valid until the next step) instead
-        of fresh arrays - 100 MB per 8192 birdview envs and step that nobody has to copy"""
+        of fresh arrays - 100 MB per 8192 birdview envs and step that nobody has to copy.
+        near_field: as BatchedWaypointEnv takes it - the NearFieldTable built with `world` (a World), or a config.NearField when
+        `world` is a WaypointSuite (every shard then builds the same table from the one seed; a `candidates` hook must pickle).
+        The spawner's draws are keyed by the global env index like the reset's, so the shards spawn what the unsharded batch does."""
         import dataclasses
 
         import numpy as np
@@ -127,6 +130,8 @@ class ShardedBatchedEnv:
             cfg = dataclasses.replace(cfg, seed=int(np.random.randint(0, 2**31 - 1)))
         self.config = cfg
         self.copy_obs = bool(copy_obs)
+        if near_field is not None:
+            env_kw = dict(env_kw, near_field=near_field)
         self.devices = list(devices) if devices is not None else [r % ndev for r in range(self.n_shards)]
         self.num_envs = int(total_envs)
         obs_mode = env_kw.get("obs_mode", "birdview")

@@ -289,11 +289,16 @@ class World:
             self._host_struct = _abi.fill_world_struct(self.arrays, self.ints)
         return self._host_struct
 
-    def to_device(self, device):
+    def to_device(self, device, first_gap=True):
+        """first_gap=False: the device world has no first-step gap cache (tde_world.first_gap = NULL): every first step runs the
+        NPC controller's sweep (what near-field envs need: the cache assumes the NPCs at their spawn records)"""
         import torch
 
         tens = {}
         for k, a in self.arrays.items():
+            if k == "first_gap" and not first_gap:
+                tens[k] = None
+                continue
             if a.dtype.names is not None:      # record arrays travel as raw bytes
                 t = torch.from_numpy(a.reshape(-1).view(np.uint8).copy())
             else:
@@ -400,6 +405,7 @@ class DeviceWorld:
         self.struct = _abi.fill_world_struct(tensors, ints)
         self.scene_camera_host = None   # float32 [n_scn, 3] "map" camera of every scenario (World.scene_cameras; render_scene)
         self._scene_camera = None
+        self.near_field = None          # the DeviceNearField of the envs that use this copy (BatchedWaypointEnv(near_field=...))
 
     @property
     def scene_camera(self):
@@ -553,3 +559,234 @@ def assemble_world(meshes, scenarios, A, threshold=0.5, cell=0.5, lights=None, l
     ints = dict(n_maps=len(maps), n_scn=S, NW=NW, A=A, n_routes=len(routes), RW=RW, n_replay=len(replays), RT=RT,
                 hints=_abi.WORLD_LARGE_GRID if large else 0, NH=NH)
     return World(arrays, ints, threshold)
+
+
+# ---- near-field candidate tables (tde_near_field; tde_near_field_spawn) ----------------------------------------------------------
+NF_LEN, NF_WID, NF_LR = (4.8, 5.5), (1.8, 2.2), (0.82, 0.97)    # the reference's attribute ranges (gym_env.py:193-195)
+NF_ROAD_SLACK = 0.05        # a candidate's corners lie this far inside the offroad distance (float64 here, fp32 in the kernels)
+
+
+def _pt_tri_dist(P, T):
+    """float64 distances [q, t] of points P [q, 2] to the (filled) triangles T [t, 3, 2]"""
+    Pq = P[:, None, :]
+    a, b, c = T[None, :, 0], T[None, :, 1], T[None, :, 2]
+
+    def side(o, u):
+        return (u[..., 0] - o[..., 0]) * (Pq[..., 1] - o[..., 1]) - (u[..., 1] - o[..., 1]) * (Pq[..., 0] - o[..., 0])
+
+    def seg(o, u):
+        d = u - o
+        dd = (d * d).sum(-1)
+        t = np.clip(((Pq - o) * d).sum(-1) / np.where(dd > 0, dd, 1.0), 0.0, 1.0)
+        q = o + t[..., None] * d - Pq
+        return np.sqrt((q * q).sum(-1))
+
+    s1, s2, s3 = side(a, b), side(b, c), side(c, a)
+    inside = ((s1 >= 0) & (s2 >= 0) & (s3 >= 0)) | ((s1 <= 0) & (s2 <= 0) & (s3 <= 0))
+    return np.where(inside, 0.0, np.minimum(np.minimum(seg(a, b), seg(b, c)), seg(c, a)))
+
+
+def mesh_distance(pts, tri, reach, cell=8.0):
+    """float64 distance of every point of pts [m, 2] to the mesh tri [n, 3, 2], exact up to `reach` (farther: inf)"""
+    pts = np.asarray(pts, np.float64).reshape(-1, 2)
+    out = np.full(len(pts), np.inf)
+    if len(pts) == 0:
+        return out
+    tri = np.asarray(tri, np.float64).reshape(-1, 3, 2)
+    lo, hi = tri.min(1) - reach, tri.max(1) + reach
+    pl, ph = pts.min(0), pts.max(0)
+    sel = (hi >= pl).all(1) & (lo <= ph).all(1)
+    tri, lo, hi = tri[sel], lo[sel], hi[sel]
+    if len(tri) == 0:
+        return out
+    n = np.floor((ph - pl) / cell).astype(np.int64) + 1
+    c0 = np.clip(np.floor((lo - pl) / cell).astype(np.int64), 0, n - 1)
+    c1 = np.clip(np.floor((hi - pl) / cell).astype(np.int64), 0, n - 1)
+    buckets = {}
+    for t in range(len(tri)):
+        for ix in range(c0[t, 0], c1[t, 0] + 1):
+            for iy in range(c0[t, 1], c1[t, 1] + 1):
+                buckets.setdefault(ix * n[1] + iy, []).append(t)
+    pc = np.floor((pts - pl) / cell).astype(np.int64)
+    key = pc[:, 0] * n[1] + pc[:, 1]
+    for k in np.unique(key):
+        ts = buckets.get(int(k))
+        if not ts:
+            continue
+        q = np.flatnonzero(key == k)
+        d = _pt_tri_dist(pts[q], tri[np.asarray(ts)]).min(1)
+        out[q] = np.where(d <= reach, d, np.inf)
+    return out
+
+
+def box_corners(x, y, c, s, hl, hw):
+    """[n, 4, 2] float64 corners of boxes centred at (x, y), heading (c, s), half extents hl (along) and hw (across)"""
+    fx, fy, lx, ly = c * hl, s * hl, -s * hw, c * hw
+    return np.stack([np.stack([x + fx + lx, y + fy + ly], -1), np.stack([x + fx - lx, y + fy - ly], -1),
+                     np.stack([x - fx - lx, y - fy - ly], -1), np.stack([x - fx + lx, y - fy + ly], -1)], 1)
+
+
+def sat_overlap(a, b):
+    """strict overlap of oriented boxes, pairwise: a and b are tuples (x, y, c, s, hl, hw) of float64 arrays of one length; True
+    where no axis of the four separates the pair (touching boxes do not overlap)"""
+    dx, dy = b[0] - a[0], b[1] - a[1]
+    over = np.ones(np.broadcast(dx, dy).shape, bool)
+    for ux, uy in ((a[2], a[3]), (-a[3], a[2]), (b[2], b[3]), (-b[3], b[2])):
+        ra = a[4] * np.abs(a[2] * ux + a[3] * uy) + a[5] * np.abs(-a[3] * ux + a[2] * uy)
+        rb = b[4] * np.abs(b[2] * ux + b[3] * uy) + b[5] * np.abs(-b[3] * ux + b[2] * uy)
+        over &= np.abs(dx * ux + dy * uy) < ra + rb
+    return over
+
+
+def _pairs_overlapping(box):
+    """(i, j) index arrays, i < j, of the overlapping pairs among the boxes `box` = (x, y, c, s, hl, hw)"""
+    x, y = box[0], box[1]
+    r = np.hypot(box[4], box[5])
+    n = len(x)
+    I, J = [], []
+    for i0 in range(0, n, 256):                      # (blocks of rows: the circumcircle filter, then the exact test)
+        i = np.arange(i0, min(n, i0 + 256))
+        near = (x[i, None] - x[None, :]) ** 2 + (y[i, None] - y[None, :]) ** 2 < (r[i, None] + r[None, :]) ** 2
+        near &= np.arange(n)[None, :] > i[:, None]
+        ii, jj = np.nonzero(near)
+        ii = i[ii]
+        ov = sat_overlap(tuple(v[ii] for v in box), tuple(v[jj] for v in box))
+        I.append(ii[ov])
+        J.append(jj[ov])
+    return np.concatenate(I) if I else np.zeros(0, np.int64), np.concatenate(J) if J else np.zeros(0, np.int64)
+
+
+class NearFieldTable:
+    """Host copy of a world's near-field candidate tables (tde_near_field): cand [S][NC] (NF_CAND_DTYPE), nbr [S][NC][K] uint16,
+    nbr_n / fixed [S][NC] uint8, n_cand [S] int32, and the parameters of the draw."""
+
+    def __init__(self, cand, nbr, nbr_n, fixed, n_cand, A, radius, clear_ego, count, density, sources=None):
+        self.cand, self.nbr, self.nbr_n, self.fixed = cand, nbr, nbr_n, fixed
+        self.n_cand = np.ascontiguousarray(n_cand, np.int32)
+        self.S, self.NC, self.K = cand.shape[0], cand.shape[1], nbr.shape[2]
+        self.A, self.radius, self.clear_ego = int(A), float(radius), float(clear_ego)
+        self.count, self.density = int(count), int(density)
+        self.sources = sources or []
+
+    def struct_of(self, arrays):
+        st = _abi.TdeNearField()
+        for k in ("cand", "nbr", "nbr_n", "fixed", "n_cand"):
+            setattr(st, k, _abi.ptr_of(arrays[k]))
+        st.S, st.A, st.NC, st.K = self.S, self.A, self.NC, self.K
+        st.radius, st.clear_ego, st.count, st.density = self.radius, self.clear_ego, self.count, self.density
+        return st
+
+    def neighbours(self, s, i):
+        """scenario-local indices of the neighbours of candidate i of scenario s"""
+        return self.nbr[s, i, :self.nbr_n[s, i]].astype(np.int64)
+
+    def to_device(self, device):
+        import torch
+
+        tens = dict(cand=torch.from_numpy(self.cand.reshape(-1).view(np.float32).copy()).to(device),
+                    nbr=torch.from_numpy(self.nbr.reshape(-1).view(np.int16).copy()).to(device),
+                    nbr_n=torch.from_numpy(self.nbr_n.reshape(-1).copy()).to(device),
+                    fixed=torch.from_numpy(self.fixed.reshape(-1).copy()).to(device),
+                    n_cand=torch.from_numpy(self.n_cand.copy()).to(device))
+        return DeviceNearField(self, tens)
+
+
+class DeviceNearField:
+    def __init__(self, table, tensors):
+        self.table, self.tensors = table, tensors          # (the tensors keep the device memory alive)
+        self.struct = table.struct_of(tensors)
+
+
+def build_near_field(world, positions, nf, seed, density=0):
+    """The near-field candidate table of `world` (NearFieldTable) from candidate positions per scenario (`positions[s]`: float
+    array [m, 3] of x, y, psi) and a config.NearField: candidates within radius + |p1 - p0| of the first waypoint p0 (every ego
+    start on the first segment), whose boxes are on the drivable surface (every corner within the world's offroad distance minus
+    NF_ROAD_SLACK of the scenario's mesh, float64); attributes and desired speeds drawn from a generator seeded by (seed, scenario);
+    at most TDE_NF_MAX_CAND per scenario (the nearest to p0); neighbour lists and fixed-conflict bits from an exact float64 SAT of
+    the boxes inflated by margin / 2 each; candidates with more than TDE_NF_MAX_NBR neighbours dropped."""
+    import warnings
+
+    S, A = world.n_scn, world.A
+    if len(positions) != S:
+        raise ValueError(f"positions for {len(positions)} scenarios, the world has {S}")
+    thr = 0.5 if world.threshold is None else float(world.threshold)
+    tri_all = world.arrays["tri"].reshape(-1, 3, 2).astype(np.float64)
+    maps, scn, wp, spawn = world.arrays["maps"], world.arrays["scn"], world.arrays["wp_xy"], world.arrays["spawn"]
+    hm = 0.5 * float(nf.margin)
+    lo_v, hi_v = (float(v) for v in nf.speed)
+    r_cand = math.hypot(0.5 * NF_LEN[1], 0.5 * NF_WID[1])
+    r_ego = float(np.hypot(0.5 * spawn["len"][:, 0].astype(np.float64), 0.5 * spawn["wid"][:, 0].astype(np.float64)).max())
+    if float(nf.clear_ego) < r_cand + r_ego + float(nf.margin):
+        raise ValueError(f"near_field.clear_ego = {nf.clear_ego:g} m is below the largest circumradii of the ego ({r_ego:.3f}) and of a "
+                         f"candidate ({r_cand:.3f}) plus margin ({nf.margin:g}): a spawned car could overlap the ego")
+    rows = []
+    for si in range(S):
+        P = np.asarray(positions[si], np.float64).reshape(-1, 3)
+        P = P[np.isfinite(P).all(1)]
+        p0, p1 = wp[si, 0], wp[si, 1]
+        reach = float(nf.radius) + float(np.hypot(*(p1 - p0)))
+        P = P[np.hypot(P[:, 0] - p0[0], P[:, 1] - p0[1]) <= reach]
+        m = len(P)
+        rng = np.random.default_rng([int(seed) & 0xFFFFFFFFFFFFFFFF, si])
+        L = rng.uniform(*NF_LEN, m).astype(np.float32)
+        W = rng.uniform(*NF_WID, m).astype(np.float32)
+        LR = rng.uniform(*NF_LR, m).astype(np.float32)
+        V = rng.uniform(lo_v, hi_v, m).astype(np.float32)
+        x32, y32, p32 = P[:, 0].astype(np.float32), P[:, 1].astype(np.float32), P[:, 2].astype(np.float32)
+        X, Y, psi = x32.astype(np.float64), y32.astype(np.float64), p32.astype(np.float64)
+        c, s = np.cos(psi), np.sin(psi)
+        hl, hw = 0.5 * L.astype(np.float64), 0.5 * W.astype(np.float64)
+        md = maps[int(scn["map"][si])]
+        mesh = tri_all[int(md["tri_base"]):int(md["tri_base"]) + int(md["n_tri"])]
+        d = mesh_distance(box_corners(X, Y, c, s, hl, hw).reshape(-1, 2), mesh, thr).reshape(m, 4)
+        keep = np.flatnonzero((d <= thr - NF_ROAD_SLACK).all(1))
+        if len(keep) > _abi.NF_MAX_CAND:
+            dist = np.hypot(X[keep] - p0[0], Y[keep] - p0[1])
+            warnings.warn(f"near field, scenario {si}: {len(keep)} candidates, the {_abi.NF_MAX_CAND} nearest to the first waypoint are "
+                          f"kept (raise near_field.pitch to thin them)", stacklevel=3)
+            keep = np.sort(keep[np.argsort(dist, kind="stable")[:_abi.NF_MAX_CAND]])
+        while True:                                                 # (dropping the crowded ones only lowers the others' counts)
+            box = (X[keep], Y[keep], c[keep], s[keep], hl[keep] + hm, hw[keep] + hm)
+            I, J = _pairs_overlapping(box)
+            cnt = np.bincount(np.concatenate([I, J]), minlength=len(keep))
+            crowded = cnt > _abi.NF_MAX_NBR
+            if not crowded.any():
+                break
+            warnings.warn(f"near field, scenario {si}: {int(crowded.sum())} candidates overlap more than {_abi.NF_MAX_NBR} others and are "
+                          f"dropped (raise near_field.pitch)", stacklevel=3)
+            keep = keep[~crowded]
+        n = len(keep)
+        fixed = np.zeros(n, np.uint8)
+        ag = spawn[si, 1:][spawn[si, 1:]["present"] != 0]
+        if len(ag) and n:
+            ca = ag["psi"].astype(np.float64)
+            abox = (ag["x"].astype(np.float64), ag["y"].astype(np.float64), np.cos(ca), np.sin(ca),
+                    0.5 * ag["len"].astype(np.float64) + hm, 0.5 * ag["wid"].astype(np.float64) + hm)
+            ov = sat_overlap(tuple(v[:, None] for v in box), tuple(v[None, :] for v in abox))
+            fixed = ov.any(1).astype(np.uint8)
+        nbrs = [[] for _ in range(n)]
+        for i, j in zip(I.tolist(), J.tolist()):
+            nbrs[i].append(j)
+            nbrs[j].append(i)
+        rec = np.zeros(n, _abi.NF_CAND_DTYPE)
+        k = keep
+        rec["x"], rec["y"], rec["psi"] = x32[k], y32[k], p32[k]
+        rec["c"], rec["s"] = c[k].astype(np.float32), s[k].astype(np.float32)
+        rec["len"], rec["wid"], rec["lr"], rec["vdes"] = L[k], W[k], LR[k], V[k]
+        rows.append((rec, [sorted(v) for v in nbrs], fixed))
+    NC = max(1, max(len(r[0]) for r in rows))
+    K = max(1, max((len(v) for r in rows for v in r[1]), default=1))
+    cand = np.zeros((S, NC), _abi.NF_CAND_DTYPE)
+    nbr = np.zeros((S, NC, K), np.uint16)
+    nbr_n = np.zeros((S, NC), np.uint8)
+    fixed = np.zeros((S, NC), np.uint8)
+    n_cand = np.zeros(S, np.int32)
+    for si, (rec, nb, fx) in enumerate(rows):
+        n = len(rec)
+        n_cand[si] = n
+        cand[si, :n] = rec
+        fixed[si, :n] = fx
+        for i, v in enumerate(nb):
+            nbr_n[si, i] = len(v)
+            nbr[si, i, :len(v)] = v
+    return NearFieldTable(cand, nbr, nbr_n, fixed, n_cand, A, nf.radius, nf.clear_ego, nf.count, density)
