@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TDE_ABI_VERSION 11
+#define TDE_ABI_VERSION 12
 #define TDE_MAX_AGENTS 128
 
 /* feature bits of tde_config.flags */
@@ -451,6 +451,25 @@ typedef struct tde_near_field {
     int32_t count;              /* 95 (gym_env.py:237: max(95 - n, agent_density)) */
     int32_t density;            /* the background file's agent_density, else 0 */
 } tde_near_field;
+
+/* (ABI 12) Vector observation (tde_vector_obs, include/tde_hip.h): the K nearest agents in the ego frame plus ray distances to the
+ * road edge, to other cars and to red stop lines, float32 [B][D] with D = TDE_VO_EGO + TDE_VO_NBR * k_nbr + TDE_VO_RAY * n_rays
+ * (no reference counterpart; the reference only has the birdview). */
+#define TDE_VO_MAX_NBR     16   /* k_nbr in [0, TDE_VO_MAX_NBR] */
+#define TDE_VO_MAX_RAYS    64   /* n_rays in [0, TDE_VO_MAX_RAYS] */
+#define TDE_VO_MAX_SAMPLES 1024 /* ray_range / ray_step in [1, TDE_VO_MAX_SAMPLES] */
+#define TDE_VO_EGO 10           /* values of the ego block */
+#define TDE_VO_NBR 9            /* values per neighbour entry */
+#define TDE_VO_RAY 3            /* channels per ray: road, car, red line */
+struct tde_vector_obs {      /* a struct tag without a typedef: the name is also the entry point's */
+    const float *ray_dir;       /* DEVICE [n_rays][2] unit vectors (forward, left) in the ego frame */
+    int32_t k_nbr;              /* neighbour entries per row */
+    int32_t n_rays;             /* rays per row */
+    float nbr_radius;           /* an agent is a neighbour when d2 < nbr_radius^2 [m] */
+    float ray_range;            /* ray length [m] */
+    float ray_step;             /* road-march sample spacing [m]; ray_range / ray_step is an integer M */
+    int32_t _pad0;              /* 32 bytes */
+};
 
 #ifdef __cplusplus
 }

@@ -200,6 +200,39 @@ TDE_API int tde_first_gaps(const tde_config *config, const tde_world *world, voi
 TDE_API int tde_near_field_spawn(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_near_field *nf,
                                  const uint8_t *mask, void *stream);
 
+/* Vector observation of every env with only[e] != 0 (uint8 [B]; NULL: all envs) -> out[e] = float32 [D], D = TDE_VO_EGO + TDE_VO_NBR *
+ * vo.k_nbr + TDE_VO_RAY * vo.n_rays (tde_abi.h: struct tde_vector_obs); the other rows are not written.  No reference counterpart.
+ * Every expression below is float32 with one rounding per written operation (no contraction), so a restatement matches it bit
+ * for bit.  Env e: s = state.scn[e], m = world.maps[world.scn[s].map], ego = slot 0 (x0, y0, psi0, v0, len0, wid0) with
+ * (s0, c0) = sincos_f32(psi0); every agent's (c, s) is sincos_f32 of its psi (tde_device.h); "frame(dx, dy)" = (dx*c0 + dy*s0,
+ * dy*c0 - dx*s0), (forward, left).
+ * Ego block [0, 10): v0, len0, wid0; for j = target_idx and target_idx + 1: frame((float)wp.x - x0, (float)wp.y - y0) of waypoint
+ * j of scenario s when j < wp_n, else (0, 0) (2 + 2 values; the first pair is tde_state_obs's); (float)min(max(wp_n - target_idx,
+ * 0), 2); (float)steps / (float)config.max_steps; 1 when m.n_stop > 0 and m.cycle_steps > 0, else 0.
+ * Neighbour block, k_nbr entries of 9 from 10: the present slots a in 1..A-1 with d2 < nbr_radius*nbr_radius, where dx = x_a - x0,
+ * dy = y_a - y0, d2 = dx*dx + dy*dy, ordered by (d2, a), the first k_nbr of them: 1, frame(dx, dy), cr = c_a*c0 + s_a*s0, sr =
+ * s_a*c0 - c_a*s0, v_a*cr - v0, v_a*sr, len_a, wid_a.  Entries past the last neighbour are zeros.
+ * Ray block, n_rays rays of 3 from 10 + 9 * k_nbr: ray k has the world direction ux = rx*c0 - ry*s0, uy = rx*s0 + ry*c0, (rx, ry) =
+ * vo.ray_dir[k], and M = ray_range / ray_step.
+ *   road  (float)j * ray_step for the first j in 1..M whose sample (x0 + ((float)j * ray_step)*ux, y0 + ((float)j * ray_step)*uy)
+ *         is farther than the offroad threshold from the map's mesh (the predicate of one box corner of the step: d^2 > thr2 with
+ *         thr2 as config.offroad_threshold_squared selects; the grid index equals the brute force over m's triangles), else
+ *         ray_range
+ *   car   min(ray_range, least entry distance over the present slots a in 1..A-1), the box of a = (x_a, y_a, c_a, s_a, 0.5f*len_a,
+ *         0.5f*wid_a)
+ *   red   the same over the stop lines q of m (box x, y, c, s, hl, hw) whose light is red at state.steps[e]: with
+ *         TDE_F_TRAFFIC_LIGHTS in config.flags, (red_mask >> (light & 31)) & 1 of the phase of steps % cycle_steps (the lines
+ *         tde_render_ego paints red); none without the flag
+ *   entry distance of a box (bx, by, bc, bs, h0, h1): rx = x0 - bx, ry = y0 - by; o0 = rx*bc + ry*bs, o1 = ry*bc - rx*bs; d0 =
+ *         ux*bc + uy*bs, d1 = uy*bc - ux*bs; per axis i: d_i == 0 -> [-inf, +inf] when -h_i <= o_i <= h_i, else a miss; otherwise
+ *         ta = (-h_i - o_i) / d_i, tb = (h_i - o_i) / d_i, [min(ta, tb), max(ta, tb)]; tn = max of the lows, tf = min of the
+ *         highs; a hit when tn <= tf and tf >= 0, at max(tn, 0)
+ * One wavefront per env, four envs per workgroup, one lane per ray.  Rejected: NULL cfg / world / state / vo / out, ray_dir NULL
+ * with n_rays > 0, k_nbr or n_rays out of range, nbr_radius / ray_range / ray_step not finite or <= 0, ray_range / ray_step not an
+ * integer in [1, TDE_VO_MAX_SAMPLES], config.max_steps < 1.  No allocation, no synchronisation (graph-capturable). */
+TDE_API int tde_vector_obs(const tde_config *cfg, const tde_world *world, const tde_state *state, const struct tde_vector_obs *vo,
+                           const uint8_t *only, float *out, void *stream);
+
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 
 /* Offroad grid index of ONE drivable mesh - what the simulator prepares once per map from the road mesh it is constructed

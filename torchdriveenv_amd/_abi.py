@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-TDE_ABI_VERSION = 11
+TDE_ABI_VERSION = 12
 TDE_MAX_AGENTS = 128
 
 F_NPC = 1 << 0
@@ -137,6 +137,15 @@ NF_MAX_CAND, NF_MAX_NBR, NF_TAG = 1024, 32, 0x4E46
 NF_CAND_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("psi", "f4"), ("c", "f4"), ("s", "f4"), ("len", "f4"), ("wid", "f4"),
                           ("lr", "f4"), ("vdes", "f4"), ("_pad0", "f4"), ("_pad1", "f4"), ("_pad2", "f4")])
 assert NF_CAND_DTYPE.itemsize == 48
+
+class TdeVectorObs(C.Structure):
+    """struct tde_vector_obs (tde_abi.h): the parameters of tde_vector_obs"""
+    _fields_ = [("ray_dir", _p), ("k_nbr", C.c_int32), ("n_rays", C.c_int32), ("nbr_radius", C.c_float), ("ray_range", C.c_float),
+                ("ray_step", C.c_float), ("_pad0", C.c_int32)]
+
+
+VO_MAX_NBR, VO_MAX_RAYS, VO_MAX_SAMPLES = 16, 64, 1024
+VO_EGO, VO_NBR, VO_RAY = 10, 9, 3
 
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7

@@ -171,3 +171,64 @@ def check_near_field(nf, cfg: Optional[EnvConfig] = None):
     if nf.candidates is not None and not callable(nf.candidates):
         raise ValueError("near_field.candidates must be a callable (location, scenario_index) -> array [n, 3] of (x, y, psi)")
     return nf
+
+
+@dataclass
+class VectorObs:
+    """The vector observation of BatchedWaypointEnv(obs_mode="vector") (tde_vector_obs, include/tde_hip.h): per env a float32 row of
+    dim = 10 + 9 * k_neighbours + 3 * n_rays values - the ego block (v, length, width, the offsets of the current and the next target
+    waypoint in the ego frame, targets left (at most 2), steps / max_steps, map-has-lights), the k_neighbours nearest other agents
+    within neighbour_radius (valid, forward, left, cos / sin of the relative heading, relative velocity forward / left, length,
+    width) and, per ray, the distances to the road edge, to another car and to a red stop line.  Positions are (forward, left) in
+    the ego frame.  No reference counterpart.
+
+      k_neighbours      neighbour entries per row, 0 .. 16
+      n_rays            rays per row, 0 .. 64, spread evenly counter-clockwise from straight ahead
+      ray_range         ray length [m]
+      ray_step          spacing of the road-edge samples along a ray [m]; ray_range / ray_step must be an integer <= 1024
+      neighbour_radius  agents farther than this from the ego are not neighbours [m]"""
+    k_neighbours: int = 8
+    n_rays: int = 32
+    ray_range: float = 50.0
+    ray_step: float = 0.5
+    neighbour_radius: float = 50.0
+
+    @property
+    def dim(self):
+        return 10 + 9 * int(self.k_neighbours) + 3 * int(self.n_rays)
+
+    def ray_directions(self):
+        """float32 [n_rays, 2]: unit vectors (forward, left) of the rays, ray k at angle 2 pi k / n_rays"""
+        import numpy as np
+
+        a = 2.0 * np.pi * np.arange(int(self.n_rays), dtype=np.float64) / max(1, int(self.n_rays))
+        return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], -1).astype(np.float32).reshape(int(self.n_rays), 2))
+
+    def slices(self):
+        """name -> slice of a row: ego fields, the neighbour block (reshape row[s] to [k_neighbours, 9]), the ray block (reshape to
+        [n_rays, 3]) and its three channels (strided slices, one value per ray)"""
+        k, n = int(self.k_neighbours), int(self.n_rays)
+        r0 = 10 + 9 * k
+        return {"v": slice(0, 1), "length": slice(1, 2), "width": slice(2, 3), "target": slice(3, 5), "next_target": slice(5, 7),
+                "targets_left": slice(7, 8), "progress": slice(8, 9), "has_lights": slice(9, 10), "ego": slice(0, 10),
+                "neighbours": slice(10, r0), "rays": slice(r0, r0 + 3 * n), "road": slice(r0, r0 + 3 * n, 3),
+                "car": slice(r0 + 1, r0 + 3 * n, 3), "red_line": slice(r0 + 2, r0 + 3 * n, 3)}
+
+
+def check_vector_obs(vo):
+    """validate a VectorObs (tde_vector_obs rejects the same); returns it (a dict is accepted as VectorObs(**dict))"""
+    import numpy as np
+
+    if isinstance(vo, dict):
+        vo = VectorObs(**vo)
+    if not isinstance(vo, VectorObs):
+        raise TypeError("vector_obs must be a VectorObs (or a dict of its fields)")
+    if not (0 <= int(vo.k_neighbours) <= 16) or not (0 <= int(vo.n_rays) <= 64):
+        raise ValueError("vector_obs: k_neighbours must be in [0, 16] and n_rays in [0, 64]")
+    vals = [np.float32(v) for v in (vo.neighbour_radius, vo.ray_range, vo.ray_step)]
+    if not all(np.isfinite(v) and v > 0 for v in vals):
+        raise ValueError("vector_obs: neighbour_radius, ray_range and ray_step must be finite and > 0")
+    q = np.float32(vals[1] / vals[2])
+    if not (1 <= q <= 1024) or q != np.rint(q):
+        raise ValueError("vector_obs: ray_range / ray_step must be an integer in [1, 1024]")
+    return vo

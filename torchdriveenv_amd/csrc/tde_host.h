@@ -101,6 +101,9 @@ int launch_render_scene(const tde_config *cfg, const tde_world *world, const tde
 // tde_near_field.hip: near_field_kernel (tde_near_field_spawn; arguments checked by the caller)
 int launch_near_field(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_near_field *nf,
                       const uint8_t *mask, void *stream);
+// tde_vector_obs.hip: vector_obs_kernel (tde_vector_obs; arguments checked by the caller)
+int launch_vector_obs(const tde_config *cfg, const tde_world *world, const tde_state *st, const struct tde_vector_obs *vo,
+                      const uint8_t *only, float *out, void *stream);
 
 }  // namespace tde_host
 

@@ -305,6 +305,28 @@ class EnvHandle {
         check_rc(tde_state_obs(&world_, &state_, p, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_state_obs");
     }
 
+    // tde_vector_obs: float32 [B, D] (D = 10 + 9 k_nbr + 3 n_rays) of the envs in `only` (all without it); ray_dir float32 [n_rays, 2]
+    void vector_obs(const at::Tensor &out, const at::Tensor &ray_dir, int64_t k_nbr, int64_t n_rays, double nbr_radius, double ray_range,
+                    double ray_step, const std::optional<at::Tensor> &only, int64_t flags)
+    {
+        TORCH_CHECK(k_nbr >= 0 && k_nbr <= TDE_VO_MAX_NBR && n_rays >= 0 && n_rays <= TDE_VO_MAX_RAYS, "vector_obs: k_nbr / n_rays out of range");
+        const int64_t D = TDE_VO_EGO + TDE_VO_NBR * k_nbr + TDE_VO_RAY * n_rays;
+        struct tde_vector_obs vo;
+        std::memset(&vo, 0, sizeof(vo));
+        vo.ray_dir = static_cast<const float *>(dev_ptr(ray_dir, at::kFloat, 2 * n_rays, "ray_dir", dev_));
+        vo.k_nbr = (int32_t)k_nbr;
+        vo.n_rays = (int32_t)n_rays;
+        vo.nbr_radius = (float)nbr_radius;
+        vo.ray_range = (float)ray_range;
+        vo.ray_step = (float)ray_step;
+        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, (int64_t)state_.B * D, "out", dev_)));
+        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        cfg_.flags = static_cast<uint32_t>(flags);
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_vector_obs(&cfg_, &world_, &state_, &vo, m, p, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                 "tde_vector_obs");
+    }
+
     // tde_ego_infractions: float32 [B, 4] = the ego's (offroad, collision, overlap count, 0) magnitudes of the state as it is (gym_env.py:427-428)
     void ego_infractions(const at::Tensor &out, int64_t flags)
     {
@@ -472,6 +494,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         .def("ego_infractions", &EnvHandle::ego_infractions, py::arg("out"), py::arg("flags"))
         .def("post_step", &EnvHandle::post_step, py::arg("magnitudes"), py::arg("flags"))
         .def("near_field_spawn", &EnvHandle::near_field_spawn, py::arg("nf"), py::arg("mask"), py::arg("flags"))
+        .def("vector_obs", &EnvHandle::vector_obs, py::arg("out"), py::arg("ray_dir"), py::arg("k_nbr"), py::arg("n_rays"),
+             py::arg("nbr_radius"), py::arg("ray_range"), py::arg("ray_step"), py::arg("only"), py::arg("flags"))
         .def_property_readonly("flags", &EnvHandle::flags)
         .def_property_readonly("num_envs", &EnvHandle::num_envs)
         .def_property_readonly("agents_per_env", &EnvHandle::agents_per_env);

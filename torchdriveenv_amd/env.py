@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _abi, ops
-from .config import EnvConfig, NearField, WaypointSuite, check_near_field, render_flags, to_tde_config, validate
+from .config import (EnvConfig, NearField, VectorObs, WaypointSuite, check_near_field, check_vector_obs, render_flags, to_tde_config,
+                     validate)
 from .state import EnvState
 from .video import VideoRecorder
 from .world import (NearFieldTable, World, assemble_world, build_near_field, check_threshold, corridor_mesh,
@@ -523,8 +524,9 @@ class BatchedWaypointEnv:
 
     step(actions [B,2]) -> (obs, reward f32[B], terminated bool[B], truncated bool[B], info dict of [B] tensors), all
     device-resident torch tensors.  obs is the ego-centred birdview uint8 [B, 3*frame_stack, 64, 64] (obs_mode
-    "birdview", the reference's observation, ref gym_env.py:95,122-124) or a compact float32 [B, 8] kinematic vector
-    (obs_mode "state").  Finished envs are re-spawned inside the same kernel (auto_reset=True); with a frame stack their
+    "birdview", the reference's observation, ref gym_env.py:95,122-124), a compact float32 [B, 8] kinematic vector
+    (obs_mode "state") or the float32 [B, D] vector observation of config.VectorObs (obs_mode "vector": nearest agents, road-edge,
+    car and red-line rays).  Finished envs are re-spawned inside the same kernel (auto_reset=True); with a frame stack their
     older frames restart blank in the same observation (VecFrameStack semantics, ref examples/rl_training.py:160).
     reward / terminated / truncated are the env's own buffers, overwritten by the next step (clone what must be
     kept).  (Replaying step + observation from a captured HIP graph was measured and is slower than the two direct
@@ -538,7 +540,7 @@ class BatchedWaypointEnv:
     def __init__(self, cfg: EnvConfig, data, num_envs, agents_per_env=16, device=None, obs_mode="birdview",
                  frame_stack=1, auto_reset=True, with_info=True, background=None, env_base=0, binding="ext",
                  info_magnitudes=True, road_meshes=None, near_range=None, traffic_lights=None, start_headings=None, light_radius=150.0,
-                 heading_samples=16, near_field=None):
+                 heading_samples=16, near_field=None, vector_obs=None):
         """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp), "ctypes" = through
         the ctypes binding of the same C-ABI (ops.py); both call the very same entry points of libtde_hip.so.
         info_magnitudes (default): info["offroad"] / info["collision"] hold the MAGNITUDES the reference reports there (ref
@@ -555,7 +557,9 @@ class BatchedWaypointEnv:
         iai_conditional_initialize, ref gym_env.py:232-238): a config.NearField (or a dict of its fields) when `data` is a
         WaypointSuite, or a world.NearFieldTable built for the World `data` is (world_from_waypoint_suite(..., near_field=)).  Every
         (re)spawn - reset(), auto-reset in step(), the VecEnv's re-spawn - then runs the spawner before the state is observed;
-        rollout() and the multi-stream step raise.  None (default): no near field, every path as it was."""
+        rollout() and the multi-stream step raise.  None (default): no near field, every path as it was.
+        vector_obs: the config.VectorObs (or a dict of its fields) of obs_mode="vector" (None: VectorObs()); the observation is
+        float32 [B, vector_obs.dim] (tde_vector_obs), taken after every reset, step and re-spawn (after the near-field spawner)."""
         validate(cfg)
         if near_field is not None and not isinstance(near_field, NearFieldTable):
             near_field = check_near_field(near_field, cfg)
@@ -568,8 +572,13 @@ class BatchedWaypointEnv:
             raise ValueError("a NearFieldTable belongs to the World it was built for: pass that World as `data`")
         if binding not in ("ext", "ctypes"):
             raise ValueError("binding must be 'ext' or 'ctypes'")                                              # ref gym_env.py:79-80 and the fields this path rejects
-        if obs_mode not in ("birdview", "state"):
-            raise ValueError("obs_mode must be 'birdview' or 'state'")
+        if obs_mode not in ("birdview", "state", "vector"):
+            raise ValueError("obs_mode must be 'birdview', 'state' or 'vector'")
+        if obs_mode == "vector" and int(frame_stack) > 1:
+            raise ValueError("obs_mode='vector' has no frame stack: frame_stack must be 1")
+        if vector_obs is not None and obs_mode != "vector":
+            raise ValueError("vector_obs= needs obs_mode='vector'")
+        self.vector_obs = check_vector_obs(vector_obs if vector_obs is not None else VectorObs()) if obs_mode == "vector" else None
         self.config = cfg
         dev = device or cfg.device or ("cuda" if torch.cuda.is_available() else None)
         if dev is None or not torch.cuda.is_available():
@@ -626,8 +635,12 @@ class BatchedWaypointEnv:
         self._rflags = render_flags(cfg)
         self._obs = self._stack = None
         self.action_space = _box(ACTION_LOW, ACTION_HIGH)
-        self.observation_space = (_box(0, 255, (3 * self.frame_stack, self._res, self._res), np.uint8)
-                                  if obs_mode == "birdview" else _box(-np.inf, np.inf, (8,), np.float32))
+        self.observation_space = (_box(0, 255, (3 * self.frame_stack, self._res, self._res), np.uint8) if obs_mode == "birdview" else
+                                  _box(-np.inf, np.inf, (self.vector_obs.dim if obs_mode == "vector" else 8,), np.float32))
+        self._vobs = self._ray_dir = None
+        if obs_mode == "vector":
+            self._vobs = torch.zeros((self.num_envs, self.vector_obs.dim), dtype=torch.float32, device=self.torch_device)
+            self._ray_dir = torch.from_numpy(self.vector_obs.ray_directions()).to(self.torch_device)
         self.reward_range = (-float("inf"), float("inf"))           # ref gym_env.py:97
         self._vec = None
         self._h = None
@@ -673,6 +686,8 @@ class BatchedWaypointEnv:
         else:
             ops.env_reset(self.tde_cfg, self.dworld, self.state, m)
         self._spawn_near_field(m)                                    # (near-field envs: reset -> spawn -> render)
+        if self.obs_mode == "vector":
+            return self._vector_obs(m)                               # (a masked reset rewrites the re-spawned envs' rows only)
         if self.obs_mode == "state" or m is None or self._obs is None:
             if self._stack is not None:
                 self._stack.clear()                                  # VecFrameStack clears the stack on reset
@@ -721,6 +736,8 @@ class BatchedWaypointEnv:
         st = self.state
         if self.obs_mode == "state":
             obs = st["obs"]
+        elif self.obs_mode == "vector":
+            obs = self._vector_obs()
         else:
             fresh = None
             if self.auto_reset and self.frame_stack > 1:
@@ -760,6 +777,8 @@ class BatchedWaypointEnv:
         info = _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
         if self.obs_mode == "state":
             obs = st["obs"]                                           # written by the step, refreshed by the re-spawn
+        elif self.obs_mode == "vector":
+            obs = self._vector_obs()
         else:
             # the finished envs were re-spawned: their frame stacks restart blank (bits 0-1 of done_bits = the step's done flags)
             fresh = None
@@ -784,6 +803,8 @@ class BatchedWaypointEnv:
         return ops.env_rollout(self.tde_cfg, self.dworld, self.state, a)
 
     def get_obs(self, fresh=None):
+        if self.obs_mode == "vector":
+            return self._vector_obs()
         if self.obs_mode == "state":
             # x, y, psi, v, target offset (forward, left) in the ego frame, target-exists flag, environment_steps
             if self._h is not None:
@@ -800,6 +821,16 @@ class BatchedWaypointEnv:
             self._obs = torch.zeros((self.num_envs, 3, self._res, self._res), dtype=torch.uint8, device=self.torch_device)
         self._render1(self._obs)
         return self._obs
+
+    def _vector_obs(self, only=None):
+        """tde_vector_obs into the env's [B, D] buffer (the rows of `only`, uint8 [B], or all) -> the buffer"""
+        vo = self.vector_obs
+        if self._h is not None:
+            self._h.vector_obs(self._vobs, self._ray_dir, int(vo.k_neighbours), int(vo.n_rays), float(vo.neighbour_radius),
+                               float(vo.ray_range), float(vo.ray_step), only, int(self.tde_cfg.flags))
+        else:
+            ops.vector_obs(self.tde_cfg, self.dworld, self.state, vo, self._ray_dir, self._vobs, only)
+        return self._vobs
 
     def _render1(self, out, only=None):
         """single-frame raster of every (or the masked) view into `out`"""

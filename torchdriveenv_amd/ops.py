@@ -231,6 +231,28 @@ def state_obs(dworld, state, out=None):
     return out
 
 
+def vector_obs(cfg, dworld, state, vo, ray_dir=None, out=None, only=None):
+    """tde_vector_obs: the vector observation of every env (or of those in `only`, uint8 [B] on the device; the other rows of `out`
+    are left as they are) -> float32 [B, D] on the device, D = vo.dim.  vo: config.VectorObs; ray_dir: its ray_directions() as a
+    float32 [n_rays, 2] device tensor (formed from vo when None).  Asynchronous."""
+    from .config import check_vector_obs
+
+    vo = check_vector_obs(vo)
+    L = _lib.load()
+    dev = torch.device(state.device)
+    if ray_dir is None:
+        ray_dir = torch.from_numpy(vo.ray_directions()).to(dev)
+    if out is None:
+        out = torch.empty((state.B, vo.dim), dtype=torch.float32, device=dev)
+    pr = _chk(ray_dir, torch.float32, 2 * vo.n_rays, "ray_dir", dev)
+    po = _chk(out, torch.float32, state.B * vo.dim, "out", dev)
+    pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
+    s = _abi.TdeVectorObs(pr, vo.k_neighbours, vo.n_rays, vo.neighbour_radius, vo.ray_range, vo.ray_step, 0)
+    _lib.check(_call(dev, L.tde_vector_obs, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(s), pm, po,
+                     _lib.current_stream(dev)), "tde_vector_obs")
+    return out
+
+
 def render_ego(cfg, dworld, state, H=64, W=64, fov=35.0, n_stack=1, out=None, layers=None, phase=0, flags=0,
                fresh=None, only=None):
     """render_egocentric() of every env's ego -> uint8 [B, 3*n_stack, H, W] on device (ref gym_env.py:122-124).

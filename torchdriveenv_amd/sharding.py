@@ -137,7 +137,12 @@ class ShardedBatchedEnv:
         obs_mode = env_kw.get("obs_mode", "birdview")
         fs = max(1, int(env_kw.get("frame_stack", 1)))
         r = cfg.simulator.renderer
-        oshape = (3 * fs, int(r.res), int(r.res)) if obs_mode == "birdview" else (8,)
+        if obs_mode == "vector":
+            from .config import VectorObs, check_vector_obs
+            vo = env_kw.get("vector_obs")
+            oshape = (check_vector_obs(vo if vo is not None else VectorObs()).dim,)
+        else:
+            oshape = (3 * fs, int(r.res), int(r.res)) if obs_mode == "birdview" else (8,)
         odt = torch.uint8 if obs_mode == "birdview" else torch.float32
         self._shm = {"obs": torch.zeros((self.num_envs,) + oshape, dtype=odt).share_memory_(),
                      "reward": torch.zeros(self.num_envs, dtype=torch.float32).share_memory_(),
