@@ -400,6 +400,31 @@ TDE_DEV bool box_offroad(const tde_world &w, const tde_map &m, bool live, float 
     return offroad_resolve<PAIR, CLS2>(w, k, thr2, m.rec_base);
 }
 
+// ONE corner of the box per lane: corner i (0 FL, 1 FR, 2 RR, 3 RL, offroad_issue's order) is off the road.  The box is off
+// (box_offroad) iff one of its four corners is: box_offroad's early exits only skip corners.  Same corner arithmetic as
+// offroad_issue with the signs as operands (u - v == u + (-v) exactly), same cell look-up, and offroad_resolve's test for a
+// corner in a MIXED cell (one record per trip: on the road at the first record within sqrt(thr2), off after the last).
+template <bool CLS2 = false>
+TDE_DEV bool corner_offroad(const tde_world &w, const tde_map &m, int i, float x, float y, float c, float s, float hl, float hw,
+                            float thr2)
+{
+    const float lx = hl * c, ly = hl * s, wx = hw * s, wy = hw * c;
+    const bool front = i < 2, right = i == 1 || i == 2;
+    const float px = (x + (front ? lx : -lx)) + (right ? wx : -wx);
+    const float py = (y + (front ? ly : -ly)) + (right ? -wy : wy);
+    uint32_t wd = CLS2 ? cell_class_lookup(w, m, px, py) : cell_lookup(w, m, px, py);
+    const uint32_t cls = wd & 3u;
+    if (cls != TDE_CELL_MIXED) return cls == TDE_CELL_EMPTY;
+    if constexpr (CLS2) wd = w.cell_word[wd >> 2];
+    uint32_t cur = (wd >> 10) + (uint32_t)m.rec_base;
+    const uint32_t end = cur + ((wd >> 2) & 255u);
+    const float4 *recs = reinterpret_cast<const float4 *>(w.cell_tri);
+    do {
+        if (point_tri_d2_packed(px, py, recs + 3 * (size_t)cur) <= thr2) return false;
+    } while (++cur != end);
+    return true;
+}
+
 // Philox4x32-10, key = seed, counter = (c0,c1,c2,c3) — the reset RNG (R16).  Returned by value (uint4) so the four
 // words live in registers: an output array would be placed in scratch memory.
 TDE_DEV uint4 philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3)

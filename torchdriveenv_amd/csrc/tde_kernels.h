@@ -2306,6 +2306,14 @@ template <int N> TDE_DEV void dummy_valu(float seed)
 #define TDE_ROLLOUT_CONST_ARGS 0
 #endif
 struct RolloutArgs { tde_config cfg; tde_world w; tde_state st; tde_rollout ro; uint32_t act_hash; };
+// a ballot with the OR of each env's A lane bits on the env's first (ego) lane bit; the other bits hold partial ORs
+// (wave-uniform: scalar shifts by constant amounts)
+template <int A> TDE_DEV unsigned long long fold_env_to_ego(unsigned long long m)
+{
+#pragma unroll
+    for (int s = 1; s < A; s <<= 1) m |= m >> s;
+    return m;
+}
 #if TDE_ROLLOUT_CONST_ARGS
 __constant__ RolloutArgs g_rollout_args;
 #endif
@@ -2331,6 +2339,11 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6)
         sh.red_seq = -1;
     }
     const uint32_t F = cfg.flags;
+    // Before the launch's last step the judges compute the EGO's collision / offroad flags only (the done byte and the reward read
+    // nothing else; every slot's flags are stored after the last step, which keeps the all-slot forms).  Where the ego forms fit
+    // the 80-VGPR budget: at A = 32, and for judge O with LIGHTS, either form raised the kernel's spills above the all-slot form's
+    // (profiles/ego_judges_kernel_resources.txt), so those keep the all-slot forms at every step.
+    constexpr bool kEgoJudgeC = A <= 16, kEgoJudgeO = A <= 16 && !LIGHTS;
     // Traffic lights (LIGHTS): the NPCs' gaps to red stop lines are JUDGE C's work - first thing behind barrier B, from the rows the
     // driver's controller is reading at that moment, handed over through LDS (sh.red_gap / sh.red_seq; the driver needs them only at
     // the end of its sweep).  In the driver the map's light fields, the red-mask window and the four-lines-per-trip loop (32
@@ -2613,11 +2626,30 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6)
             const int k = er.steps;
             if (lights && i + 1 < ro.K) publish_red_gaps(i + 1, p, k + 1);      // the driver is computing step i + 1 from these rows now
             const float4 ra = sh.a[p][lane], rb = sh.b[p][lane], rc = sh.c[p][lane];
-            if constexpr (A == 16 && TDE_COLLIDE_DPP)
-                hit = collide_rows_dpp16(&sh.a[p][base], &sh.b[p][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
-            else
-                hit = collide_rows<A>(&sh.a[p][base], &sh.b[p][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
-            const unsigned long long m = __ballot(hit);
+            unsigned long long m;
+            if (kEgoJudgeC && i + 1 < ro.K) {
+                // before the launch's last step only the EGO's flag is read (done_of: infr & ego), so lane a >= 1 tests the one
+                // pair (ego, slot a): the circumradius verdict of collide_rows / collide_rows_dpp16 (the same sign bit: the
+                // differences negate exactly when the pair is swapped, rr is a commutative sum) and the ego lane's own exact
+                // test of that partner, same operands in the same order.  The env's OR lands on the ego lane's bit.
+                const float4 ea = sh.a[p][base];
+                const float dx = ra.x - ea.x, dy = ra.y - ea.y, rr = ea.z + ra.z;
+                const float dy2 = dy * dy;
+                const float v = __builtin_fmaf(-rr, rr, __builtin_fmaf(dx, dx, dy2));
+                bool pair = false;
+                if (a > 0 && (__float_as_uint(v) >> 31) && sh.c[p][base].z != 0.0f) {      // (a candidate of a live ego)
+                    const float4 eb = sh.b[p][base];
+                    pair = obb_overlap(ea.x, ea.y, eb.x, eb.y, eb.z, eb.w, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w);
+                }
+                m = fold_env_to_ego<A>(__ballot(pair));
+            } else {
+                // the last step: every slot's flag (st.collided below)
+                if constexpr (A == 16 && TDE_COLLIDE_DPP)
+                    hit = collide_rows_dpp16(&sh.a[p][base], &sh.b[p][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
+                else
+                    hit = collide_rows<A>(&sh.a[p][base], &sh.b[p][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
+                m = __ballot(hit);
+            }
             if (lane == 0) sh.hit_mask = m;
             TDE_PROBE(TDE_DUMMY_C, ra.x);
             if (batch) {
@@ -2684,7 +2716,23 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6)
             const float4 ra = sh.a[p][lane], rb = sh.b[p][lane], rc = sh.c[p][lane];
             const bool live = rc.z != 0.0f;
             off = false;
-            if (F & TDE_F_OFFROAD) off = box_offroad<false, BIG || TDE_ROLLOUT_CLS2>(w, cx.m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, thr2);
+            unsigned long long om = 0ull;
+            if (F & TDE_F_OFFROAD) {
+                if (kEgoJudgeO && i + 1 < ro.K) {
+                    // before the launch's last step only the EGO's flag is read (done_of: infr & ego): lanes 0..3 of the env test
+                    // one corner of the ego's box each (cx.m is the env's map on every lane) and the OR lands on the ego's bit
+                    bool corner = false;
+                    if (a < 4 && sh.c[p][base].z != 0.0f) {
+                        const float4 ea = sh.a[p][base], eb = sh.b[p][base];
+                        corner = corner_offroad<BIG || TDE_ROLLOUT_CLS2>(w, cx.m, a, ea.x, ea.y, eb.x, eb.y, eb.z, eb.w, thr2);
+                    }
+                    om = fold_env_to_ego<A>(__ballot(corner));
+                } else {
+                    // the last step: every slot's flag (st.offroad below)
+                    off = box_offroad<false, BIG || TDE_ROLLOUT_CLS2>(w, cx.m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, thr2);
+                    om = __ballot(off);
+                }
+            }
             tl = false;
             if (lights && a == 0 && valid) {
                 const int4 lw = sh.lights2[p][lane / A];     // judge C's: (red mask at this step, -, stop_base, n_stop) of the env's map
@@ -2692,7 +2740,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6)
                 else tl = tl_violation_of(CachedLines<A>{sh, w.stoplines + lw.z, lane / A}, lw.w, (uint32_t)lw.x, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w);
             }
             TDE_PROBE(TDE_DUMMY_O, ra.x);
-            const unsigned long long om = __ballot(off), tm = __ballot(tl);
+            const unsigned long long tm = __ballot(tl);
             if (lane == 0) { sh.off_mask = om; sh.tl_mask = tm; }
             if (ego) sh.act[p][lane] = act2;                 // step i+2 -> slot i & 1 (step i's action is consumed: B passed)
         }
