@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TDE_ABI_VERSION 12
+#define TDE_ABI_VERSION 13
 #define TDE_MAX_AGENTS 128
 
 /* feature bits of tde_config.flags */
@@ -470,6 +470,33 @@ struct tde_vector_obs {      /* a struct tag without a typedef: the name is also
     float ray_step;             /* road-march sample spacing [m]; ray_range / ray_step is an integer M */
     int32_t _pad0;              /* 32 bytes */
 };
+
+/* (ABI 13) Sampling planner (tde_plan_action, include/tde_hip.h): a lattice of constant (acceleration, steering) candidates rolled
+ * forward through the step's own kinematics and judged by the step's own predicates (no reference counterpart).  A HOST struct; the
+ * two lattice tables are INLINE (the entry point checks their values on the host; the kernel reads them from its argument block). */
+#define TDE_PLAN_MAX_CAND 64    /* n_a * n_s in [1, TDE_PLAN_MAX_CAND]: one lane of a wavefront per candidate */
+#define TDE_PLAN_MAX_H    32    /* horizon in [1, TDE_PLAN_MAX_H] */
+#define TDE_PLAN_FAIL_UNIT 2048.0f /* cost per horizon step a candidate fails early */
+#define TDE_PLAN_RUN_MAX   1024.0f /* the running cost is clamped to [0, TDE_PLAN_RUN_MAX] ... */
+#define TDE_PLAN_RUN_BIAS  512.0f  /* ... after this is added to it (progress enters it negatively) */
+typedef struct tde_planner {
+    float accel[TDE_PLAN_MAX_CAND]; /* the first n_a used, each in [-1, 1] (gym_env.py:83) */
+    float steer[TDE_PLAN_MAX_CAND]; /* the first n_s used, each in [-0.3, 0.3] (gym_env.py:84) */
+    int32_t n_a, n_s;           /* candidate i = ia * n_s + is has (accel[ia], steer[is]) */
+    int32_t horizon;            /* H steps of config.dt */
+    float v_target;             /* speed the plan tracks while a target waypoint exists [m/s], >= 0 */
+    float margin;               /* added to the half extents of the other agents' predicted boxes [m], >= 0 */
+    float w_progress;           /* cost weights (>= 0): per metre gained towards the target waypoint */
+    float w_speed;              /*                      per (m/s)^2 of speed error, summed over the steps */
+    float w_steer;              /*                      per rad^2 of the candidate's steering */
+} tde_planner;
+
+typedef struct tde_plan_diag {  /* 16 bytes per env */
+    int32_t winner;             /* index of the winning candidate */
+    int32_t fail_step;          /* its failure step f in 1..H, H + 1 = it never fails */
+    float cost;                 /* its cost */
+    int32_t n_safe;             /* candidates with f == H + 1; 0 = "no safe plan" (the winner is then the one that fails last) */
+} tde_plan_diag;
 
 #ifdef __cplusplus
 }

@@ -233,6 +233,46 @@ TDE_API int tde_near_field_spawn(const tde_config *cfg, const tde_world *world, 
 TDE_API int tde_vector_obs(const tde_config *cfg, const tde_world *world, const tde_state *state, const struct tde_vector_obs *vo,
                            const uint8_t *only, float *out, void *stream);
 
+/* (ABI 13) Sampling planner: for every env with only[e] != 0 (uint8 [B]; NULL: all envs) action[e] = (acceleration, steering) for
+ * the ego (slot 0) on the state as it is; the other rows of action (and of diag) are not written.  No reference counterpart (its
+ * policies come from outside: examples/rl_training.py).  plan = tde_planner (tde_abi.h, a HOST struct with its lattice inline).
+ * Every expression below is float32 with one rounding per written operation (no contraction); (s, c) of a heading = sincos_f32
+ * (tde_device.h); bicycle and obb_overlap are the step's own (tde_device.h); tests/planner_ref.py restates this in numpy.
+ * Env e: s = state.scn[e], m = world.maps[world.scn[s].map], wp_n = world.scn[s].wp_n, ego = slot 0: (x0, y0, psi0, v0), inv_lr =
+ * 1.0f / lr0, hl0 = 0.5f * len0, hw0 = 0.5f * wid0, dt = config.dt, H = plan.horizon, rr = (float)config.reach_radius.
+ * Candidate i in [0, n_a * n_s): a = accel[i / n_s], d = steer[i % n_s].
+ *   Trajectory  (x, y, psi, v) = the ego's state; for h = 1..H: a_h = 0.0f when v + a * dt < 0.0f (a candidate does not plan to
+ *               reverse), else a; bicycle(x, y, psi, v, inv_lr, a_h, d, dt) gives s_h; (sn, cs) = sincos_f32(psi) of s_h.
+ *   Others      every present slot j in 1..A-1, (c_j, s_j) = sincos_f32(psi_j): at step h the box (x_j + (float)h * ((v_j * c_j) *
+ *               dt), y_j + (float)h * ((v_j * s_j) * dt), c_j, s_j, 0.5f * len_j + margin, 0.5f * wid_j + margin).
+ *   Failure     f = the first h in 1..H at which one of these holds for s_h, else H + 1:
+ *               (i)   a corner of the box (x, y, cs, sn, hl0, hw0) is off the road: the step's predicate (tde_compute_offroad: corners
+ *                     FL, FR, RR, RL = (x +- hl0*cs) -+ hw0*sn, (y +- hl0*sn) +- hw0*cs; d^2 > thr2 with thr2 as
+ *                     config.offroad_threshold_squared selects; the grid index equals the brute force over m's triangles);
+ *               (ii)  obb_overlap(ego box; box of j at step h) for some j (the ego's box first, not inflated);
+ *               (iii) with TDE_F_TRAFFIC_LIGHTS, m.n_stop > 0 and m.cycle_steps > 0: obb_overlap(ego box; x, y, c, s, hl, hw of stop
+ *                     line q of m) for a q with (red >> (light_q & 31)) & 1, red = the red mask of the phase of (state.steps[e] + h) %
+ *                     cycle_steps - the value of environment_steps the real step would judge s_h under.
+ *   Cost        ti = state.target_idx[e], gain = 0, sv = 0; when ti < wp_n: (wx, wy) = ((float)wp.x, (float)wp.y) of waypoint ti, dx =
+ *               wx - x0, dy = wy - y0, dp = sqrtf(dx*dx + dy*dy).  At every step h < f, in this order, on s_h:
+ *                 when ti < wp_n: dx = wx - x, dy = wy - y, dn = sqrtf(dx*dx + dy*dy); gain = gain + (dp - dn); dp = dn; when dn < rr
+ *                   (check_reach_target, gym_env.py:391-394, in float32): ti = ti + 1 and, when still ti < wp_n, (wx, wy) = waypoint
+ *                   ti and dp = its distance from s_h by the same expression;
+ *                 ev = v - (ti < wp_n ? v_target : 0.0f) (a finished route plans a stop); sv = sv + ev * ev.
+ *               run = (w_speed * sv + w_steer * (d * d)) - w_progress * gain;
+ *               cost = (float)(H + 1 - f) * TDE_PLAN_FAIL_UNIT + fminf(fmaxf(run + TDE_PLAN_RUN_BIAS, 0.0f), TDE_PLAN_RUN_MAX):
+ *               a candidate that fails earlier costs more than any that fails later or never, whatever the weights.
+ *   Winner      the least (k, i), k = the cost's bits b as an ordered integer (b ^ 0x80000000 for b >= 0 as int32, else ~b): exact ties
+ *               go to the lower index; when every candidate fails this picks the one that fails last.
+ *   action[e] = (a_1 of the winner - its a after the no-reverse rule at the state as it is -, its d);
+ *   diag[e]   = (winner, its f, its cost, the number of candidates with f == H + 1) when diag != NULL.
+ * One wavefront per env, one lane per candidate, four envs per workgroup; reads state only.  Rejected: NULL cfg / world / state /
+ * plan / action, n_a or n_s < 1 or n_a * n_s > TDE_PLAN_MAX_CAND, horizon outside [1, TDE_PLAN_MAX_H], an accel outside [-1, 1] or a
+ * steer outside [-0.3, 0.3] (gym_env.py:83-84) or not finite, v_target / margin / a weight negative or not finite, config.dt not
+ * finite or <= 0.  No allocation, no synchronisation (graph-capturable). */
+TDE_API int tde_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_planner *plan,
+                            const uint8_t *only, float *action, tde_plan_diag *diag, void *stream);
+
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 
 /* Offroad grid index of ONE drivable mesh - what the simulator prepares once per map from the road mesh it is constructed

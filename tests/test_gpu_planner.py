@@ -1,0 +1,302 @@
+"""tde_plan_action on the GPU against its numpy restatement (tests/planner_ref.py), bit for bit - actions as uint32 patterns, every
+diag field equal - through both bindings: a junction world at 16 slots on fresh resets and on the states a few hundred steps under the
+planner's own actions reach, the default lattice and a 64-candidate one, horizons 1 and 32, towns (the large-grid path), 128 crowded
+slots, lights across phase changes, egos near and beyond the grid edge and off the road, `only` masks, both threshold readings, two
+shards against one batch; and the behaviour: the planner against the zero and the uniform random policy on the same world, seed and
+batch."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle
+from tests import planner_ref as R
+from torchdriveenv_amd import _abi, _ext, ops
+from torchdriveenv_amd.config import EnvConfig, Planner
+from torchdriveenv_amd.env import BatchedWaypointEnv
+from torchdriveenv_amd.state import EnvState
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+WIDE = Planner(accelerations=(-1.0, -0.6, -0.3, 0.0, 0.2, 0.4, 0.7, 1.0), steerings=(-0.3, -0.15, -0.05, 0.0, 0.02, 0.08, 0.2, 0.3),
+               horizon=20, v_target=7.0, margin=0.5, w_progress=2.0, w_speed=0.1, w_steer=4.0)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _arrays(hs):
+    return hs.arrays if hasattr(hs, "arrays") else hs
+
+
+def _check(cfg, world, hs, pl, only=None, what=""):
+    """the kernel (both bindings) on the device copy of host state `hs` == the restatement; returns (actions, diag) of the latter"""
+    B, A = len(hs["scn"]), world.A
+    fill = only is not None
+    act0 = np.full((B, 2), -3.0, np.float32)
+    dg0 = np.full((B, 4), -7, np.int32)
+    want_a, want_d = R.plan(cfg, world, hs, pl, only=only, out=act0 if fill else None, diag=dg0 if fill else None)
+    dw = world.to_device(DEV)
+    ds = EnvState(B, A, device=DEV)
+    ds.load({k: v for k, v in _arrays(hs).items() if v is not None})
+    m = torch.from_numpy(np.asarray(only, np.uint8)).to(DEV) if only is not None else None
+    for binding in ("ctypes", "ext"):
+        out = torch.full((B, 2), -3.0, dtype=torch.float32, device=DEV)
+        dg = torch.full((B, 4), -7, dtype=torch.int32, device=DEV)
+        if binding == "ctypes":
+            ops.plan_action(cfg, dw, ds, pl, out, m, dg)
+        else:
+            _ext.env_handle(cfg, dw, ds).plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings],
+                                                     int(pl.horizon), float(pl.v_target), float(pl.margin), float(pl.w_progress),
+                                                     float(pl.w_speed), float(pl.w_steer), m, dg, int(cfg.flags))
+        torch.cuda.synchronize()
+        got_a = out.cpu().numpy()
+        got_d = dg.cpu().numpy().view(_abi.PLAN_DIAG_DTYPE).reshape(B)
+        for n in ("winner", "fail_step", "n_safe"):
+            bad = np.flatnonzero(got_d[n] != want_d[n])
+            assert len(bad) == 0, (what, binding, n, bad[:8].tolist(), got_d[bad[:4]], want_d[bad[:4]])
+        assert np.array_equal(got_d["cost"].view(np.uint32), want_d["cost"].view(np.uint32)), (what, binding, "cost")
+        bad = np.argwhere(_bits(got_a) != _bits(want_a))
+        assert len(bad) == 0, (what, binding, bad[:8].tolist(), got_a[bad[0][0]], want_a[bad[0][0]])
+    return want_a, want_d
+
+
+def _reset_state(cfg, world, B, episode=0):
+    hs = EnvState(B, world.A)
+    hs["episode"][...] = episode
+    oracle.env_reset(cfg, world, hs)
+    return hs
+
+
+def _lights_cfg(world, **kw):
+    cfg = _abi.default_config(**kw)
+    if world.has_lights:
+        cfg.flags |= _abi.F_TRAFFIC_LIGHTS
+    return cfg
+
+
+@pytest.mark.parametrize("pl", [Planner(), WIDE, Planner(horizon=1), Planner(accelerations=(0.0,), steerings=(0.0,), horizon=32)],
+                         ids=["default", "wide64", "h1", "one"])
+def test_junction_world_at_16_slots(small_world, pl):
+    cfg = _lights_cfg(small_world, seed=3)
+    hs = _reset_state(cfg, small_world, 192)
+    act, dg = _check(cfg, small_world, hs, pl, what="junctions")
+    if pl.n_candidates > 1 and pl.horizon > 1:
+        assert len(np.unique(dg["winner"])) > 3 and (dg["n_safe"] > 0).any() and (dg["n_safe"] < pl.n_candidates).any()
+
+
+@pytest.mark.parametrize("binding", ["ext", "ctypes"])
+def test_states_reached_under_the_planners_own_actions(small_world, binding):
+    """closed loop with auto-reset: step(plan_actions()) for 300 steps, the plan of every 25th state against the restatement (queues
+    behind NPCs, red lines, junction turns), and the env's own plan_actions() row for row"""
+    cfg = EnvConfig(seed=14, distance_cutoff=0.25, max_environment_steps=200)
+    B = 96
+    pl = Planner()
+    env = BatchedWaypointEnv(cfg, small_world, num_envs=B, device=DEV, obs_mode="state", binding=binding, planner=pl)
+    env.reset()
+    safe = unsafe = 0
+    for t in range(300):
+        a, d = env.plan_actions(diag=True)
+        if t % 25 == 0:
+            hs = env.state.host()
+            want_a, want_d = _check(env.tde_cfg, small_world, hs, pl, what=("loop", t))
+            assert np.array_equal(_bits(a.cpu().numpy()), _bits(want_a)), t
+            assert np.array_equal(d.cpu().numpy().view(_abi.PLAN_DIAG_DTYPE).reshape(B)["winner"], want_d["winner"]), t
+            unsafe += int((want_d["n_safe"] < pl.n_candidates).sum())
+            safe += int((want_d["n_safe"] > 0).sum())
+        env.step(a)
+    assert safe > 0 and unsafe > 0
+
+
+def test_towns_large_grid(small_town, town):
+    cfg = _lights_cfg(small_town, seed=4)
+    hs = _reset_state(cfg, small_town, 96)
+    hs["steps"][...] = np.arange(96) * 3
+    _check(cfg, small_town, hs, Planner(), what="town")
+    assert town.arrays["maps"]["nx"].max() * town.arrays["maps"]["ny"].max() > 2 ** 21       # (TDE_WORLD_LARGE_GRID)
+    cfg = _lights_cfg(town, seed=6)
+    _check(cfg, town, _reset_state(cfg, town, 24), Planner(horizon=16), what="town 1 km")
+
+
+def test_128_crowded_slots():
+    from torchdriveenv_amd.synth import synthetic_world
+
+    world = synthetic_world(n_scn=4, A=128, seed=5, n_maps=2)
+    cfg = _lights_cfg(world, seed=5)
+    B, A = 32, 128
+    hs = _reset_state(cfg, world, B)
+    rng = np.random.default_rng(7)
+    x, y = hs["x"].reshape(B, A), hs["y"].reshape(B, A)
+    # every slot present, scattered within 40 m of the ego but not on it, moving
+    ang, rad = rng.uniform(-np.pi, np.pi, (B, A - 1)), rng.uniform(6, 40, (B, A - 1))
+    x[:, 1:] = x[:, :1] + (rad * np.cos(ang)).astype(np.float32)
+    y[:, 1:] = y[:, :1] + (rad * np.sin(ang)).astype(np.float32)
+    hs["psi"].reshape(B, A)[:, 1:] = rng.uniform(-3.1, 3.1, (B, A - 1)).astype(np.float32)
+    hs["v"].reshape(B, A)[:, 1:] = rng.uniform(0, 12, (B, A - 1)).astype(np.float32)
+    hs["present"][...] = 1
+    for pl in (Planner(), WIDE):
+        act, dg = _check(cfg, world, hs, pl, what="crowded")
+        assert (dg["fail_step"] <= pl.horizon).any()
+
+
+def test_lights_across_phase_changes(small_world):
+    cfg = _lights_cfg(small_world, seed=11)
+    assert cfg.flags & _abi.F_TRAFFIC_LIGHTS
+    B, A = 128, small_world.A
+    hs = _reset_state(cfg, small_world, B)
+    # half of the egos a few metres in front of a stop line of their map, heading across it
+    mp, stop = small_world.arrays["maps"], small_world.arrays["stoplines"]
+    m = small_world.map_of_scn()[hs["scn"]]
+    rng = np.random.default_rng(5)
+    for e in range(0, B, 2):
+        n = int(mp["n_stop"][m[e]])
+        if n == 0:
+            continue
+        ln = stop[int(mp["stop_base"][m[e]]) + int(rng.integers(n))]
+        back = rng.uniform(3.0, 12.0)
+        hs["x"][e * A], hs["y"][e * A] = ln["x"] - back * ln["c"], ln["y"] - back * ln["s"]
+        hs["psi"][e * A] = np.arctan2(ln["s"], ln["c"])
+        hs["v"][e * A] = rng.uniform(2.0, 8.0)
+    seen = []
+    for k in (0, 40, 79, 80, 95, 120, 145, 159, 160, 400):
+        hs["steps"][...] = k
+        act, dg = _check(cfg, small_world, hs, Planner(), what=("lights", k))
+        seen.append(int(dg["n_safe"].sum()))
+    assert len(set(seen)) > 1                                        # which candidates are safe changes with the phase
+
+
+def test_egos_near_the_grid_edge_and_offroad(small_world):
+    cfg = _lights_cfg(small_world, seed=12)
+    B, A = 192, small_world.A
+    hs = _reset_state(cfg, small_world, B)
+    mp = small_world.arrays["maps"]
+    m = small_world.map_of_scn()[hs["scn"]]
+    ox, oy = mp["ox"][m], mp["oy"][m]
+    h = mp["ny"][m] * mp["cell"][m]
+    rng = np.random.default_rng(2)
+    x0, y0 = hs["x"][::A].astype(np.float64), hs["y"][::A].astype(np.float64)
+    a, b = slice(0, B // 3), slice(B // 3, 2 * (B // 3))
+    n = B // 3
+    # near the edge (inside), beyond it by 1 to 30 m (the clamp to the EMPTY border), and a few metres off the road
+    x0[a] = ox[a] + rng.uniform(0.2, 3.0, n)
+    y0[a] = oy[a] + rng.uniform(0.0, 1.0, n) * h[a]
+    x0[b] = ox[b] - rng.uniform(1.0, 30.0, n)
+    y0[b] = oy[b] + rng.uniform(-10.0, 30.0, n) + h[b]
+    x0[2 * n:] += rng.uniform(3.0, 9.0, B - 2 * n)
+    hs["x"][::A], hs["y"][::A] = x0.astype(np.float32), y0.astype(np.float32)
+    hs["psi"][::A] = rng.uniform(-3.14, 3.14, B).astype(np.float32)
+    act, dg = _check(cfg, small_world, hs, Planner(), what="edge")
+    assert (dg["n_safe"][b] == 0).all() and (dg["fail_step"][b] == 1).all()      # off the grid: every candidate fails at once
+    assert (dg["fail_step"][2 * n:] > 1).any()
+
+
+def test_only_masks_leave_the_other_rows(small_world):
+    cfg = _lights_cfg(small_world, seed=8)
+    hs = _reset_state(cfg, small_world, 100)
+    only = (np.random.default_rng(0).random(100) < 0.3).astype(np.uint8)
+    _check(cfg, small_world, hs, Planner(horizon=12), only=only, what="only")
+    _check(cfg, small_world, hs, Planner(horizon=12), only=np.zeros(100, np.uint8), what="none")
+
+
+@pytest.mark.parametrize("squared", [False, True])
+def test_both_threshold_readings(squared):
+    from torchdriveenv_amd.synth import synthetic_world
+    from torchdriveenv_amd.world import effective_offroad_distance
+
+    world = synthetic_world(n_scn=8, A=16, seed=0, n_maps=2, threshold=effective_offroad_distance(0.5, squared))
+    cfg = _lights_cfg(world, seed=3, offroad_threshold=0.5, offroad_threshold_squared=int(squared))
+    hs = _reset_state(cfg, world, 8 if squared else 64)               # (the squared reading's checker walks the mesh per corner)
+    act, dg = _check(cfg, world, hs, Planner(horizon=10 if squared else 32), what=("squared", squared))
+    assert (dg["n_safe"] > 0).any()
+
+
+def test_two_shards_equal_the_unsharded_batch(small_world):
+    from torchdriveenv_amd.sharding import ShardedBatchedEnv
+
+    cfg = EnvConfig(seed=52, distance_cutoff=0.25, max_environment_steps=25)
+    B = 64
+    one = BatchedWaypointEnv(cfg, small_world, num_envs=B, device=DEV, obs_mode="state").as_vec_env()
+    two = ShardedBatchedEnv(cfg, small_world, B, n_shards=2, devices=[0, 0], obs_mode="state")
+    try:
+        one.reset(), two.reset()
+        n_done = 0
+        for t in range(40):
+            aa, da = one.plan_actions(diag=True)
+            ab, db = two.plan_actions(diag=True)
+            assert aa.shape == (B, 2) and np.array_equal(_bits(aa), _bits(ab)) and np.array_equal(da, db), t
+            _, _, d1, _ = one.step(aa)
+            _, _, d2, _ = two.step(ab)
+            assert np.array_equal(d1, d2)
+            n_done += int(d1.sum())
+        assert n_done > 0
+    finally:
+        two.close()
+
+
+def test_one_env_surface(small_world_a8):
+    from torchdriveenv_amd.env import SingleAgentWrapper, WaypointSuiteEnv
+
+    cfg = EnvConfig(seed=5, distance_cutoff=0.25)
+    env = SingleAgentWrapper(WaypointSuiteEnv(cfg, small_world_a8, agents_per_env=8, planner=Planner(horizon=16)))
+    env.reset()
+    for _ in range(5):
+        a = env.expert_action()
+        assert a.shape == (2,) and a.dtype == np.float32 and abs(a[0]) <= 1 and abs(a[1]) <= np.float32(0.3)
+        env.step(a)
+    env.close()
+
+
+# ---- behaviour -----------------------------------------------------------------------------------------------------------------------
+
+BEHAVIOUR_B, BEHAVIOUR_STEPS = 512, 400       # 512 envs x 2 * max_steps (200) steps per policy, the same world, seed and batch
+
+
+def behaviour_rows(world, B=BEHAVIOUR_B, steps=BEHAVIOUR_STEPS, seed=7):
+    """policy -> dict of episode statistics (auto-reset on): zero actions, seeded uniform random actions, the planner"""
+    rows = {}
+    for name in ("zero", "random", "planner"):
+        cfg = EnvConfig(seed=seed, distance_cutoff=0.25, max_environment_steps=200)
+        env = BatchedWaypointEnv(cfg, world, num_envs=B, device=DEV, obs_mode="state", planner=Planner())
+        env.reset()
+        gen = torch.Generator(device=DEV).manual_seed(seed)
+        lo = torch.tensor(env.action_space.low, device=DEV)
+        hi = torch.tensor(env.action_space.high, device=DEV)
+        acc = torch.zeros(7, dtype=torch.float64, device=DEV)   # episodes, infraction ends, offroad, collision, red light, waypoints, length
+        for _ in range(steps):
+            if name == "zero":
+                a = torch.zeros(B, 2, device=DEV)
+            elif name == "random":
+                a = lo + (hi - lo) * torch.rand(B, 2, device=DEV, generator=gen)
+            else:
+                a = env.plan_actions()
+            env.step(a)
+            bits = env.state["done_bits"].to(torch.int64)
+            done = ((bits & 3) != 0).double()
+            acc += torch.stack([done.sum(), (done * (bits & 1)).sum(), (done * ((bits >> 2) & 1)).sum(), (done * ((bits >> 3) & 1)).sum(),
+                                (done * ((bits >> 4) & 1)).sum(), (done * env.state["info_reached"].double()).sum(),
+                                (done * env.state["ep_final_len"].double()).sum()])
+        n, inf, off, col, red, wps, ln = acc.tolist()
+        n = max(n, 1.0)
+        rows[name] = dict(episodes=int(acc[0].item()), infraction_ends=int(acc[1].item()), waypoints_per_episode=wps / n, infraction_rate=inf / n, offroad_rate=off / n,
+                          collision_rate=col / n, red_light_rate=red / n, success_rate=1.0 - inf / n, episode_length=ln / n)
+    return rows
+
+
+def format_rows(rows):
+    keys = ("episodes", "infraction_ends", "waypoints_per_episode", "offroad_rate", "collision_rate", "red_light_rate", "success_rate", "episode_length")
+    out = [f"{'policy':>8} " + " ".join(f"{k:>21}" for k in keys)]
+    for name, r in rows.items():
+        out.append(f"{name:>8} " + " ".join(f"{r[k]:>21.3f}" if isinstance(r[k], float) else f"{r[k]:>21d}" for k in keys))
+    return "\n".join(out)
+
+
+def test_the_planner_outdrives_the_zero_and_the_random_policy(small_world):
+    rows = behaviour_rows(small_world)
+    print("\n" + format_rows(rows))
+    z, r, p = rows["zero"], rows["random"], rows["planner"]
+    assert z["infraction_rate"] >= 0.5                               # the comparison means something on this world
+    assert p["episodes"] > 0
+    assert p["waypoints_per_episode"] > z["waypoints_per_episode"] and p["waypoints_per_episode"] > r["waypoints_per_episode"]
+    assert p["infraction_ends"] < z["infraction_ends"] and p["infraction_ends"] < r["infraction_ends"]
+    assert p["infraction_rate"] < z["infraction_rate"] and p["infraction_rate"] < r["infraction_rate"]

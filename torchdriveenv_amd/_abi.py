@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-TDE_ABI_VERSION = 12
+TDE_ABI_VERSION = 13
 TDE_MAX_AGENTS = 128
 
 F_NPC = 1 << 0
@@ -146,6 +146,17 @@ class TdeVectorObs(C.Structure):
 
 VO_MAX_NBR, VO_MAX_RAYS, VO_MAX_SAMPLES = 16, 64, 1024
 VO_EGO, VO_NBR, VO_RAY = 10, 9, 3
+
+class TdePlanner(C.Structure):
+    """tde_planner (tde_abi.h): the parameters of tde_plan_action, the lattice tables inline"""
+    _fields_ = [("accel", C.c_float * 64), ("steer", C.c_float * 64), ("n_a", C.c_int32), ("n_s", C.c_int32), ("horizon", C.c_int32),
+                ("v_target", C.c_float), ("margin", C.c_float), ("w_progress", C.c_float), ("w_speed", C.c_float), ("w_steer", C.c_float)]
+
+
+PLAN_MAX_CAND, PLAN_MAX_H = 64, 32
+PLAN_FAIL_UNIT, PLAN_RUN_MAX, PLAN_RUN_BIAS = 2048.0, 1024.0, 512.0
+PLAN_DIAG_DTYPE = np.dtype([("winner", "i4"), ("fail_step", "i4"), ("cost", "f4"), ("n_safe", "i4")])
+assert PLAN_DIAG_DTYPE.itemsize == 16
 
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7

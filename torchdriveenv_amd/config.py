@@ -232,3 +232,67 @@ def check_vector_obs(vo):
     if not (1 <= q <= 1024) or q != np.rint(q):
         raise ValueError("vector_obs: ray_range / ray_step must be an integer in [1, 1024]")
     return vo
+
+
+@dataclass
+class Planner:
+    """The sampling planner of BatchedWaypointEnv.plan_actions() (tde_plan_action, include/tde_hip.h): every pair of an acceleration
+    and a steering value is rolled forward `horizon` steps through the step's own kinematics; a candidate that leaves the road,
+    overlaps the predicted box of another agent (constant velocity, inflated by `margin`) or crosses a red stop line fails at that
+    step; the cheapest candidate wins, any earlier failure costing more than any later one.  No reference counterpart.
+
+      accelerations  candidate accelerations, each in [-1, 1] (the action box); must contain 0 exactly
+      steerings      candidate steering values, each in [-0.3, 0.3]; must contain 0 exactly; len(accelerations) * len(steerings) <= 64
+      horizon        steps rolled forward, 1 .. 32
+      v_target       speed tracked while a target waypoint exists [m/s] (a finished route plans a stop)
+      margin         inflation of the other agents' half extents [m]
+      w_progress, w_speed, w_steer   cost weights: per metre gained towards the target waypoint, per (m/s)^2 of speed error summed over
+                     the steps, per rad^2 of steering"""
+    accelerations: tuple = (-1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0)
+    steerings: tuple = (-0.3, -0.2, -0.1, 0.0, 0.1, 0.2, 0.3)
+    horizon: int = 32
+    v_target: float = 4.0
+    margin: float = 0.3
+    w_progress: float = 1.0
+    w_speed: float = 0.2
+    w_steer: float = 1.0
+
+    @property
+    def n_candidates(self):
+        return len(self.accelerations) * len(self.steerings)
+
+    def tables(self):
+        """(float32 [n_a], float32 [n_s]): the lattice; candidate i = ia * n_s + is"""
+        import numpy as np
+
+        return np.asarray(self.accelerations, np.float32).reshape(-1), np.asarray(self.steerings, np.float32).reshape(-1)
+
+    def candidate(self, i):
+        """(acceleration, steering) of candidate i as float32"""
+        a, s = self.tables()
+        return a[int(i) // len(s)], s[int(i) % len(s)]
+
+
+def check_planner(pl):
+    """validate a Planner (tde_plan_action rejects the same); returns it (a dict is accepted as Planner(**dict))"""
+    import numpy as np
+
+    if isinstance(pl, dict):
+        pl = Planner(**pl)
+    if not isinstance(pl, Planner):
+        raise TypeError("planner must be a Planner (or a dict of its fields)")
+    a, s = pl.tables()
+    if len(a) < 1 or len(s) < 1 or len(a) * len(s) > 64:
+        raise ValueError("planner: accelerations and steerings must be non-empty with at most 64 candidates in all")
+    if not (np.isfinite(a).all() and (np.abs(a) <= np.float32(1.0)).all()):
+        raise ValueError("planner: accelerations must lie in [-1, 1]")
+    if not (np.isfinite(s).all() and (np.abs(s) <= np.float32(0.3)).all()):
+        raise ValueError("planner: steerings must lie in [-0.3, 0.3]")
+    if not (a == 0).any() or not (s == 0).any():
+        raise ValueError("planner: accelerations and steerings must each contain 0 exactly")
+    if int(pl.horizon) != pl.horizon or not (1 <= int(pl.horizon) <= 32):
+        raise ValueError("planner: horizon must be an integer in [1, 32]")
+    vals = [np.float32(v) for v in (pl.v_target, pl.margin, pl.w_progress, pl.w_speed, pl.w_steer)]
+    if not all(np.isfinite(v) and v >= 0 for v in vals):
+        raise ValueError("planner: v_target, margin and the weights must be finite and >= 0")
+    return pl

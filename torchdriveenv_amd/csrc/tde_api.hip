@@ -507,6 +507,34 @@ int tde_vector_obs(const tde_config *cfg, const tde_world *world, const tde_stat
     return tde_host::launch_vector_obs(cfg, world, st, vo, only, out, stream);
 }
 
+int tde_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const uint8_t *only,
+                    float *action, tde_plan_diag *diag, void *stream)
+{
+    int rc = check_env_args("tde_plan_action", cfg, world, st);
+    if (rc) return rc;
+    if (!pl || !action) return bad("tde_plan_action: NULL argument");
+    if (pl->n_a < 1 || pl->n_s < 1 || pl->n_a > TDE_PLAN_MAX_CAND || pl->n_s > TDE_PLAN_MAX_CAND || pl->n_a * pl->n_s > TDE_PLAN_MAX_CAND)
+        return bad("tde_plan_action: n_a and n_s must be >= 1 with n_a * n_s <= TDE_PLAN_MAX_CAND");
+    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return bad("tde_plan_action: horizon must be in [1, TDE_PLAN_MAX_H]");
+    for (int i = 0; i < pl->n_a; ++i)
+        if (!(pl->accel[i] >= -1.0f && pl->accel[i] <= 1.0f)) return bad("tde_plan_action: an acceleration outside [-1, 1]");
+    for (int i = 0; i < pl->n_s; ++i)
+        if (!(pl->steer[i] >= -0.3f && pl->steer[i] <= 0.3f)) return bad("tde_plan_action: a steering outside [-0.3, 0.3]");
+    const float nn[5] = {pl->v_target, pl->margin, pl->w_progress, pl->w_speed, pl->w_steer};
+    for (int i = 0; i < 5; ++i)
+        if (!(nn[i] >= 0.0f && nn[i] <= FLT_MAX))
+            return bad("tde_plan_action: v_target, margin and the weights must be finite and >= 0");
+    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_plan_action: config.dt must be finite and > 0");
+    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->present || !st->scn || !st->steps ||
+        !st->target_idx || !world->maps || !world->scn || !world->wp_xy || !world->cell_word || !world->cell_cls2 || !world->cell_coarse ||
+        !world->cell_tri)
+        return bad("tde_plan_action: a required state / world pointer is NULL");
+    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
+        return bad("tde_plan_action: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if (st->B <= 0) return 0;
+    return tde_host::launch_plan_action(cfg, world, st, pl, only, action, diag, stream);
+}
+
 int tde_env_reset_render(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask,
                          const tde_render *rd, void *stream)
 {

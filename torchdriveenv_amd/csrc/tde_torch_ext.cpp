@@ -327,6 +327,35 @@ class EnvHandle {
                  "tde_vector_obs");
     }
 
+    // tde_plan_action: float32 [B, 2] ego actions of the envs in `only` (all without it); diag: optional int32 [B, 4] = tde_plan_diag rows
+    void plan_action(const at::Tensor &out, const std::vector<double> &accel, const std::vector<double> &steer, int64_t horizon,
+                     double v_target, double margin, double w_progress, double w_speed, double w_steer,
+                     const std::optional<at::Tensor> &only, const std::optional<at::Tensor> &diag, int64_t flags)
+    {
+        TORCH_CHECK(!accel.empty() && !steer.empty() && accel.size() * steer.size() <= (size_t)TDE_PLAN_MAX_CAND,
+                    "plan_action: accel x steer must hold 1 .. TDE_PLAN_MAX_CAND candidates");
+        tde_planner pl;
+        std::memset(&pl, 0, sizeof(pl));
+        for (size_t i = 0; i < accel.size(); ++i) pl.accel[i] = (float)accel[i];
+        for (size_t i = 0; i < steer.size(); ++i) pl.steer[i] = (float)steer[i];
+        pl.n_a = (int32_t)accel.size();
+        pl.n_s = (int32_t)steer.size();
+        pl.horizon = (int32_t)horizon;
+        pl.v_target = (float)v_target;
+        pl.margin = (float)margin;
+        pl.w_progress = (float)w_progress;
+        pl.w_speed = (float)w_speed;
+        pl.w_steer = (float)w_steer;
+        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, (int64_t)state_.B * 2, "out", dev_)));
+        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        static_assert(sizeof(tde_plan_diag) == 4 * sizeof(int32_t), "tde_plan_diag rows are four 32-bit words");
+        tde_plan_diag *d = diag ? static_cast<tde_plan_diag *>(const_cast<void *>(dev_ptr(*diag, at::kInt, (int64_t)state_.B * 4, "diag", dev_))) : nullptr;
+        cfg_.flags = static_cast<uint32_t>(flags);
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_plan_action(&cfg_, &world_, &state_, &pl, m, p, d, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                 "tde_plan_action");
+    }
+
     // tde_ego_infractions: float32 [B, 4] = the ego's (offroad, collision, overlap count, 0) magnitudes of the state as it is (gym_env.py:427-428)
     void ego_infractions(const at::Tensor &out, int64_t flags)
     {
@@ -496,6 +525,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         .def("near_field_spawn", &EnvHandle::near_field_spawn, py::arg("nf"), py::arg("mask"), py::arg("flags"))
         .def("vector_obs", &EnvHandle::vector_obs, py::arg("out"), py::arg("ray_dir"), py::arg("k_nbr"), py::arg("n_rays"),
              py::arg("nbr_radius"), py::arg("ray_range"), py::arg("ray_step"), py::arg("only"), py::arg("flags"))
+        .def("plan_action", &EnvHandle::plan_action, py::arg("out"), py::arg("accel"), py::arg("steer"), py::arg("horizon"),
+             py::arg("v_target"), py::arg("margin"), py::arg("w_progress"), py::arg("w_speed"), py::arg("w_steer"), py::arg("only"),
+             py::arg("diag"), py::arg("flags"))
         .def_property_readonly("flags", &EnvHandle::flags)
         .def_property_readonly("num_envs", &EnvHandle::num_envs)
         .def_property_readonly("agents_per_env", &EnvHandle::agents_per_env);

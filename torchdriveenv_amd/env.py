@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _abi, ops
-from .config import (EnvConfig, NearField, VectorObs, WaypointSuite, check_near_field, check_vector_obs, render_flags, to_tde_config,
+from .config import (EnvConfig, NearField, Planner, VectorObs, WaypointSuite, check_near_field, check_planner, check_vector_obs, render_flags, to_tde_config,
                      validate)
 from .state import EnvState
 from .video import VideoRecorder
@@ -540,7 +540,7 @@ class BatchedWaypointEnv:
     def __init__(self, cfg: EnvConfig, data, num_envs, agents_per_env=16, device=None, obs_mode="birdview",
                  frame_stack=1, auto_reset=True, with_info=True, background=None, env_base=0, binding="ext",
                  info_magnitudes=True, road_meshes=None, near_range=None, traffic_lights=None, start_headings=None, light_radius=150.0,
-                 heading_samples=16, near_field=None, vector_obs=None):
+                 heading_samples=16, near_field=None, vector_obs=None, planner=None):
         """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp), "ctypes" = through
         the ctypes binding of the same C-ABI (ops.py); both call the very same entry points of libtde_hip.so.
         info_magnitudes (default): info["offroad"] / info["collision"] hold the MAGNITUDES the reference reports there (ref
@@ -559,8 +559,10 @@ class BatchedWaypointEnv:
         (re)spawn - reset(), auto-reset in step(), the VecEnv's re-spawn - then runs the spawner before the state is observed;
         rollout() and the multi-stream step raise.  None (default): no near field, every path as it was.
         vector_obs: the config.VectorObs (or a dict of its fields) of obs_mode="vector" (None: VectorObs()); the observation is
-        float32 [B, vector_obs.dim] (tde_vector_obs), taken after every reset, step and re-spawn (after the near-field spawner)."""
+        float32 [B, vector_obs.dim] (tde_vector_obs), taken after every reset, step and re-spawn (after the near-field spawner).
+        planner: the config.Planner (or a dict of its fields) of plan_actions() (None: Planner())."""
         validate(cfg)
+        self.planner = check_planner(planner if planner is not None else Planner())
         if near_field is not None and not isinstance(near_field, NearFieldTable):
             near_field = check_near_field(near_field, cfg)
         if near_field is not None and cfg.ego_only:
@@ -638,6 +640,7 @@ class BatchedWaypointEnv:
         self.observation_space = (_box(0, 255, (3 * self.frame_stack, self._res, self._res), np.uint8) if obs_mode == "birdview" else
                                   _box(-np.inf, np.inf, (self.vector_obs.dim if obs_mode == "vector" else 8,), np.float32))
         self._vobs = self._ray_dir = None
+        self._plan_out = self._plan_diag = self._plan_struct = None
         if obs_mode == "vector":
             self._vobs = torch.zeros((self.num_envs, self.vector_obs.dim), dtype=torch.float32, device=self.torch_device)
             self._ray_dir = torch.from_numpy(self.vector_obs.ray_directions()).to(self.torch_device)
@@ -831,6 +834,33 @@ class BatchedWaypointEnv:
         else:
             ops.vector_obs(self.tde_cfg, self.dworld, self.state, vo, self._ray_dir, self._vobs, only)
         return self._vobs
+
+    def plan_actions(self, out=None, only=None, diag=False):
+        """the sampling planner's action for every ego on the state as it is (tde_plan_action with self.planner) -> float32 [B, 2] on
+        the device, usable as step(plan_actions()).  out: a float32 [B, 2] device tensor to write into (default: the env's own
+        buffer, overwritten by the next call); only: uint8 [B] on the device, the other rows are left as they are; diag=True: returns
+        (actions, int32 [B, 4] rows of winner, fail_step, the cost's float32 bits, n_safe - n_safe == 0: no candidate is safe)."""
+        if out is None:
+            if self._plan_out is None:
+                self._plan_out = torch.zeros((self.num_envs, 2), dtype=torch.float32, device=self.torch_device)
+            out = self._plan_out
+        d = None
+        if diag:
+            if self._plan_diag is None:
+                self._plan_diag = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.torch_device)
+            d = self._plan_diag
+        if only is not None:
+            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
+        pl = self.planner
+        if self._h is not None:
+            self._h.plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings], int(pl.horizon),
+                                float(pl.v_target), float(pl.margin), float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, d,
+                                int(self.tde_cfg.flags))
+        else:
+            if self._plan_struct is None:
+                self._plan_struct = ops.planner_struct(pl)
+            ops.plan_action(self.tde_cfg, self.dworld, self.state, self._plan_struct, out, only, d)
+        return (out, d) if diag else out
 
     def _render1(self, out, only=None):
         """single-frame raster of every (or the masked) view into `out`"""
@@ -1069,6 +1099,12 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
         out = buf.numpy()
         return out.copy() if self.copy_obs else out
 
+    def plan_actions(self, only=None, diag=False):
+        """the sampling planner's actions on the current state (BatchedWaypointEnv.plan_actions) as a float32 [B, 2] numpy array, what
+        step() takes; diag=True: (actions, int32 [B, 4] diag rows)"""
+        r = self.env.plan_actions(only=only, diag=diag)
+        return (r[0].cpu().numpy(), r[1].cpu().numpy()) if diag else r.cpu().numpy()
+
     def step_async(self, actions):
         self._pending = np.asarray(actions, dtype=np.float32)
 
@@ -1219,12 +1255,12 @@ class WaypointSuiteEnv(_GymEnvBase):
     metadata = {"render_modes": ["video", "rgb_array"], "render_fps": 10}
 
     def __init__(self, cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None,
-                 video_camera="map", background=None, near_field=None):
+                 video_camera="map", background=None, near_field=None, planner=None):
         """render_mode="video": every reset() and step() records a video_res x video_res frame at video_fov metres across (the
         reference's BirdviewRecordingWrapper, gym_env.py:295-297) from `video_camera` ("map": the centre of the map, heading pi/2;
         "ego"; or (x, y, psi)); get_birdviews() returns them, close() writes video_filename (video.save_video).
         background / near_field: the background-traffic files and the near-field traffic of every reset, as BatchedWaypointEnv
-        takes them (the reference's background mode: gym_env.py:200-238)."""
+        takes them (the reference's background mode: gym_env.py:200-238).  planner: the config.Planner of expert_action()."""
         self.config = cfg
         if cfg.render_mode == "video":               # the batched env renders rgb_array; the frames are recorded here
             cfg = dataclasses.replace(cfg, render_mode="rgb_array")
@@ -1233,7 +1269,7 @@ class WaypointSuiteEnv(_GymEnvBase):
         self._env = BatchedWaypointEnv(cfg, data, num_envs=1, agents_per_env=agents_per_env, obs_mode="birdview",
                                        frame_stack=1, auto_reset=False, info_magnitudes=True, road_meshes=road_meshes,
                                        traffic_lights=traffic_lights, start_headings=start_headings, background=background,
-                                       near_field=near_field)
+                                       near_field=near_field, planner=planner)
         self.torch_device = self._env.torch_device
         self.render_mode = self.config.render_mode
         self._video = None
@@ -1324,6 +1360,11 @@ class WaypointSuiteEnv(_GymEnvBase):
                         psi_reward=float(inf[2]), dist_reward=float(inf[3]))
         return (self._obs_pin.numpy().reshape(1, 1, 3, 64, 64).copy(), float(out["reward"][0]), bool(out["terminated"][0]), trunc, info)
 
+    def expert_action(self):
+        """the sampling planner's action on the current state (BatchedWaypointEnv.plan_actions): a float32 (2,) array, what
+        SingleAgentWrapper.step takes"""
+        return self._env.plan_actions().cpu().numpy().reshape(2).copy()
+
     def render(self):                                               # ref gym_env.py:152-157
         if self.render_mode == "rgb_array":
             return self._env.render()[0]
@@ -1372,6 +1413,9 @@ class SingleAgentWrapper(_GymWrapperBase):
             return {k: self.transform_in(v) for k, v in x.items()}
         return x
 
+    def expert_action(self):
+        return self.env.expert_action()
+
     def render(self, *args, **kwargs):
         return self.env.render(*args, **kwargs)
 
@@ -1380,7 +1424,7 @@ class SingleAgentWrapper(_GymWrapperBase):
 
 
 def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None, video_camera="map",
-         background=None, near_field=None):
+         background=None, near_field=None, planner=None):
     """what gym.make('torchdriveenv-v0', args={'cfg': cfg, 'data': data}) returns in the reference (ref __init__.py:10).
     `road_meshes`, `traffic_lights`, `start_headings`: what the reference takes from torchdrivesim's map config of the location
     (`find_map_config`: road mesh ref gym_env.py:184, stop lines + light controller :181-189, lanelet directions :359) - see
@@ -1389,7 +1433,8 @@ def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_light
     `near_field`: a config.NearField - traffic around the ego at every reset (ref gym_env.py:232-238; BatchedWaypointEnv)"""
     return SingleAgentWrapper(WaypointSuiteEnv(cfg=cfg, data=data, agents_per_env=agents_per_env, road_meshes=road_meshes,
                                                traffic_lights=traffic_lights, start_headings=start_headings,
-                                               video_camera=video_camera, background=background, near_field=near_field))
+                                               video_camera=video_camera, background=background, near_field=near_field,
+                                               planner=planner))
 
 
 if gym is not None:  # pragma: no cover

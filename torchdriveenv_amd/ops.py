@@ -253,6 +253,41 @@ def vector_obs(cfg, dworld, state, vo, ray_dir=None, out=None, only=None):
     return out
 
 
+def planner_struct(pl):
+    """the tde_planner (host struct, lattice inline) of a config.Planner"""
+    from .config import check_planner
+
+    pl = check_planner(pl)
+    a, s = pl.tables()
+    t = _abi.TdePlanner()
+    for i, v in enumerate(a):
+        t.accel[i] = float(v)
+    for i, v in enumerate(s):
+        t.steer[i] = float(v)
+    t.n_a, t.n_s, t.horizon = len(a), len(s), int(pl.horizon)
+    t.v_target, t.margin = float(pl.v_target), float(pl.margin)
+    t.w_progress, t.w_speed, t.w_steer = float(pl.w_progress), float(pl.w_speed), float(pl.w_steer)
+    return t
+
+
+def plan_action(cfg, dworld, state, planner, out=None, only=None, diag=None):
+    """tde_plan_action: the sampling planner's ego action of every env (or of those in `only`, uint8 [B] on the device; the other
+    rows of `out` / `diag` are left as they are) -> float32 [B, 2] on the device.  planner: config.Planner (or the tde_planner
+    planner_struct made of one); diag: optional int32 [B, 4] device tensor receiving tde_plan_diag rows (winner, fail_step, the
+    cost's float32 bits, n_safe).  Asynchronous."""
+    L = _lib.load()
+    dev = torch.device(state.device)
+    ps = planner if isinstance(planner, _abi.TdePlanner) else planner_struct(planner)
+    if out is None:
+        out = torch.empty((state.B, 2), dtype=torch.float32, device=dev)
+    po = _chk(out, torch.float32, state.B * 2, "out", dev)
+    pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
+    pd = _chk(diag, torch.int32, state.B * 4, "diag", dev, optional=True)
+    _lib.check(_call(dev, L.tde_plan_action, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps), pm, po, pd,
+                     _lib.current_stream(dev)), "tde_plan_action")
+    return out
+
+
 def render_ego(cfg, dworld, state, H=64, W=64, fov=35.0, n_stack=1, out=None, layers=None, phase=0, flags=0,
                fresh=None, only=None):
     """render_egocentric() of every env's ego -> uint8 [B, 3*n_stack, H, W] on device (ref gym_env.py:122-124).

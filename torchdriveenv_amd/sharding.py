@@ -74,6 +74,9 @@ def _shard_worker(rank, n_shards, device, cfg, world, total, kw, conn, shm):
                 done_all[lo:hi] = done
                 cols = {k: np.asarray(v) for k, v in infos.columns.items()}
                 conn.send(("ok", (cols, {lo + i: ex for i, ex in infos.terminal.items()})))
+            elif cmd == "plan":
+                act, dg = venv.plan_actions(diag=True)
+                conn.send(("ok", (act, dg)))
             elif cmd == "state":
                 conn.send(("ok", {k: v.cpu().numpy() for k, v in env.state.arrays.items() if v is not None}))
             elif cmd == "close":
@@ -243,6 +246,14 @@ class ShardedBatchedEnv:
         # with copy_obs, the copy of the gathered observations
         self.last_step_timing = {"step_s": t1 - t0, "gather_s": t2 - t1, "obs_bytes": int(self._shm["obs"].numel() * self._shm["obs"].element_size())}
         return out
+
+    def plan_actions(self, diag=False):
+        """the sampling planner's actions of every shard on its current state (BatchedWaypointEnv.plan_actions; planner= is an env
+        keyword) in global env order: float32 [B, 2], what step() takes; diag=True: (actions, int32 [B, 4] diag rows)"""
+        np = self._np
+        parts = self._all("plan")
+        act = np.concatenate([p[0] for p in parts])
+        return (act, np.concatenate([p[1] for p in parts])) if diag else act
 
     def gather_state(self):
         """every shard's state arrays concatenated in global env order (tests / checkpoints)"""
