@@ -12,18 +12,20 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from torchdriveenv_amd.config import EnvConfig, Planner
+from torchdriveenv_amd.config import EnvConfig, Planner, PlanRefine
 from torchdriveenv_amd.env import BatchedWaypointEnv
 from torchdriveenv_amd.synth import synthetic_world
 
 
 def main():
-    num_envs = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 400
-    save = sys.argv[3] if len(sys.argv) > 3 else None
+    args = [a for a in sys.argv[1:] if a != "--refine"]
+    refine = PlanRefine() if "--refine" in sys.argv[1:] else None   # --refine: brake tail + knot refinement (tde_score_plans)
+    num_envs = int(args[0]) if len(args) > 0 else 1024
+    steps = int(args[1]) if len(args) > 1 else 400
+    save = args[2] if len(args) > 2 else None
     cfg = EnvConfig(seed=0, distance_cutoff=0.25)
     world = synthetic_world(n_scn=64, A=16, seed=0, n_maps=4)               # or a WaypointSuite from the loaders
-    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, obs_mode="vector", planner=Planner())
+    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, obs_mode="vector", planner=Planner(), plan_refine=refine)
     obs = env.reset()
     stats = torch.zeros(6, dtype=torch.float64, device=obs.device)   # episodes, infraction ends, offroad, collision, red light, waypoints
     pairs = []
@@ -37,7 +39,7 @@ def main():
         stats += torch.stack([done.sum(), (done * (bits & 1)).sum(), (done * ((bits >> 2) & 1)).sum(), (done * ((bits >> 3) & 1)).sum(),
                               (done * ((bits >> 4) & 1)).sum(), (done * env.state["info_reached"].double()).sum()])
     n, inf, off, col, red, wps = stats.tolist()
-    print(f"{num_envs} envs x {steps} steps under the planner: {int(n)} episodes")
+    print(f"{num_envs} envs x {steps} steps under the {'refined ' if refine else ''}planner: {int(n)} episodes")
     if n:
         print(f"success {1 - inf / n:.1%}, offroad {off / n:.1%}, collision {col / n:.1%}, red light {red / n:.1%}, "
               f"{wps / n:.2f} waypoints per episode")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TDE_ABI_VERSION 13
+#define TDE_ABI_VERSION 14
 #define TDE_MAX_AGENTS 128
 
 /* feature bits of tde_config.flags */
@@ -497,6 +497,22 @@ typedef struct tde_plan_diag {  /* 16 bytes per env */
     float cost;                 /* its cost */
     int32_t n_safe;             /* candidates with f == H + 1; 0 = "no safe plan" (the winner is then the one that fails last) */
 } tde_plan_diag;
+
+/* (ABI 14) A set of action sequences to judge (tde_score_plans, include/tde_hip.h): N sequences per env, each K knots of
+ * (acceleration, steering), knot k held for knot_len steps (the last one for as long as the horizon lasts), then `tail` steps of
+ * full braking.  A HOST struct; `seq` is DEVICE memory.  tde_plan_diag rows written by tde_score_plans count their fail_step to
+ * H + tail + 1 and their winner over the N sequences. */
+#define TDE_PLAN_MAX_SET  1024  /* N in [1, TDE_PLAN_MAX_SET]: one lane per sequence, at most 16 wavefronts per env */
+#define TDE_PLAN_MAX_TAIL 64    /* tail in [0, TDE_PLAN_MAX_TAIL] */
+#define TDE_PLAN_BOX_ACCEL 1.0f /* the action box (gym_env.py:83-84): |acceleration| <= 1 ... */
+#define TDE_PLAN_BOX_STEER 0.3f /* ... and |steering| <= 0.3; knots are clamped into it */
+typedef struct tde_plan_set {
+    const float *seq;           /* [B][N][K][2] float32 (acceleration, steering) knots, contiguous */
+    int32_t N;                  /* sequences per env */
+    int32_t K;                  /* knots per sequence, in [1, TDE_PLAN_MAX_H] */
+    int32_t knot_len;           /* steps a knot holds, >= 1 */
+    int32_t tail;               /* brake-tail steps after the horizon */
+} tde_plan_set;
 
 #ifdef __cplusplus
 }

@@ -273,6 +273,41 @@ TDE_API int tde_vector_obs(const tde_config *cfg, const tde_world *world, const 
 TDE_API int tde_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_planner *plan,
                             const uint8_t *only, float *action, tde_plan_diag *diag, void *stream);
 
+/* (ABI 14) Judge caller-given action sequences: for every env with only[e] != 0 (uint8 [B]; NULL: all envs) and every sequence n
+ * in [0, set.N): cost[e][n] and fail_step[e][n]; with action / diag != NULL also the winner's first action and a diag row.  Rows of
+ * every output with only[e] == 0 are not written.  No reference counterpart.  set = tde_plan_set (tde_abi.h; set.seq on the device,
+ * [B][N][K][2] float32); plan supplies H = plan.horizon, margin, v_target and the three weights - its lattice (accel, steer, n_a,
+ * n_s) is not read.  T = set.tail, L = set.knot_len, K = set.K.  Everything not restated here is tde_plan_action's, expression for
+ * expression (env quantities, Others, the three Failure predicates, the Cost walk, the ordered key); tests/plan_set_ref.py restates
+ * this in numpy.
+ *   Knots       step h in 1..H uses knot k_h = min((h - 1) / L, K - 1) of sequence n: a = fminf(fmaxf(seq[e][n][k_h][0], -1.0f), 1.0f),
+ *               d = fminf(fmaxf(seq[e][n][k_h][1], -0.3f), 0.3f) (TDE_PLAN_BOX_ACCEL / _STEER; a NaN becomes the lower bound; the
+ *               kernel cannot reject device values).
+ *   Horizon     for h = 1..H: tde_plan_action's Trajectory step with this step's (a, d) - a_h = 0.0f when v + a * dt < 0.0f, else a -
+ *               and its Failure predicates on s_h (red mask of state.steps[e] + h, the others' boxes at step h); at every step
+ *               h < f its Cost walk (gain, sv, the waypoint advance).
+ *   Brake tail  a sequence with no failure in 1..H goes on for t = 1..T with a = -1.0f and the d of step H.  At the first t with
+ *               v + a * dt < 0.0f it ends, safe (it stands as far as this action box can stop it).  Otherwise bicycle(x, y, psi, v,
+ *               inv_lr, a, d, dt) and the three Failure predicates at step H + t (red mask of state.steps[e] + H + t, the others'
+ *               boxes (float)(H + t) steps ahead); a failure gives f = H + t.  The tail adds nothing to gain or sv.
+ *               f = H + T + 1 when nothing failed.
+ *   Cost        dm = the largest d * d (fmaxf, from 0.0f) over the steps h in 1..min(f, H): d * d for a constant sequence;
+ *               run = (w_speed * sv + w_steer * dm) - w_progress * gain;
+ *               cost = (float)(H + T + 1 - f) * TDE_PLAN_FAIL_UNIT + fminf(fmaxf(run + TDE_PLAN_RUN_BIAS, 0.0f), TDE_PLAN_RUN_MAX): a
+ *               sequence that cannot be brought to rest safely costs more than any that can and less than any that fails inside
+ *               the horizon.  With T = 0 and K = 1 this is tde_plan_action's cost of the candidate (a, d).
+ *   Winner      the least (ordered cost bits, n) over the N sequences; action[e] = (a_1 of the winner - knot 0's clamped a after the
+ *               no-reverse rule at the state as it is -, knot 0's clamped d); diag[e] = (n of the winner, its f, its cost, the
+ *               number of sequences with f == H + T + 1).
+ * One lane per sequence: N <= 64 one wavefront per env, four envs per workgroup; N > 64 one workgroup of ceil(N / 64) wavefronts per
+ * env.  Reads state only.  Rejected: NULL cfg / world / state / plan / set / set.seq / cost / fail_step, N outside [1,
+ * TDE_PLAN_MAX_SET], K outside [1, TDE_PLAN_MAX_H], knot_len < 1, tail outside [0, TDE_PLAN_MAX_TAIL], horizon outside [1,
+ * TDE_PLAN_MAX_H], v_target / margin / a weight negative or not finite, config.dt not finite or <= 0.  No allocation, no
+ * synchronisation (graph-capturable). */
+TDE_API int tde_score_plans(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_planner *plan,
+                            const tde_plan_set *set, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
+                            tde_plan_diag *diag, void *stream);
+
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 
 /* Offroad grid index of ONE drivable mesh - what the simulator prepares once per map from the road mesh it is constructed

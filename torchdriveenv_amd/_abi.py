@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-TDE_ABI_VERSION = 13
+TDE_ABI_VERSION = 14
 TDE_MAX_AGENTS = 128
 
 F_NPC = 1 << 0
@@ -157,6 +157,15 @@ PLAN_MAX_CAND, PLAN_MAX_H = 64, 32
 PLAN_FAIL_UNIT, PLAN_RUN_MAX, PLAN_RUN_BIAS = 2048.0, 1024.0, 512.0
 PLAN_DIAG_DTYPE = np.dtype([("winner", "i4"), ("fail_step", "i4"), ("cost", "f4"), ("n_safe", "i4")])
 assert PLAN_DIAG_DTYPE.itemsize == 16
+
+
+class TdePlanSet(C.Structure):
+    """tde_plan_set (tde_abi.h): the sequences tde_score_plans judges; seq is a device address"""
+    _fields_ = [("seq", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32), ("knot_len", C.c_int32), ("tail", C.c_int32)]
+
+
+PLAN_MAX_SET, PLAN_MAX_TAIL = 1024, 64
+PLAN_BOX_ACCEL, PLAN_BOX_STEER = 1.0, 0.3
 
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7

@@ -107,6 +107,9 @@ int launch_vector_obs(const tde_config *cfg, const tde_world *world, const tde_s
 // tde_planner.hip: plan_action_kernel (tde_plan_action; arguments checked by the caller)
 int launch_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const uint8_t *only,
                        float *action, tde_plan_diag *diag, void *stream);
+// tde_plan_set.hip: score_plans_kernel (tde_score_plans; arguments checked by the caller)
+int launch_score_plans(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
+                       const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream);
 
 }  // namespace tde_host
 

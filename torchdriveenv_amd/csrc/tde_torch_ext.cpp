@@ -356,6 +356,42 @@ class EnvHandle {
                  "tde_plan_action");
     }
 
+    // tde_score_plans: cost float32 [B, N] and fail_step int32 [B, N] of the N sequences of seq (float32 [B, N, K, 2], contiguous); action
+    // float32 [B, 2] / diag int32 [B, 4]: optional, the winner's first action and its tde_plan_diag row
+    void score_plans(const at::Tensor &seq, int64_t knot_len, int64_t tail, const at::Tensor &cost, const at::Tensor &fail_step,
+                     int64_t horizon, double v_target, double margin, double w_progress, double w_speed, double w_steer,
+                     const std::optional<at::Tensor> &only, const std::optional<at::Tensor> &action,
+                     const std::optional<at::Tensor> &diag, int64_t flags)
+    {
+        TORCH_CHECK(seq.dim() == 4 && seq.size(0) == state_.B && seq.size(3) == 2, "score_plans: seq must be [B, N, K, 2]");
+        TORCH_CHECK(seq.is_contiguous(), "score_plans: seq must be contiguous (no copy of it is made)");
+        const int64_t N = seq.size(1), K = seq.size(2);
+        tde_planner pl;
+        std::memset(&pl, 0, sizeof(pl));
+        pl.horizon = (int32_t)horizon;
+        pl.v_target = (float)v_target;
+        pl.margin = (float)margin;
+        pl.w_progress = (float)w_progress;
+        pl.w_speed = (float)w_speed;
+        pl.w_steer = (float)w_steer;
+        tde_plan_set ps;
+        ps.seq = static_cast<const float *>(dev_ptr(seq, at::kFloat, (int64_t)state_.B * N * K * 2, "seq", dev_));
+        ps.N = (int32_t)N;
+        ps.K = (int32_t)K;
+        ps.knot_len = (int32_t)knot_len;
+        ps.tail = (int32_t)tail;
+        float *pc = static_cast<float *>(const_cast<void *>(dev_ptr(cost, at::kFloat, (int64_t)state_.B * N, "cost", dev_)));
+        int32_t *pf = static_cast<int32_t *>(const_cast<void *>(dev_ptr(fail_step, at::kInt, (int64_t)state_.B * N, "fail_step", dev_)));
+        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        float *pa = action ? static_cast<float *>(const_cast<void *>(dev_ptr(*action, at::kFloat, (int64_t)state_.B * 2, "action", dev_))) : nullptr;
+        tde_plan_diag *d = diag ? static_cast<tde_plan_diag *>(const_cast<void *>(dev_ptr(*diag, at::kInt, (int64_t)state_.B * 4, "diag", dev_))) : nullptr;
+        cfg_.flags = static_cast<uint32_t>(flags);
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_score_plans(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d,
+                                 c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                 "tde_score_plans");
+    }
+
     // tde_ego_infractions: float32 [B, 4] = the ego's (offroad, collision, overlap count, 0) magnitudes of the state as it is (gym_env.py:427-428)
     void ego_infractions(const at::Tensor &out, int64_t flags)
     {
@@ -528,6 +564,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         .def("plan_action", &EnvHandle::plan_action, py::arg("out"), py::arg("accel"), py::arg("steer"), py::arg("horizon"),
              py::arg("v_target"), py::arg("margin"), py::arg("w_progress"), py::arg("w_speed"), py::arg("w_steer"), py::arg("only"),
              py::arg("diag"), py::arg("flags"))
+        .def("score_plans", &EnvHandle::score_plans, py::arg("seq"), py::arg("knot_len"), py::arg("tail"), py::arg("cost"),
+             py::arg("fail_step"), py::arg("horizon"), py::arg("v_target"), py::arg("margin"), py::arg("w_progress"), py::arg("w_speed"),
+             py::arg("w_steer"), py::arg("only"), py::arg("action"), py::arg("diag"), py::arg("flags"))
         .def_property_readonly("flags", &EnvHandle::flags)
         .def_property_readonly("num_envs", &EnvHandle::num_envs)
         .def_property_readonly("agents_per_env", &EnvHandle::agents_per_env);

@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import _abi, ops
-from .config import (EnvConfig, NearField, Planner, VectorObs, WaypointSuite, check_near_field, check_planner, check_vector_obs, render_flags, to_tde_config,
-                     validate)
+from .config import (EnvConfig, NearField, Planner, VectorObs, WaypointSuite, check_near_field, check_plan_refine, check_planner, check_vector_obs,
+                     render_flags, to_tde_config, validate)
 from .state import EnvState
 from .video import VideoRecorder
 from .world import (NearFieldTable, World, assemble_world, build_near_field, check_threshold, corridor_mesh,
@@ -540,7 +540,7 @@ class BatchedWaypointEnv:
     def __init__(self, cfg: EnvConfig, data, num_envs, agents_per_env=16, device=None, obs_mode="birdview",
                  frame_stack=1, auto_reset=True, with_info=True, background=None, env_base=0, binding="ext",
                  info_magnitudes=True, road_meshes=None, near_range=None, traffic_lights=None, start_headings=None, light_radius=150.0,
-                 heading_samples=16, near_field=None, vector_obs=None, planner=None):
+                 heading_samples=16, near_field=None, vector_obs=None, planner=None, plan_refine=None):
         """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp), "ctypes" = through
         the ctypes binding of the same C-ABI (ops.py); both call the very same entry points of libtde_hip.so.
         info_magnitudes (default): info["offroad"] / info["collision"] hold the MAGNITUDES the reference reports there (ref
@@ -560,9 +560,12 @@ class BatchedWaypointEnv:
         rollout() and the multi-stream step raise.  None (default): no near field, every path as it was.
         vector_obs: the config.VectorObs (or a dict of its fields) of obs_mode="vector" (None: VectorObs()); the observation is
         float32 [B, vector_obs.dim] (tde_vector_obs), taken after every reset, step and re-spawn (after the near-field spawner).
-        planner: the config.Planner (or a dict of its fields) of plan_actions() (None: Planner())."""
+        planner: the config.Planner (or a dict of its fields) of plan_actions() (None: Planner()).
+        plan_refine: a config.PlanRefine (or a dict of its fields): plan_actions() then judges the lattice with a brake tail and
+        refines the winner knot by knot through tde_score_plans.  None (default): plan_actions() is tde_plan_action as it was."""
         validate(cfg)
         self.planner = check_planner(planner if planner is not None else Planner())
+        self.plan_refine = check_plan_refine(plan_refine, self.planner) if plan_refine is not None else None
         if near_field is not None and not isinstance(near_field, NearFieldTable):
             near_field = check_near_field(near_field, cfg)
         if near_field is not None and cfg.ego_only:
@@ -640,7 +643,7 @@ class BatchedWaypointEnv:
         self.observation_space = (_box(0, 255, (3 * self.frame_stack, self._res, self._res), np.uint8) if obs_mode == "birdview" else
                                   _box(-np.inf, np.inf, (self.vector_obs.dim if obs_mode == "vector" else 8,), np.float32))
         self._vobs = self._ray_dir = None
-        self._plan_out = self._plan_diag = self._plan_struct = None
+        self._plan_out = self._plan_diag = self._plan_struct = self._refine = None
         if obs_mode == "vector":
             self._vobs = torch.zeros((self.num_envs, self.vector_obs.dim), dtype=torch.float32, device=self.torch_device)
             self._ray_dir = torch.from_numpy(self.vector_obs.ray_directions()).to(self.torch_device)
@@ -852,6 +855,11 @@ class BatchedWaypointEnv:
         if only is not None:
             only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         pl = self.planner
+        if self.plan_refine is not None:
+            if self._plan_diag is None:
+                self._plan_diag = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.torch_device)
+            self._plan_refined(out, only, self._plan_diag)
+            return (out, self._plan_diag) if diag else out
         if self._h is not None:
             self._h.plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings], int(pl.horizon),
                                 float(pl.v_target), float(pl.margin), float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, d,
@@ -861,6 +869,69 @@ class BatchedWaypointEnv:
                 self._plan_struct = ops.planner_struct(pl)
             ops.plan_action(self.tde_cfg, self.dworld, self.state, self._plan_struct, out, only, d)
         return (out, d) if diag else out
+
+    def _score_plans(self, seq, knot_len, tail, only, cost, fail_step, action, diag):
+        """tde_score_plans through the env's binding (arguments already checked)"""
+        pl = self.planner
+        if self._h is not None:
+            self._h.score_plans(seq, knot_len, tail, cost, fail_step, int(pl.horizon), float(pl.v_target), float(pl.margin),
+                                float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, action, diag, int(self.tde_cfg.flags))
+        else:
+            if self._plan_struct is None:
+                self._plan_struct = ops.planner_struct(pl)
+            ops.score_plans(self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step, action, diag)
+
+    def score_plans(self, seq, knot_len=None, tail=0, only=None):
+        """how each of N action sequences per ego fares on the state as it is (tde_score_plans with self.planner's horizon, margin,
+        v_target and weights) -> (cost float32 [B, N], fail_step int32 [B, N]) on the device.  seq: float32 [B, N, K, 2] device tensor
+        of (acceleration, steering) knots, contiguous (raises otherwise: no copy is made); knot k holds knot_len steps (None:
+        ceil(horizon / K)), the last one to the end of the horizon; then `tail` steps of full braking.  fail_step is the first step
+        off the road, on a predicted box of another agent or on a red stop line, horizon + tail + 1 for a safe sequence; a lower cost
+        is better and any earlier failure costs more than any later one.  only: uint8 [B]; the other rows are not written."""
+        N, K, knot_len, tail = ops.check_plan_set(seq, self.num_envs, self.planner.horizon, knot_len, tail)
+        if only is not None:
+            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
+        cost = torch.zeros((self.num_envs, N), dtype=torch.float32, device=self.torch_device)
+        fail_step = torch.zeros((self.num_envs, N), dtype=torch.int32, device=self.torch_device)
+        self._score_plans(seq, knot_len, tail, only, cost, fail_step, None, None)
+        return cost, fail_step
+
+    def _plan_refined(self, out, only, diag):
+        """plan_actions() under self.plan_refine (config.PlanRefine states the rounds): device work only, no synchronisation"""
+        pl, pr = self.planner, self.plan_refine
+        B, nc, K, R = self.num_envs, pl.n_candidates, int(pr.knots), int(pr.rounds)
+        dev = self.torch_device
+        if self._refine is None:
+            acc, ste = pl.tables()
+            lat = np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(np.float32)      # [nc, 2]: candidate i = ia * n_s + is
+            rf = {"seq0": torch.from_numpy(lat).to(dev)[None, :, None, :].expand(B, nc, K, 2).contiguous(),
+                  "cost0": torch.zeros((B, nc), dtype=torch.float32, device=dev), "fail0": torch.zeros((B, nc), dtype=torch.int32, device=dev),
+                  "lo": torch.tensor([-_abi.PLAN_BOX_ACCEL, -_abi.PLAN_BOX_STEER], dtype=torch.float32, device=dev),
+                  "hi": torch.tensor([_abi.PLAN_BOX_ACCEL, _abi.PLAN_BOX_STEER], dtype=torch.float32, device=dev)}
+            if R:
+                s, deltas = np.float32(1.0), []
+                for _ in range(R):
+                    s = np.float32(s * np.float32(pr.shrink))
+                    deltas.append(lat * s)
+                rf["delta"] = torch.from_numpy(np.stack(deltas)).to(dev)                                        # [R, nc, 2]
+                rf["cand"] = torch.zeros((B, K * nc, K, 2), dtype=torch.float32, device=dev)
+                rf["cost"] = torch.zeros((B, K * nc), dtype=torch.float32, device=dev)
+                rf["fail"] = torch.zeros((B, K * nc), dtype=torch.int32, device=dev)
+            self._refine = rf
+        rf = self._refine
+        knot_len, tail = -(-int(pl.horizon) // K), int(pr.tail)
+        self._score_plans(rf["seq0"], knot_len, tail, only, rf["cost0"], rf["fail0"], out, diag)
+        seqs = rf["seq0"]
+        for r in range(R):
+            # (rows outside `only` keep an older winner in diag: clamped, their candidates are built and never judged)
+            win = diag[:, 0].long().clamp_(0, seqs.shape[1] - 1)
+            w = torch.gather(seqs, 1, win.view(B, 1, 1, 1).expand(B, 1, K, 2)).squeeze(1)                       # [B, K, 2]
+            cv = rf["cand"].view(B, K, nc, K, 2)
+            cv.copy_(w[:, None, None, :, :].expand(B, K, nc, K, 2))
+            for k in range(K):
+                cv[:, k, :, k, :] = torch.minimum(torch.maximum(w[:, k, None, :] + rf["delta"][r][None], rf["lo"]), rf["hi"])
+            seqs = rf["cand"]
+            self._score_plans(seqs, knot_len, tail, only, rf["cost"], rf["fail"], out, diag)
 
     def _render1(self, out, only=None):
         """single-frame raster of every (or the masked) view into `out`"""
@@ -1255,12 +1326,13 @@ class WaypointSuiteEnv(_GymEnvBase):
     metadata = {"render_modes": ["video", "rgb_array"], "render_fps": 10}
 
     def __init__(self, cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None,
-                 video_camera="map", background=None, near_field=None, planner=None):
+                 video_camera="map", background=None, near_field=None, planner=None, plan_refine=None):
         """render_mode="video": every reset() and step() records a video_res x video_res frame at video_fov metres across (the
         reference's BirdviewRecordingWrapper, gym_env.py:295-297) from `video_camera` ("map": the centre of the map, heading pi/2;
         "ego"; or (x, y, psi)); get_birdviews() returns them, close() writes video_filename (video.save_video).
         background / near_field: the background-traffic files and the near-field traffic of every reset, as BatchedWaypointEnv
-        takes them (the reference's background mode: gym_env.py:200-238).  planner: the config.Planner of expert_action()."""
+        takes them (the reference's background mode: gym_env.py:200-238).  planner / plan_refine: the config.Planner and the optional
+        config.PlanRefine of expert_action()."""
         self.config = cfg
         if cfg.render_mode == "video":               # the batched env renders rgb_array; the frames are recorded here
             cfg = dataclasses.replace(cfg, render_mode="rgb_array")
@@ -1269,7 +1341,7 @@ class WaypointSuiteEnv(_GymEnvBase):
         self._env = BatchedWaypointEnv(cfg, data, num_envs=1, agents_per_env=agents_per_env, obs_mode="birdview",
                                        frame_stack=1, auto_reset=False, info_magnitudes=True, road_meshes=road_meshes,
                                        traffic_lights=traffic_lights, start_headings=start_headings, background=background,
-                                       near_field=near_field, planner=planner)
+                                       near_field=near_field, planner=planner, plan_refine=plan_refine)
         self.torch_device = self._env.torch_device
         self.render_mode = self.config.render_mode
         self._video = None
@@ -1424,7 +1496,7 @@ class SingleAgentWrapper(_GymWrapperBase):
 
 
 def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None, video_camera="map",
-         background=None, near_field=None, planner=None):
+         background=None, near_field=None, planner=None, plan_refine=None):
     """what gym.make('torchdriveenv-v0', args={'cfg': cfg, 'data': data}) returns in the reference (ref __init__.py:10).
     `road_meshes`, `traffic_lights`, `start_headings`: what the reference takes from torchdrivesim's map config of the location
     (`find_map_config`: road mesh ref gym_env.py:184, stop lines + light controller :181-189, lanelet directions :359) - see
@@ -1434,7 +1506,7 @@ def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_light
     return SingleAgentWrapper(WaypointSuiteEnv(cfg=cfg, data=data, agents_per_env=agents_per_env, road_meshes=road_meshes,
                                                traffic_lights=traffic_lights, start_headings=start_headings,
                                                video_camera=video_camera, background=background, near_field=near_field,
-                                               planner=planner))
+                                               planner=planner, plan_refine=plan_refine))
 
 
 if gym is not None:  # pragma: no cover

@@ -288,6 +288,55 @@ def plan_action(cfg, dworld, state, planner, out=None, only=None, diag=None):
     return out
 
 
+def check_plan_set(seq, B, H, knot_len=None, tail=0):
+    """the shape / range checks of score_plans that need no GPU: seq float32 [B, N, K, 2], contiguous (no silent copy) -> (N, K,
+    knot_len, tail) with knot_len=None resolved to ceil(H / K)"""
+    if not torch.is_tensor(seq) or seq.dtype != torch.float32:
+        raise ValueError("seq must be a float32 torch tensor")
+    if seq.dim() != 4 or seq.shape[0] != B or seq.shape[3] != 2:
+        raise ValueError(f"seq must be [B={B}, N, K, 2], got {tuple(seq.shape)}")
+    if not seq.is_contiguous():
+        raise ValueError("seq must be contiguous (score_plans makes no copy of it)")
+    N, K = int(seq.shape[1]), int(seq.shape[2])
+    if not 1 <= N <= _abi.PLAN_MAX_SET:
+        raise ValueError(f"seq: N must be in [1, {_abi.PLAN_MAX_SET}], got {N}")
+    if not 1 <= K <= _abi.PLAN_MAX_H:
+        raise ValueError(f"seq: K must be in [1, {_abi.PLAN_MAX_H}], got {K}")
+    if knot_len is None:
+        knot_len = -(-int(H) // K)
+    if int(knot_len) != knot_len or int(knot_len) < 1:
+        raise ValueError("knot_len must be an integer >= 1")
+    if int(tail) != tail or not 0 <= int(tail) <= _abi.PLAN_MAX_TAIL:
+        raise ValueError(f"tail must be an integer in [0, {_abi.PLAN_MAX_TAIL}]")
+    return N, K, int(knot_len), int(tail)
+
+
+def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, action=None, diag=None):
+    """tde_score_plans: how each of N action sequences per env fares on the state as it is -> (cost float32 [B, N], fail_step int32
+    [B, N]) on the device.  seq: float32 [B, N, K, 2] device tensor of (acceleration, steering) knots, contiguous; knot k holds for
+    knot_len steps (None: ceil(horizon / K)), then `tail` steps of full braking; planner: config.Planner (or its tde_planner) for
+    the horizon, margin, v_target and the weights.  fail_step == horizon + tail + 1: the sequence is safe.  only: uint8 [B], the
+    other rows of every output are left as they are; action float32 [B, 2] / diag int32 [B, 4]: optional, receive the winner's first
+    action and its tde_plan_diag row.  Asynchronous."""
+    L = _lib.load()
+    ps = planner if isinstance(planner, _abi.TdePlanner) else planner_struct(planner)
+    N, K, knot_len, tail = check_plan_set(seq, state.B, ps.horizon, knot_len, tail)
+    dev = torch.device(state.device)
+    if cost is None:
+        cost = torch.empty((state.B, N), dtype=torch.float32, device=dev)
+    if fail_step is None:
+        fail_step = torch.empty((state.B, N), dtype=torch.int32, device=dev)
+    st = _abi.TdePlanSet(_chk(seq, torch.float32, state.B * N * K * 2, "seq", dev), N, K, knot_len, tail)
+    pc = _chk(cost, torch.float32, state.B * N, "cost", dev)
+    pf = _chk(fail_step, torch.int32, state.B * N, "fail_step", dev)
+    pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
+    pa = _chk(action, torch.float32, state.B * 2, "action", dev, optional=True)
+    pd = _chk(diag, torch.int32, state.B * 4, "diag", dev, optional=True)
+    _lib.check(_call(dev, L.tde_score_plans, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps), C.byref(st), pm, pc,
+                     pf, pa, pd, _lib.current_stream(dev)), "tde_score_plans")
+    return cost, fail_step
+
+
 def render_ego(cfg, dworld, state, H=64, W=64, fov=35.0, n_stack=1, out=None, layers=None, phase=0, flags=0,
                fresh=None, only=None):
     """render_egocentric() of every env's ego -> uint8 [B, 3*n_stack, H, W] on device (ref gym_env.py:122-124).

@@ -248,8 +248,8 @@ class ShardedBatchedEnv:
         return out
 
     def plan_actions(self, diag=False):
-        """the sampling planner's actions of every shard on its current state (BatchedWaypointEnv.plan_actions; planner= is an env
-        keyword) in global env order: float32 [B, 2], what step() takes; diag=True: (actions, int32 [B, 4] diag rows)"""
+        """the sampling planner's actions of every shard on its current state (BatchedWaypointEnv.plan_actions; planner= and
+        plan_refine= are env keywords) in global env order: float32 [B, 2], what step() takes; diag=True: (actions, int32 [B, 4] diag rows)"""
         np = self._np
         parts = self._all("plan")
         act = np.concatenate([p[0] for p in parts])
