@@ -1,0 +1,327 @@
+"""Every consumer of the grid index on every world of the mesh zoo (tests/mesh_zoo.py), bit for bit against what the suite already uses
+as truth: the offroad operator, the closed-loop step and the persistent rollouts in every role split (oracle), the infraction
+magnitudes (oracle), the ego birdview and the scene renderer (oracle raster), the vector observation, the planner and the plan judge
+(their numpy restatements, which take the road predicate from the oracle's brute force).  The states are the zoo's poses loaded into
+host and device states: box corners astride the threshold around vertices, slivers, holes and gaps, boxes beyond the grid, boxes 400 m
+away.  Shapes are the smallest that reach the code: 24 envs of 16 slots, one 128-slot case (the wide kernels), one 4-slot case,
+one 32-slot case on the large grid."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+from oracle import oracle  # noqa: E402
+from tests import mesh_zoo as Z  # noqa: E402
+from tests import plan_set_ref as S  # noqa: E402
+from tests import planner_ref as P  # noqa: E402
+from tests import vector_obs_ref as V  # noqa: E402
+from tests.scene_util import free_last_slot, oracle_scene_views  # noqa: E402
+from tests.test_gpu_parity import assert_state_equal, dev  # noqa: E402
+from torchdriveenv_amd import _abi, _lib, ops  # noqa: E402
+from torchdriveenv_amd.config import Planner, VectorObs  # noqa: E402
+from torchdriveenv_amd.state import EnvState  # noqa: E402
+
+DEV = "cuda:0"
+B, A = 24, 16
+ZOO = [(n, c, False) for n in Z.NAMES for c in Z.CELLS] + [(Z.SQUARED, 0.5, True)]
+IDS = [f"{n}-{c}{'-squared' if s else ''}" for n, c, s in ZOO]
+zoo = pytest.mark.parametrize("name,cell,squared", ZOO, ids=IDS)
+# the closed-loop step and the rollouts also at 128 slots (the wide kernels: two roles in eight or four wavefronts) and at 4
+# and at 32 on the large grid (the one-step kernel has its class-map form at 32 and 64 slots only)
+SHAPES = [(n, c, s, B, A) for n, c, s in ZOO] + [("fan", 0.5, False, 4, 128), ("roundabout", 0.25, False, B, 4), ("islands", 0.25, False, 8, 32)]
+SHAPE_IDS = IDS + ["fan-0.5-4x128", "roundabout-0.25-24x4", "islands-0.25-8x32"]
+PLANNED = [(n, c) for n in ("roundabout", "long_slivers", "far_ribbon") for c in Z.CELLS]
+K = 9                           # one zero-action step from the loaded poses, then 8 random-action steps
+_DEVICE_WORLDS = {}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _differ(got, want):
+    return int((np.asarray(got) != np.asarray(want)).sum())
+
+
+def _device(world):
+    if id(world) not in _DEVICE_WORLDS:
+        _DEVICE_WORLDS[id(world)] = (world, world.to_device(DEV))
+    return _DEVICE_WORLDS[id(world)][1]
+
+
+def _loaded(world, cfg, b, seed):
+    """host state of b envs one step after a reset, every slot moved to one of the zoo's poses; the lights (far_ribbon) at different
+    steps of their cycle"""
+    hs = EnvState(b, world.A)
+    oracle.env_reset(cfg, world, hs)
+    hs.load(Z.poses(world, b * world.A, np.random.default_rng([seed, world.A])))
+    # no env is at step 0: a state there promises its NPCs at their spawn records (tde_first_gap, the first-step gap cache); on
+    # far_ribbon steps 1, 2, 3: its cycle of 4 red and 3 green steps is crossed within the steps that follow
+    hs["steps"][...] = 1 + (np.arange(b) % 3 if world.has_lights else 0)
+    if getattr(world, "zoo_name", "") == "fan":
+        _fan_boxes_hang_on_late_records(world, hs)
+    return hs
+
+
+def _fan_boxes_hang_on_late_records(world, hs):
+    """what makes fan's long candidate lists matter, from the oracle alone: boxes that are on the road with every corner while one
+    corner is within the threshold of no record before position 64 / 128 of its cell's list, or of the last of 255 records only - a
+    walk that stops early or drops the odd last record turns exactly these boxes offroad"""
+    thr2 = np.float32(0.25)
+    cx, cy = Z.box_corners(hs["x"], hs["y"], hs["psi"], hs["len"], hs["wid"])
+    tri = world.arrays["tri"]
+    near = np.array([oracle.point_mesh_d2(a, b, tri) <= thr2 for a, b in zip(cx.ravel(), cy.ravel())]).reshape(-1, 4)
+    pos, length = (v.reshape(-1, 4) for v in Z.list_positions(world, cx.ravel(), cy.ravel(), thr2))
+    on = near.all(1)
+    n64, n128, n_last = (int((on & m.any(1)).sum()) for m in (pos > 64, pos > 128, (pos == 255) & (length == 255)))
+    assert n64 >= hs.B and n128 >= hs.B // 2 and n_last >= 2, f"fan: {n64}, {n128}, {n_last} boxes hang on records beyond 64, beyond 128, on the 255th"
+    if hs.A == 16:                              # (and egos among them: rewards, done bits and magnitudes are the ego's)
+        assert (on & (pos > 64).any(1))[::16].sum() >= 1 + hs.B // 12
+
+
+def _on_device(hs, **kw):
+    d = EnvState(hs.B, hs.A, device=DEV, **kw)
+    d.load(hs.host())
+    return d
+
+
+def _copy(hs):
+    c = EnvState(hs.B, hs.A)
+    c.load(hs.host())
+    return c
+
+
+def _actions(b, seed):
+    rng = np.random.default_rng(seed)
+    a = np.stack([rng.uniform(-1, 1, (K, b)), rng.uniform(-0.3, 0.3, (K, b))], -1).astype(np.float32)
+    a[0] = 0.0
+    return a
+
+
+def _cfg(world, squared, **kw):
+    # infractions do not end an episode (the egos keep driving from where the poses put them: over the edges, the holes, off the
+    # grid), eight steps do (six steps from the poses, then a re-spawn inside the nine steps)
+    kw = dict(dict(terminated_at_infraction=0, max_steps=8, distance_cutoff=0.25), **kw)
+    return Z.config(world, squared, **kw)
+
+
+@zoo
+def test_offroad_operator(name, cell, squared):
+    world = Z.world(name, cell, squared)
+    hs = _loaded(world, _cfg(world, squared, seed=1), B, seed=11)
+    args = [hs[k] for k in ("x", "y", "psi", "len", "wid", "present")]
+    moe = np.zeros(B, np.int32)
+    want = oracle.compute_offroad(B, A, *args, world, moe, world.threshold)
+    got = ops.compute_offroad(B, A, *map(dev, args), _device(world), dev(moe), world.threshold).cpu().numpy()
+    assert np.array_equal(got, want), f"{Z.where(name, cell, squared)}: {_differ(got, want)} of {want.size} offroad flags differ"
+    assert 0.05 < want.mean() < 1.0
+
+
+@pytest.mark.parametrize("name,cell,squared,b,a", SHAPES, ids=SHAPE_IDS)
+def test_step_and_rollout_in_every_role_split(name, cell, squared, b, a):
+    """tde_env_step (one role / three roles / the wide kernel; with obs and magnitudes, and without the lookup caches) and
+    tde_env_rollout (one / two / three roles) from the loaded poses == the oracle's steps: rewards, done bits, magnitudes per step,
+    the whole state after the first and the last step"""
+    where = Z.where(name, cell, squared) + f", {b} x {a}"
+    world = Z.world(name, cell, squared, A=a)
+    dw = _device(world)
+    assert bool(world.ints["hints"] & _abi.WORLD_LARGE_GRID) == (name == "islands" and cell == 0.25)
+    cfg = _cfg(world, squared, seed=2)
+    assert bool(cfg.flags & _abi.F_TRAFFIC_LIGHTS) == (name == "far_ribbon")
+    hs0 = _loaded(world, cfg, b, seed=12)
+    acts = _actions(b, seed=13)
+    hs = _copy(hs0)
+    snaps, per_step = {}, []
+    for t in range(K):
+        hs["action"][...] = acts[t]
+        oracle.env_step(cfg, world, hs)
+        per_step.append((hs["reward"].copy(), hs["done_bits"].copy(), hs["magnitudes"].copy()))
+        if t in (0, K - 1):
+            snaps[t] = hs.host()
+    assert any((d & 3).any() for _, d, _ in per_step) and any((d & 4).any() for _, d, _ in per_step), where   # ends and offroad egos
+    step_forms = {128: ("solo", None), 32: ("solo", "trio"), 16: ("solo", "trio"), 4: ("solo",)}[a]
+    variants = [(f, dict(with_obs=True, with_magnitudes=True)) for f in step_forms] + [(None, dict(with_cache=False))]
+    dacts = dev(acts)
+    try:
+        for form, kw in variants:
+            what = f"{where}, step {form or 'auto'}{'' if kw.get('with_cache', True) else ' without caches'}"
+            d = _on_device(hs0, **kw)
+            _lib.kernel_override(step=form)
+            for t in range(K):
+                ops.env_step(cfg, dw, d, action=dacts[t])
+                r, dn, mg = per_step[t]
+                got = d["reward"].cpu().numpy()
+                assert np.array_equal(_bits(got), _bits(r)), f"{what}: {_differ(_bits(got), _bits(r))} rewards differ at step {t}"
+                got = d["done_bits"].cpu().numpy()
+                assert np.array_equal(got, dn), f"{what}: {_differ(got, dn)} done bits differ at step {t}"
+                got = d["magnitudes"].cpu().numpy()
+                assert np.array_equal(_bits(got), _bits(mg)), f"{what}: {_differ(_bits(got), _bits(mg))} magnitudes differ at step {t}"
+                if t in snaps:
+                    assert_state_equal(snaps[t], d.host(), f"{what}, step {t}")
+                    if d["obs"] is not None:
+                        got, ref = d["obs"].view(torch.int32).cpu().numpy(), ops.state_obs(dw, d).view(torch.int32).cpu().numpy()
+                        assert np.array_equal(got, ref), f"{what}: {_differ(got, ref)} of {ref.size} obs values differ from tde_state_obs at step {t}"
+            _lib.kernel_override()
+        hr, hd = oracle.env_rollout(cfg, world, _copy(hs0), acts)
+        for t in range(K):
+            n_bad = _differ(_bits(hr[t]), _bits(per_step[t][0])) + _differ(hd[t], per_step[t][1])
+            assert n_bad == 0, f"{where}: the oracle's rollout and its steps differ in {n_bad} rewards / done bytes at step {t}"
+        for form in {128: ("solo", None, "duo"), 32: ("solo", "duo", "trio"), 16: ("solo", "duo", "trio"), 4: ("solo", "duo")}[a]:
+            what = f"{where}, rollout {form or 'auto'}"
+            d = _on_device(hs0, with_episode=False, with_magnitudes=False)
+            _lib.kernel_override(rollout=form)
+            r, dn = ops.env_rollout(cfg, dw, d, dacts)
+            torch.cuda.synchronize()
+            _lib.kernel_override()
+            r, dn = r.cpu().numpy(), dn.cpu().numpy()
+            assert np.array_equal(_bits(r), _bits(hr)), f"{what}: {_differ(_bits(r), _bits(hr))} of {hr.size} rewards differ"
+            assert np.array_equal(dn, hd), f"{what}: {_differ(dn, hd)} of {hd.size} done bytes differ"
+            skip = ("done_bits", "magnitudes", "ep_return", "ep_final", "ep_final_len")
+            assert_state_equal({k: v for k, v in snaps[K - 1].items() if k not in skip}, d.host(), what)
+    finally:
+        _lib.kernel_override()
+
+
+@zoo
+@pytest.mark.parametrize("near_range", [0.0, None], ids=["no_near_lists", "near_lists"])
+def test_magnitudes(name, cell, squared, near_range):
+    """tde_ego_infractions on the loaded poses - boxes beyond the grid and 400 m away among them - and tde_env_post_step after a
+    step without re-spawn == the oracle's brute force, with near lists and without any (every flagged corner scans the grid)"""
+    where = Z.where(name, cell, squared) + f", near_range {near_range}"
+    world = Z.world(name, cell, squared, near_range=near_range)
+    tn = world.arrays["tile_near"]
+    assert bool(((tn != 0) & (tn != 0xFFFFFFFF)).any()) == (near_range is None)
+    dw = _device(world)
+    cfg = _cfg(world, squared, seed=3, flags=_abi.F_ALL & ~_abi.F_AUTORESET)
+    cfg_post = _abi.TdeConfig.from_buffer_copy(cfg)
+    cfg_post.flags |= _abi.F_AUTORESET
+    hs = _loaded(world, cfg, B, seed=14)
+    d = _on_device(hs, with_obs=True)
+    want = oracle.ego_infractions(cfg, world, hs)
+    got = ops.ego_infractions(cfg, dw, d).cpu().numpy()
+    assert np.array_equal(_bits(got), _bits(want)), f"{where}: {_differ(_bits(got), _bits(want))} of {want.size} magnitudes differ"
+    assert (want[:, 0] > 300.0).any() and (want[:, 0] > 0).sum() > B // 4, where          # (egos 400 m away among them)
+    mag = torch.zeros(B, 4, device=DEV)
+    acts = _actions(B, seed=15)
+    for t in range(3):
+        hs["action"][...] = acts[t]
+        oracle.env_step(cfg, world, hs)
+        want = oracle.ego_infractions(cfg, world, hs)
+        done = (hs["terminated"] | hs["truncated"]).astype(np.uint8)
+        oracle.env_reset(cfg, world, hs, done)
+        ops.env_step(cfg, dw, d, action=dev(acts[t]))
+        ops.env_post_step(cfg_post, dw, d, mag)
+        got = mag.cpu().numpy()
+        assert np.array_equal(_bits(got), _bits(want)), f"{where}: {_differ(_bits(got), _bits(want))} post-step magnitudes differ at step {t}"
+    assert_state_equal(hs.host(), d.host(), f"{where}: post_step")
+
+
+@zoo
+def test_birdview(name, cell, squared):
+    """tde_render_ego from the loaded poses - egos on road edges, over holes, beside slivers, off the grid: 64 x 64 at 35 m and 20 m,
+    36 x 36 at 70 m (other block sizes of the pyramid), right- and left-handed"""
+    world = Z.world(name, cell, squared)
+    dw = _device(world)
+    cfg = _cfg(world, squared, seed=4)
+    hs = _loaded(world, cfg, B, seed=16)
+    hs["target_idx"][::2] = 2                                # (half of the views without waypoint discs over the road)
+    d = _on_device(hs)
+    seen = set()
+    for H, fov in ((64, 35.0), (64, 20.0), (36, 70.0)):
+        for flags in (0, _abi.RENDER_LEFT_HANDED):
+            want = oracle.render_ego(cfg, world, hs, H, H, fov, flags=flags)
+            got = ops.render_ego(cfg, dw, d, H, H, fov, flags=flags).cpu().numpy()
+            assert np.array_equal(got, want), (f"{Z.where(name, cell, squared)}: {_differ(got, want)} of {want.size} bytes differ "
+                                               f"({H} x {H}, fov {fov}, flags {flags})")
+            seen |= set(np.unique(want[:, 0]).tolist())
+    assert 255 in seen and (128 in seen or name == "speck")     # background and road (speck's lies under the egos and waypoints)
+
+
+@pytest.mark.parametrize("name", ["roundabout", "far_ribbon"])
+@pytest.mark.parametrize("cell", Z.CELLS)
+def test_scene_renderer(name, cell):
+    """tde_render_scene's tiles: a 256 x 256 map camera over the whole mesh, two envs"""
+    world = Z.world(name, cell)
+    dw = _device(world)
+    cfg = _cfg(world, False, seed=5)
+    hs = _loaded(world, cfg, 2, seed=17)
+    h = free_last_slot(hs.host(), 2, A)
+    d = EnvState(2, A, device=DEV)
+    d.load(h)
+    fov = 140.0
+    for flags in (0, _abi.RENDER_LEFT_HANDED):
+        got = ops.render_scene(cfg, dw, d, [0, 1], 256, 256, fov, camera="map", flags=flags | _abi.RENDER_PLAIN_EGO).cpu().numpy()
+        want = oracle_scene_views(cfg, world, h, 2, A, [0, 1], world.scene_cameras()[h["scn"][[0, 1]]], 256, 256, fov, flags)
+        assert np.array_equal(got, want), f"{Z.where(name, cell)}: {_differ(got, want)} of {want.size} bytes differ (flags {flags})"
+    assert (want[:, 0] == 128).mean() > 0.02
+
+
+@zoo
+@pytest.mark.parametrize("ray_step", [0.5, 0.2])
+def test_vector_obs(name, cell, squared, ray_step):
+    """tde_vector_obs: the road rays and their clearance-based sample skipping, at two sample spacings"""
+    world = Z.world(name, cell, squared)
+    cfg = _cfg(world, squared, seed=6)
+    hs = _loaded(world, cfg, B, seed=18)
+    vo = VectorObs(k_neighbours=4, n_rays=16, ray_range=30.0, ray_step=ray_step, neighbour_radius=30.0)
+    want = V.vector_obs(cfg, world, hs, vo)
+    got = ops.vector_obs(cfg, _device(world), _on_device(hs), vo).cpu().numpy()
+    assert np.array_equal(_bits(got), _bits(want)), (f"{Z.where(name, cell, squared)}, ray_step {ray_step}: "
+                                                     f"{_differ(_bits(got), _bits(want))} of {want.size} values differ")
+    road = want[:, vo.slices()["road"]]
+    assert (road < vo.ray_range).any() and (road > ray_step).any()
+
+
+def _planner_state(world, cfg, seed):
+    """the loaded poses with the egos slowed to a few m/s and half of them put back on the road, so that some plans are safe"""
+    hs = _loaded(world, cfg, B, seed)
+    fresh = EnvState(B, A)
+    oracle.env_reset(cfg, world, fresh)
+    for k in ("x", "y", "psi"):
+        hs[k][0:B * A:2 * A] = fresh[k][0:B * A:2 * A]
+    hs["v"][::A] = np.random.default_rng(seed).uniform(0.5, 5.0, B).astype(np.float32)
+    return hs
+
+
+@pytest.mark.parametrize("name,cell", PLANNED, ids=[f"{n}-{c}" for n, c in PLANNED])
+def test_planner(name, cell):
+    """tde_plan_action: the road judge of the sampling planner along 63 candidate trajectories per ego"""
+    world = Z.world(name, cell)
+    cfg = _cfg(world, False, seed=7)
+    hs = _planner_state(world, cfg, seed=19)
+    pl = Planner(horizon=16)
+    want_a, want_d = P.plan(cfg, world, hs, pl)
+    out = torch.full((B, 2), -3.0, dtype=torch.float32, device=DEV)
+    dg = torch.full((B, 4), -7, dtype=torch.int32, device=DEV)
+    ops.plan_action(cfg, _device(world), _on_device(hs), pl, out, None, dg)
+    got_a, got_d = out.cpu().numpy(), dg.cpu().numpy().view(_abi.PLAN_DIAG_DTYPE).reshape(B)
+    where = Z.where(name, cell)
+    for n in ("winner", "fail_step", "n_safe"):
+        assert np.array_equal(got_d[n], want_d[n]), f"{where}: {_differ(got_d[n], want_d[n])} of {B} diag.{n} differ"
+    got_c, want_c = got_d["cost"].view(np.uint32), want_d["cost"].view(np.uint32)
+    assert np.array_equal(got_c, want_c), f"{where}: {_differ(got_c, want_c)} of {B} diag.cost differ"
+    assert np.array_equal(_bits(got_a), _bits(want_a)), f"{where}: {_differ(_bits(got_a), _bits(want_a))} of {want_a.size} action values differ"
+    assert (want_d["n_safe"] > 0).any() and (want_d["n_safe"] < pl.n_candidates).any(), where
+
+
+@pytest.mark.parametrize("N", [40, 130], ids=["one_wavefront", "team"])
+@pytest.mark.parametrize("name,cell", PLANNED, ids=[f"{n}-{c}" for n, c in PLANNED])
+def test_plan_judge(name, cell, N):
+    """tde_score_plans on random knot sequences, in both of its forms: one wavefront per env (N <= 64) and a team of wavefronts"""
+    world = Z.world(name, cell)
+    cfg = _cfg(world, False, seed=8)
+    hs = _planner_state(world, cfg, seed=20)
+    pl = Planner(horizon=16)
+    rng = np.random.default_rng(21)
+    seq = S.random_knots(rng, B, N, 4)
+    calm = rng.random((B, N)) < 0.35
+    seq[calm] = np.stack([rng.uniform(-1.0, 0.1, seq[calm].shape[:-1]), rng.uniform(-0.02, 0.02, seq[calm].shape[:-1])], -1).astype(np.float32)
+    want = S.score(cfg, world, hs, pl, seq, 4, 10)
+    cost, fail = ops.score_plans(cfg, _device(world), _on_device(hs), pl, dev(seq), 4, 10)
+    got_c, got_f = cost.cpu().numpy(), fail.cpu().numpy()
+    where = Z.where(name, cell) + f", N {N}"
+    assert np.array_equal(got_f, want["f"]), f"{where}: {_differ(got_f, want['f'])} of {got_f.size} fail steps differ"
+    assert np.array_equal(_bits(got_c), _bits(want["cost"])), f"{where}: {_differ(_bits(got_c), _bits(want['cost']))} of {got_c.size} costs differ"
+    assert (want["cause"] == S.OFFROAD).any() and (want["f"] == pl.horizon + 10 + 1).any(), where

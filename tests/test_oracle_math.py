@@ -5,7 +5,7 @@ import math
 import numpy as np
 
 from oracle import oracle
-from torchdriveenv_amd import _abi
+from tests.mesh_zoo import edge_points as _edge_points, grid_offroad_numpy
 
 
 def test_sincos_within_2ulp_of_libm():
@@ -84,41 +84,6 @@ def test_philox_known_answer():
         [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]
 
 
-def grid_offroad_numpy(world, map_id, px, py, thr, use_sub=False):
-    """float32 emulation of the kernel's cell lookup + candidate test (tde_device.h: cell_lookup / box_offroad)"""
-    f = np.float32
-    m = world.arrays["maps"][map_id]
-    words, recs = world.arrays["cell_word"], world.arrays["cell_tri"]
-    out = np.zeros(len(px), bool)
-    for i, (x, y) in enumerate(zip(px.astype(f), py.astype(f))):
-        fx, fy = f((x - m["ox"]) * m["inv_cell"]), f((y - m["oy"]) * m["inv_cell"])
-        if not (fx >= 0 and fy >= 0 and fx < m["nx"] and fy < m["ny"]):
-            out[i] = True
-            continue
-        ix, iy = int(fx), int(fy)
-        wd = int(words[m["cell_base"] + (iy << m["row_shift"]) + ix])
-        cls = wd & 3
-        if cls != _abi.CELL_MIXED:
-            out[i] = cls == _abi.CELL_EMPTY
-            continue
-        if use_sub:                                        # sub-cell classes of the MIXED cell (world.py: subcell_classes)
-            tile = ((iy >> 2) << (int(m["row_shift"]) - 3)) + (ix >> 3)
-            bm = int(world.arrays["cell_sub"][m["cell_base"] + ((tile << 5) | ((iy & 3) << 3) | (ix & 7))])
-            sx, sy = min(int((fx - f(ix)) * f(4)), 3), min(int((fy - f(iy)) * f(4)), 3)
-            sc = (bm >> (2 * (4 * sy + sx))) & 3
-            if sc != _abi.CELL_MIXED:
-                out[i] = sc == _abi.CELL_EMPTY
-                continue
-        ok = False
-        first = int(m["rec_base"]) + (wd >> 10)         # record offsets count from the map's rec_base (ABI 9)
-        for k in range(first, first + ((wd >> 2) & 255)):
-            if oracle.point_mesh_d2(x, y, recs[k, :6]) <= f(thr) * f(thr):
-                ok = True
-                break
-        out[i] = not ok
-    return out
-
-
 def test_grid_index_equals_brute_force(small_world):
     w = small_world
     rng = np.random.default_rng(7)
@@ -139,18 +104,6 @@ def test_grid_index_equals_brute_force(small_world):
         got = grid_offroad_numpy(w, map_id, px, py, 0.5, use_sub=True)     # what the rasteriser does in MIXED cells
         assert np.array_equal(got, want)
         assert 0.2 < want.mean() < 0.95
-
-
-def _edge_points(tri, n, rng, spread=0.6):
-    """points scattered around the mesh's vertices and edge midpoints (where the offroad predicate flips) plus a few far ones"""
-    t = np.asarray(tri, np.float64).reshape(-1, 3, 2)
-    k = rng.integers(len(t), size=n)
-    a, b = t[k, rng.integers(3, size=n)], t[k, rng.integers(3, size=n)]
-    p = a + (b - a) * rng.uniform(size=(n, 1)) + rng.normal(0, spread, (n, 2))
-    far = rng.uniform(size=n) < 0.1
-    lo, hi = t.reshape(-1, 2).min(0) - 5, t.reshape(-1, 2).max(0) + 5
-    p[far] = rng.uniform(lo, hi, (int(far.sum()), 2))
-    return p[:, 0].astype(np.float32), p[:, 1].astype(np.float32)
 
 
 def test_near_mesh_predicate_equals_brute_force_minimum(small_world, small_town):
