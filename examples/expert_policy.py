@@ -2,7 +2,7 @@
 batch; the rates the reference trainer's evaluation callback logs (ref examples/rl_training.py:23-119: success, offroad, collision,
 red light) are printed and, with a file name, the (observation, action) pairs are saved for behaviour cloning.
 
-    python examples/expert_policy.py [num_envs] [steps] [pairs.npz]
+    python examples/expert_policy.py [--refine] [--predict constant|route] [num_envs] [steps] [pairs.npz]
 """
 import os
 import sys
@@ -19,13 +19,18 @@ from torchdriveenv_amd.synth import synthetic_world
 
 def main():
     args = [a for a in sys.argv[1:] if a != "--refine"]
+    predict = "constant"                                            # --predict route: the others by tde_forecast_agents (Planner.predict)
+    if "--predict" in args:
+        i = args.index("--predict")
+        predict = args[i + 1]
+        del args[i:i + 2]
     refine = PlanRefine() if "--refine" in sys.argv[1:] else None   # --refine: brake tail + knot refinement (tde_score_plans)
     num_envs = int(args[0]) if len(args) > 0 else 1024
     steps = int(args[1]) if len(args) > 1 else 400
     save = args[2] if len(args) > 2 else None
     cfg = EnvConfig(seed=0, distance_cutoff=0.25)
     world = synthetic_world(n_scn=64, A=16, seed=0, n_maps=4)               # or a WaypointSuite from the loaders
-    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, obs_mode="vector", planner=Planner(), plan_refine=refine)
+    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, obs_mode="vector", planner=Planner(predict=predict), plan_refine=refine)
     obs = env.reset()
     stats = torch.zeros(6, dtype=torch.float64, device=obs.device)   # episodes, infraction ends, offroad, collision, red light, waypoints
     pairs = []

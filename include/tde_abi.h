@@ -506,6 +506,7 @@ typedef struct tde_plan_diag {  /* 16 bytes per env */
 #define TDE_PLAN_MAX_TAIL 64    /* tail in [0, TDE_PLAN_MAX_TAIL] */
 #define TDE_PLAN_BOX_ACCEL 1.0f /* the action box (gym_env.py:83-84): |acceleration| <= 1 ... */
 #define TDE_PLAN_BOX_STEER 0.3f /* ... and |steering| <= 0.3; knots are clamped into it */
+#define TDE_FORECAST_MAX_T (TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL) /* steps of a forecast (tde_forecast_agents, tde_score_plans_forecast) */
 typedef struct tde_plan_set {
     const float *seq;           /* [B][N][K][2] float32 (acceleration, steering) knots, contiguous */
     int32_t N;                  /* sequences per env */

@@ -308,6 +308,57 @@ TDE_API int tde_score_plans(const tde_config *cfg, const tde_world *world, const
                             const tde_plan_set *set, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
                             tde_plan_diag *diag, void *stream);
 
+/* Free-flow forecast of the other agents: for every env with only[e] != 0 (uint8 [B]; NULL: all envs), every slot j and h = 1..T,
+ * out[e][h - 1][j] = (x, y, psi, v) of slot j at environment_steps = state.steps[e] + h when nobody is in its cone (out: DEVICE float32
+ * [B][T][A][4]; envs with only[e] == 0 are not touched).  Slot 0 (the ego) and absent slots get four zeros at every h.  No reference
+ * counterpart (its NPCs are a service's: gym_env.py:285-294).  The rule is tde_env_step's treatment of a present slot j >= 1, in its
+ * order, with the controller's leader sweep replaced by "no leader": for an agent whose cone stays empty - and for a replayed one
+ * while its record lasts - row h is, bit for bit, what the h-th tde_env_step from here leaves in the state.  Every expression is
+ * float32 with one rounding per written operation (no contraction); bicycle, sincos_f32, the controller and the stop-line gap are the
+ * step's own (tde_device.h, tde_kernels.h: npc_act_of_gap, red_line_gap; the oracle's tde_npc_action with an empty scene);
+ * tests/forecast_ref.py restates this in numpy.
+ * Env e: F = config.flags, s = state.scn[e], m = world.maps[world.scn[s].map], dt = config.dt; slot j: (x, y, psi, v) and len, lr, vdes
+ * from the state, inv_lr = 1.0f / lr, wp = state.route_wp[e][j] (a running copy: the state is not written), rec = world.spawn[s * A + j]:
+ * route = rec.route and route_n = rec.route_n with TDE_F_NPC (else no route), replay = rec.replay and replay_len = rec.replay_len
+ * with TDE_F_REPLAY (else none); (tx, ty) = world.route_xy[route * RW + wp] while route >= 0 and wp < route_n.
+ * For h = 1..T, k = state.steps[e] + h, (sp, cp) = sincos_f32(psi):
+ *   Action       has_target = TDE_F_NPC and route >= 0 and wp < route_n.  (acc, beta) = (0, 0) without TDE_F_NPC, and at k == 1 without
+ *                TDE_F_NPC_FIRST_STEP.  Otherwise, with amax = npc_max_accel, smax = npc_max_steer, clamp(u, lo, hi) = fminf(fmaxf(u, lo), hi):
+ *                  without has_target: acc = clamp(npc_k_speed * (0.0f - v), -amax, amax), beta = 0 (a finished route brakes to rest);
+ *                  else dx = tx - x, dy = ty - y, fwd = dx*cp + dy*sp, lat = dy*cp - dx*sp, dist = sqrtf(dx*dx + dy*dy), sin_err = lat /
+ *                  fmaxf(dist, 1e-3f); beta = copysignf(smax, lat) when fwd < 0.0f, else clamp(npc_k_steer * sin_err, -smax, smax);
+ *                  gap = fminf(1e30f, red_gap) - 1e30f is what the leader sweep returns when it takes no slot -; vd = fminf(vdes,
+ *                  sqrtf(amax * fmaxf(gap - npc_gap_s0, 0.0f))); acc = clamp(npc_k_speed * (vd - v), -amax, amax).
+ *                red_gap = 1e30f unless TDE_F_TRAFFIC_LIGHTS is set, m.n_stop > 0, has_target holds and red != 0, red = the red mask of
+ *                the phase of k % m.cycle_steps (0 when cycle_steps <= 0); then the least g + npc_gap_s0 - 1.0f (fminf from 1e30f) over
+ *                the stop lines q of m with (red >> light_q) & 1, where ex = x_q - x, ey = y_q - y, fj = ex*cp + ey*sp, lj = ey*cp - ex*sp,
+ *                hd = cp*c_q + sp*s_q, g = fj - 0.5f * len, that have g > 0.0f, fabsf(lj) < hw_q and hd > 0.5f.
+ *   Bicycle      bicycle(x, y, psi, v, inv_lr, acc, beta, dt).
+ *   Replay       with TDE_F_REPLAY, replay >= 0 and k < replay_len: (x, y, psi, v) = world.replay_states[replay * RT + k].
+ *   Route        when has_target and dx*dx + dy*dy < npc_reach * npc_reach for dx = tx - x, dy = ty - y at the new position: wp = wp + 1
+ *                and (tx, ty) = the next route waypoint while wp < route_n.
+ *   Row          out[e][h - 1][j] = (x, y, psi, v).
+ * One lane per (env, slot), the T steps a loop in registers; at every step the lanes of an env store A consecutive 16-byte rows.  Reads
+ * state only.  Rejected: NULL cfg / world / state / out, T outside [1, TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL], config.dt not finite or
+ * <= 0, a NULL array among the state's x, y, psi, v, len, wid, lr, vdes, route_wp, present, scn, steps (a slot is read by the step's own
+ * load_agent, which takes wid with the rest) or world.spawn / world.scn.  No allocation, no synchronisation (graph-capturable). */
+TDE_API int tde_forecast_agents(const tde_config *cfg, const tde_world *world, const tde_state *state, int32_t T, const uint8_t *only,
+                                float *out /* DEVICE [B][T][A][4] */, void *stream);
+
+/* tde_score_plans with the other agents where a caller-given forecast puts them: forecast = DEVICE float32 [B][forecast_T][A][4], rows of
+ * (x, y, psi, v) per step and slot in tde_forecast_agents' layout (tde_forecast_agents' output, a learned predictor's, ...; v is not
+ * read).  Every line of the tde_score_plans specification holds except
+ *   Others      every present slot j in 1..A-1 (presence, len_j and wid_j from the state): at horizon or tail step h in 1..H + T the box
+ *               (x, y, c, s, 0.5f * len_j + margin, 0.5f * wid_j + margin) with (x, y, psi) = forecast[e][h - 1][j] and (s, c) =
+ *               sincos_f32(psi).
+ * A forecast that holds x_j + (float)h * ((v_j * c_j) * dt), y_j + (float)h * ((v_j * s_j) * dt), psi_j gives tde_score_plans' bits.
+ * The rows of envs with only[e] == 0 are not read.  Same two forms as tde_score_plans; each wavefront stages the rows of a step for
+ * itself, (s, c) once per row.  Rejected in addition: forecast NULL, forecast_T < horizon + tail, forecast_T > TDE_PLAN_MAX_H +
+ * TDE_PLAN_MAX_TAIL.  No allocation, no synchronisation (graph-capturable).  tests/forecast_ref.py restates it in numpy. */
+TDE_API int tde_score_plans_forecast(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_planner *plan,
+                                     const tde_plan_set *set, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
+                                     tde_plan_diag *diag, const float *forecast, int32_t forecast_T, void *stream);
+
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 
 /* Offroad grid index of ONE drivable mesh - what the simulator prepares once per map from the road mesh it is constructed

@@ -234,6 +234,9 @@ def check_vector_obs(vo):
     return vo
 
 
+PLANNER_PREDICT = ("constant", "route")
+
+
 @dataclass
 class Planner:
     """The sampling planner of BatchedWaypointEnv.plan_actions() (tde_plan_action, include/tde_hip.h): every pair of an acceleration
@@ -247,7 +250,16 @@ class Planner:
       v_target       speed tracked while a target waypoint exists [m/s] (a finished route plans a stop)
       margin         inflation of the other agents' half extents [m]
       w_progress, w_speed, w_steer   cost weights: per metre gained towards the target waypoint, per (m/s)^2 of speed error summed over
-                     the steps, per rad^2 of steering"""
+                     the steps, per rad^2 of steering
+      predict        how plan_actions() predicts the other agents: "constant" (default; tde_plan_action as it is: each slides along
+                     its heading at its speed) or "route": tde_forecast_agents once per call - the environment's own rules for an agent
+                     with an empty cone: replay records, route following, braking for red lines and at the route's end - and the lattice
+                     judged as one-knot sequences through tde_score_plans_forecast (with PlanRefine's tail and rounds when one is given,
+                     every round on the same forecast).  EXPERIMENTAL and opt-in: the forecast is exact for an agent that meets
+                     nobody (tests/test_gpu_forecast.py) but ignores queues and yielding, and it does not pay yet: on the junction
+                     world with lights (512 envs x 400 steps) collision-ended episodes rise from 117 to 244 of ~1040 (with a 40-step
+                     tail from 95 to 159) while red-light ends fall from 37 to 9 and offroad ends from 18 to 6
+                     (profiles/forecast_behaviour.txt)"""
     accelerations: tuple = (-1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0)
     steerings: tuple = (-0.3, -0.2, -0.1, 0.0, 0.1, 0.2, 0.3)
     horizon: int = 32
@@ -256,6 +268,7 @@ class Planner:
     w_progress: float = 1.0
     w_speed: float = 0.2
     w_steer: float = 1.0
+    predict: str = "constant"
 
     @property
     def n_candidates(self):
@@ -341,4 +354,6 @@ def check_planner(pl):
     vals = [np.float32(v) for v in (pl.v_target, pl.margin, pl.w_progress, pl.w_speed, pl.w_steer)]
     if not all(np.isfinite(v) and v >= 0 for v in vals):
         raise ValueError("planner: v_target, margin and the weights must be finite and >= 0")
+    if pl.predict not in PLANNER_PREDICT:
+        raise ValueError(f"planner: predict must be one of {PLANNER_PREDICT}, got {pl.predict!r}")
     return pl

@@ -535,30 +535,72 @@ int tde_plan_action(const tde_config *cfg, const tde_world *world, const tde_sta
     return tde_host::launch_plan_action(cfg, world, st, pl, only, action, diag, stream);
 }
 
-int tde_score_plans(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
-                    const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream)
+// tde_score_plans and tde_score_plans_forecast (forecast != NULL): one set of checks, `what` names the entry point in the messages
+static int score_plans_checked(const char *what, const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl,
+                               const tde_plan_set *ps, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
+                               tde_plan_diag *diag, void *stream, const float *forecast, int32_t forecast_T)
 {
-    int rc = check_env_args("tde_score_plans", cfg, world, st);
+    const auto badw = [what](const char *msg) {
+        snprintf(g_err, sizeof(g_err), "%s: %s", what, msg);
+        return (int)hipErrorInvalidValue;
+    };
+    int rc = check_env_args(what, cfg, world, st);
     if (rc) return rc;
-    if (!pl || !ps || !ps->seq || !cost || !fail_step) return bad("tde_score_plans: NULL argument");
-    if (ps->N < 1 || ps->N > TDE_PLAN_MAX_SET) return bad("tde_score_plans: N must be in [1, TDE_PLAN_MAX_SET]");
-    if (ps->K < 1 || ps->K > TDE_PLAN_MAX_H) return bad("tde_score_plans: K must be in [1, TDE_PLAN_MAX_H]");
-    if (ps->knot_len < 1) return bad("tde_score_plans: knot_len must be >= 1");
-    if (ps->tail < 0 || ps->tail > TDE_PLAN_MAX_TAIL) return bad("tde_score_plans: tail must be in [0, TDE_PLAN_MAX_TAIL]");
-    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return bad("tde_score_plans: horizon must be in [1, TDE_PLAN_MAX_H]");
+    if (!pl || !ps || !ps->seq || !cost || !fail_step) return badw("NULL argument");
+    if (ps->N < 1 || ps->N > TDE_PLAN_MAX_SET) return badw("N must be in [1, TDE_PLAN_MAX_SET]");
+    if (ps->K < 1 || ps->K > TDE_PLAN_MAX_H) return badw("K must be in [1, TDE_PLAN_MAX_H]");
+    if (ps->knot_len < 1) return badw("knot_len must be >= 1");
+    if (ps->tail < 0 || ps->tail > TDE_PLAN_MAX_TAIL) return badw("tail must be in [0, TDE_PLAN_MAX_TAIL]");
+    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return badw("horizon must be in [1, TDE_PLAN_MAX_H]");
     const float nn[5] = {pl->v_target, pl->margin, pl->w_progress, pl->w_speed, pl->w_steer};
     for (int i = 0; i < 5; ++i)
         if (!(nn[i] >= 0.0f && nn[i] <= FLT_MAX))
-            return bad("tde_score_plans: v_target, margin and the weights must be finite and >= 0");
-    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_score_plans: config.dt must be finite and > 0");
+            return badw("v_target, margin and the weights must be finite and >= 0");
+    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return badw("config.dt must be finite and > 0");
+    if (forecast && (forecast_T < pl->horizon + ps->tail || forecast_T > TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL))
+        return badw("forecast_T must be in [horizon + tail, TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL]");
     if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->present || !st->scn || !st->steps ||
         !st->target_idx || !world->maps || !world->scn || !world->wp_xy || !world->cell_word || !world->cell_cls2 || !world->cell_coarse ||
         !world->cell_tri)
-        return bad("tde_score_plans: a required state / world pointer is NULL");
+        return badw("a required state / world pointer is NULL");
     if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
-        return bad("tde_score_plans: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+        return badw("TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
     if (st->B <= 0) return 0;
-    return tde_host::launch_score_plans(cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream);
+    return tde_host::launch_score_plans(cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, forecast, forecast_T);
+}
+
+int tde_score_plans(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
+                    const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream)
+{
+    return score_plans_checked("tde_score_plans", cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, nullptr, 0);
+}
+
+int tde_score_plans_forecast(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl,
+                             const tde_plan_set *ps, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
+                             tde_plan_diag *diag, const float *forecast, int32_t forecast_T, void *stream)
+{
+    if (!forecast) return bad("tde_score_plans_forecast: forecast is NULL");
+    return score_plans_checked("tde_score_plans_forecast", cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, forecast,
+                               forecast_T);
+}
+
+int tde_forecast_agents(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const uint8_t *only, float *out,
+                        void *stream)
+{
+    int rc = check_env_args("tde_forecast_agents", cfg, world, st);
+    if (rc) return rc;
+    if (!out) return bad("tde_forecast_agents: NULL argument");
+    if (T < 1 || T > TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL) return bad("tde_forecast_agents: T must be in [1, TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL]");
+    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_forecast_agents: config.dt must be finite and > 0");
+    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
+        !st->steps || !world->spawn || !world->scn)
+        return bad("tde_forecast_agents: a required state / world pointer is NULL");
+    if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad("tde_forecast_agents: world.route_xy is NULL");
+    if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad("tde_forecast_agents: world.replay_states is NULL");
+    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->maps || !world->stoplines || !world->phases))
+        return bad("tde_forecast_agents: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if (st->B <= 0) return 0;
+    return tde_host::launch_forecast_agents(cfg, world, st, T, only, out, stream);
 }
 
 int tde_env_reset_render(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask,

@@ -107,9 +107,13 @@ int launch_vector_obs(const tde_config *cfg, const tde_world *world, const tde_s
 // tde_planner.hip: plan_action_kernel (tde_plan_action; arguments checked by the caller)
 int launch_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const uint8_t *only,
                        float *action, tde_plan_diag *diag, void *stream);
-// tde_plan_set.hip: score_plans_kernel (tde_score_plans; arguments checked by the caller)
+// tde_plan_set.hip: score_plans_kernel (tde_score_plans; forecast != NULL: tde_score_plans_forecast; arguments checked by the caller)
 int launch_score_plans(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
-                       const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream);
+                       const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream,
+                       const float *forecast = nullptr, int32_t forecast_T = 0);
+// tde_forecast.hip: forecast_agents_kernel (tde_forecast_agents; arguments checked by the caller)
+int launch_forecast_agents(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const uint8_t *only, float *out,
+                           void *stream);
 
 }  // namespace tde_host
 

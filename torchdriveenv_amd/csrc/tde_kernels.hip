@@ -21,4 +21,9 @@
 #include "tde_rollout_duo.hip"
 #include "tde_rollout_solo.hip"
 #include "tde_render_scene.hip"
+#include "tde_near_field.hip"
+#include "tde_vector_obs.hip"
+#include "tde_planner.hip"
+#include "tde_plan_set.hip"
+#include "tde_forecast.hip"
 #endif

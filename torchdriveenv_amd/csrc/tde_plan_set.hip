@@ -8,7 +8,13 @@
 //     for all, and the winner of each wavefront's butterfly is reduced through LDS by wavefront 0
 //   * a lane reads its knot (8 bytes) when the step loop reaches it: one (a, d) pair in registers whatever K is
 //   * the red masks of steps 1 .. H + tail <= 96: lane l holds the mask of step l in one register and of step 64 + l in a second
-// The specification is restated in numpy by tests/plan_set_ref.py.
+//   * FC = true (tde_score_plans_forecast): the others' boxes of step h come from a caller-given forecast [B][forecast_T][A][4]
+//     instead of the constant-velocity line.  What does not change with the step (slot, half extents, reject radius) is staged once
+//     as before; the rows of step h are staged PER WAVEFRONT at the top of the step - lane q takes compacted row q (and 64 + q),
+//     forms (s, c) = sincos_f32(psi) once for all lanes and writes (x, y, c, s) to its wavefront's own LDS rows - by code every lane
+//     of the wavefront still executes (lanes drop out of the judge at their first failure, not out of the staging), so the team
+//     form has no workgroup barrier in the step loop either.  The rows of step h + 1 are fetched into registers while step h is judged.
+// The specification is restated in numpy by tests/plan_set_ref.py (FC: tests/forecast_ref.py).
 #include "tde_kernels.h"
 #include "tde_host.h"
 
@@ -61,11 +67,21 @@ TDE_DEV void ps_wave_min(uint32_t &kc, int &ki)
     }
 }
 
-template <bool TEAM>
+// the one more argument of the FC form (a pack that is empty without it: the other instantiations keep their argument list)
+struct PsForecast {
+    const float4 *rows;                 // [B][T][A] rows of (x, y, psi, v)
+    int T;
+};
+TDE_DEV PsForecast ps_forecast(const PsForecast &f) { return f; }
+
+template <bool TEAM, typename... Fc>
 __global__ __launch_bounds__(TEAM ? kWave * kPsTeamMax : kWave * kPsWaves) void score_plans_kernel(
     tde_config cfg, tde_world w, tde_state st, tde_planner pl, tde_plan_set ps, const uint8_t *only, float *cost_out, int32_t *fail_out,
-    float *action, tde_plan_diag *diag)
+    float *action, tde_plan_diag *diag, Fc... fc)
 {
+    static_assert(sizeof...(Fc) <= 1, "at most one PsForecast");
+    constexpr bool FC = sizeof...(Fc) == 1;
+
     __shared__ PsRows shw[TEAM ? 1 : kPsWaves];
     __shared__ PsBest best[TEAM ? kPsTeamMax : 1];
     __shared__ int sh_nb;
@@ -102,6 +118,7 @@ __global__ __launch_bounds__(TEAM ? kWave * kPsTeamMax : kWave * kPsWaves) void 
                 const float hl = 0.5f * st.len[g] + pl.margin, hw = 0.5f * st.wid[g] + pl.margin;
                 b = make_float4(st.x[g], st.y[g], ca, sa);
                 mo = make_float4((va * ca) * dt, (va * sa) * dt, hl, hw);
+                if constexpr (FC) mo.x = __int_as_float(a);       // (the slot whose forecast rows these are; box and (v c) dt are not read)
                 const float rr = (r0 + __builtin_sqrtf(hl * hl + hw * hw)) * 1.001f + 0.01f;   // (conservative: only a shortcut)
                 rj = rr * rr;
             }
@@ -155,9 +172,43 @@ __global__ __launch_bounds__(TEAM ? kWave * kPsTeamMax : kWave * kPsWaves) void 
     const float a1 = (v + a * dt < 0.0f) ? 0.0f : a, d1 = d;
     bool alive = active;
     int f = HT + 1;
+    // FC: this wavefront's rows of the step and the forecast rows of the next one (compacted rows lane and 64 + lane)
+    float4 *fbox = nullptr;
+    float4 fnext[2] = {make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
+    int fslot[2] = {0, 0};
+    const float4 *frow = nullptr;
+    if constexpr (FC) {
+        __shared__ float4 fc_box[TEAM ? kPsTeamMax : kPsWaves][TDE_MAX_AGENTS];
+        fbox = fc_box[wv];
+        const PsForecast fo = ps_forecast(fc...);
+        frow = fo.rows + (int64_t)e * fo.T * A;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int q = p * kWave + lane;
+            if (q < nb) {
+                fslot[p] = __float_as_int(sh.mot[q].x);
+                fnext[p] = frow[fslot[p]];
+            }
+        }
+    }
     // steps 1 .. H under the knots, steps H + 1 .. H + T under full braking with the steering of step H
     for (int h = 1; h <= HT; ++h) {
         if (!__ballot(alive)) break;
+        if constexpr (FC) {
+            // every lane of the wavefront is here, alive or not: stage the others' rows of step h, fetch those of step h + 1
+            wave_lds_fence();                                 // (the judge of step h - 1 has read its rows)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int q = p * kWave + lane;
+                if (q < nb) {
+                    float sj, cj;
+                    sincos_f32(fnext[p].z, sj, cj);
+                    fbox[q] = make_float4(fnext[p].x, fnext[p].y, cj, sj);
+                    if (h < HT) fnext[p] = frow[(int64_t)h * A + fslot[p]];
+                }
+            }
+            wave_lds_fence();
+        }
         const bool tail = h > H;                              // (wave-uniform)
         if (tail) {
             a = -TDE_PLAN_BOX_ACCEL;
@@ -192,8 +243,8 @@ __global__ __launch_bounds__(TEAM ? kWave * kPsTeamMax : kWave * kPsWaves) void 
             // (ii) the predicted boxes
             const float fh = (float)h;
             for (int j = 0; j < nb; ++j) {
-                const float4 b = sh.box[j], mo = sh.mot[j];
-                const float bx = b.x + fh * mo.x, by = b.y + fh * mo.y;
+                const float4 b = FC ? fbox[j] : sh.box[j], mo = sh.mot[j];
+                const float bx = FC ? b.x : b.x + fh * mo.x, by = FC ? b.y : b.y + fh * mo.y;
                 const float ex = bx - x, ey = by - y;
                 if (ex * ex + ey * ey > sh.rej2[j]) continue;
                 if (obb_overlap(x, y, cs, sn, hl0, hw0, bx, by, b.z, b.w, mo.z, mo.w)) { fail = true; break; }
@@ -302,8 +353,22 @@ __global__ __launch_bounds__(TEAM ? kWave * kPsTeamMax : kWave * kPsWaves) void 
 namespace tde_host {
 
 int launch_score_plans(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
-                       const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream)
+                       const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream,
+                       const float *forecast, int32_t forecast_T)
 {
+    if (forecast) {
+        const tde::PsForecast fc{reinterpret_cast<const float4 *>(forecast), forecast_T};
+        if (ps->N <= tde::kWave) {
+            const unsigned nb = (unsigned)((st->B + tde::kPsWaves - 1) / tde::kPsWaves);
+            tde::score_plans_kernel<false, tde::PsForecast><<<nb, tde::kWave * tde::kPsWaves, 0, (hipStream_t)stream>>>(
+                *cfg, *world, *st, *pl, *ps, only, cost, fail_step, action, diag, fc);
+        } else {
+            const unsigned nw = (unsigned)((ps->N + tde::kWave - 1) / tde::kWave);
+            tde::score_plans_kernel<true, tde::PsForecast><<<(unsigned)st->B, tde::kWave * nw, 0, (hipStream_t)stream>>>(
+                *cfg, *world, *st, *pl, *ps, only, cost, fail_step, action, diag, fc);
+        }
+        return launch_status("tde_score_plans_forecast");
+    }
     if (ps->N <= tde::kWave) {
         const unsigned nb = (unsigned)((st->B + tde::kPsWaves - 1) / tde::kPsWaves);
         tde::score_plans_kernel<false><<<nb, tde::kWave * tde::kPsWaves, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *pl, *ps, only, cost,

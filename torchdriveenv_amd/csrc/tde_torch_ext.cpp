@@ -361,7 +361,7 @@ class EnvHandle {
     void score_plans(const at::Tensor &seq, int64_t knot_len, int64_t tail, const at::Tensor &cost, const at::Tensor &fail_step,
                      int64_t horizon, double v_target, double margin, double w_progress, double w_speed, double w_steer,
                      const std::optional<at::Tensor> &only, const std::optional<at::Tensor> &action,
-                     const std::optional<at::Tensor> &diag, int64_t flags)
+                     const std::optional<at::Tensor> &diag, int64_t flags, const std::optional<at::Tensor> &forecast)
     {
         TORCH_CHECK(seq.dim() == 4 && seq.size(0) == state_.B && seq.size(3) == 2, "score_plans: seq must be [B, N, K, 2]");
         TORCH_CHECK(seq.is_contiguous(), "score_plans: seq must be contiguous (no copy of it is made)");
@@ -387,9 +387,35 @@ class EnvHandle {
         tde_plan_diag *d = diag ? static_cast<tde_plan_diag *>(const_cast<void *>(dev_ptr(*diag, at::kInt, (int64_t)state_.B * 4, "diag", dev_))) : nullptr;
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        if (forecast) {
+            // float32 [B, T, A, 4], contiguous: the others' (x, y, psi, v) per step (tde_score_plans_forecast)
+            const at::Tensor &fc = *forecast;
+            TORCH_CHECK(fc.dim() == 4 && fc.size(0) == state_.B && fc.size(2) == state_.A && fc.size(3) == 4,
+                        "score_plans: forecast must be [B, T, A, 4]");
+            TORCH_CHECK(fc.is_contiguous(), "score_plans: forecast must be contiguous (no copy of it is made)");
+            const float *pfc = static_cast<const float *>(dev_ptr(fc, at::kFloat, fc.numel(), "forecast", dev_));
+            check_rc(tde_score_plans_forecast(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d, pfc, (int32_t)fc.size(1),
+                                              c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                     "tde_score_plans_forecast");
+            return;
+        }
         check_rc(tde_score_plans(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d,
                                  c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
                  "tde_score_plans");
+    }
+
+    // tde_forecast_agents: out float32 [B, T, A, 4] = (x, y, psi, v) of every slot at each of the next T steps (rows of envs outside `only` untouched)
+    void forecast_agents(const at::Tensor &out, const std::optional<at::Tensor> &only, int64_t flags)
+    {
+        TORCH_CHECK(out.dim() == 4 && out.size(0) == state_.B && out.size(2) == state_.A && out.size(3) == 4,
+                    "forecast_agents: out must be [B, T, A, 4]");
+        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, out.numel(), "out", dev_)));
+        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        cfg_.flags = static_cast<uint32_t>(flags);
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_forecast_agents(&cfg_, &world_, &state_, (int32_t)out.size(1), m, p,
+                                     c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                 "tde_forecast_agents");
     }
 
     // tde_ego_infractions: float32 [B, 4] = the ego's (offroad, collision, overlap count, 0) magnitudes of the state as it is (gym_env.py:427-428)
@@ -566,7 +592,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
              py::arg("diag"), py::arg("flags"))
         .def("score_plans", &EnvHandle::score_plans, py::arg("seq"), py::arg("knot_len"), py::arg("tail"), py::arg("cost"),
              py::arg("fail_step"), py::arg("horizon"), py::arg("v_target"), py::arg("margin"), py::arg("w_progress"), py::arg("w_speed"),
-             py::arg("w_steer"), py::arg("only"), py::arg("action"), py::arg("diag"), py::arg("flags"))
+             py::arg("w_steer"), py::arg("only"), py::arg("action"), py::arg("diag"), py::arg("flags"), py::arg("forecast") = py::none())
+        .def("forecast_agents", &EnvHandle::forecast_agents, py::arg("out"), py::arg("only"), py::arg("flags"))
         .def_property_readonly("flags", &EnvHandle::flags)
         .def_property_readonly("num_envs", &EnvHandle::num_envs)
         .def_property_readonly("agents_per_env", &EnvHandle::agents_per_env);

@@ -644,6 +644,7 @@ class BatchedWaypointEnv:
                                   _box(-np.inf, np.inf, (self.vector_obs.dim if obs_mode == "vector" else 8,), np.float32))
         self._vobs = self._ray_dir = None
         self._plan_out = self._plan_diag = self._plan_struct = self._refine = None
+        self._plan_fc = self._plan_lat = None          # planner.predict == "route": the forecast buffer, the lattice as one-knot sequences
         if obs_mode == "vector":
             self._vobs = torch.zeros((self.num_envs, self.vector_obs.dim), dtype=torch.float32, device=self.torch_device)
             self._ray_dir = torch.from_numpy(self.vector_obs.ray_directions()).to(self.torch_device)
@@ -842,7 +843,9 @@ class BatchedWaypointEnv:
         """the sampling planner's action for every ego on the state as it is (tde_plan_action with self.planner) -> float32 [B, 2] on
         the device, usable as step(plan_actions()).  out: a float32 [B, 2] device tensor to write into (default: the env's own
         buffer, overwritten by the next call); only: uint8 [B] on the device, the other rows are left as they are; diag=True: returns
-        (actions, int32 [B, 4] rows of winner, fail_step, the cost's float32 bits, n_safe - n_safe == 0: no candidate is safe)."""
+        (actions, int32 [B, 4] rows of winner, fail_step, the cost's float32 bits, n_safe - n_safe == 0: no candidate is safe).
+        With planner.predict == "route" the other agents are where tde_forecast_agents puts them (one forecast per call, horizon + tail
+        steps) and the lattice is judged as one-knot sequences by tde_score_plans_forecast; "constant" (default) is the path as it was."""
         if out is None:
             if self._plan_out is None:
                 self._plan_out = torch.zeros((self.num_envs, 2), dtype=torch.float32, device=self.torch_device)
@@ -855,11 +858,28 @@ class BatchedWaypointEnv:
         if only is not None:
             only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         pl = self.planner
+        fc = None
+        if pl.predict == "route":
+            T = int(pl.horizon) + (int(self.plan_refine.tail) if self.plan_refine is not None else 0)
+            if self._plan_fc is None:
+                self._plan_fc = torch.zeros((self.num_envs, T, self.A, 4), dtype=torch.float32, device=self.torch_device)
+            fc = self._forecast(self._plan_fc, only)
         if self.plan_refine is not None:
             if self._plan_diag is None:
                 self._plan_diag = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.torch_device)
-            self._plan_refined(out, only, self._plan_diag)
+            self._plan_refined(out, only, self._plan_diag, fc)
             return (out, self._plan_diag) if diag else out
+        if fc is not None:
+            if self._plan_lat is None:
+                B, nc, dev = self.num_envs, pl.n_candidates, self.torch_device
+                acc, ste = pl.tables()
+                lat = np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(np.float32)      # [nc, 2]: candidate i = ia * n_s + is
+                self._plan_lat = {"seq": torch.from_numpy(lat).to(dev)[None, :, None, :].expand(B, nc, 1, 2).contiguous(),
+                                  "cost": torch.zeros((B, nc), dtype=torch.float32, device=dev),
+                                  "fail": torch.zeros((B, nc), dtype=torch.int32, device=dev)}
+            la = self._plan_lat
+            self._score_plans(la["seq"], int(pl.horizon), 0, only, la["cost"], la["fail"], out, d, fc)
+            return (out, d) if diag else out
         if self._h is not None:
             self._h.plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings], int(pl.horizon),
                                 float(pl.v_target), float(pl.margin), float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, d,
@@ -870,33 +890,67 @@ class BatchedWaypointEnv:
             ops.plan_action(self.tde_cfg, self.dworld, self.state, self._plan_struct, out, only, d)
         return (out, d) if diag else out
 
-    def _score_plans(self, seq, knot_len, tail, only, cost, fail_step, action, diag):
-        """tde_score_plans through the env's binding (arguments already checked)"""
+    def _score_plans(self, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast=None):
+        """tde_score_plans (forecast: tde_score_plans_forecast) through the env's binding (arguments already checked)"""
         pl = self.planner
         if self._h is not None:
             self._h.score_plans(seq, knot_len, tail, cost, fail_step, int(pl.horizon), float(pl.v_target), float(pl.margin),
-                                float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, action, diag, int(self.tde_cfg.flags))
+                                float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, action, diag, int(self.tde_cfg.flags),
+                                forecast)
         else:
             if self._plan_struct is None:
                 self._plan_struct = ops.planner_struct(pl)
-            ops.score_plans(self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step, action, diag)
+            ops.score_plans(self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step, action, diag,
+                            forecast)
 
-    def score_plans(self, seq, knot_len=None, tail=0, only=None):
+    def _forecast(self, out, only):
+        """tde_forecast_agents into `out` (float32 [B, T, A, 4]) through the env's binding (arguments already checked) -> out"""
+        if self._h is not None:
+            self._h.forecast_agents(out, only, int(self.tde_cfg.flags))
+        else:
+            ops.forecast_agents(self.tde_cfg, self.dworld, self.state, out.shape[1], only, out)
+        return out
+
+    def forecast_agents(self, T=None, only=None, out=None):
+        """where the environment's own rules put every other agent at each of the next T steps when nobody is in its cone
+        (tde_forecast_agents) -> float32 [B, T, A, 4] on the device: row [e, h - 1, j] = (x, y, psi, v) of slot j at environment step
+        steps[e] + h; zeros for the ego (slot 0) and absent slots.  Replayed agents follow their records, NPCs their routes, braking
+        for red lines and at the route's end; an agent that meets nobody does exactly this in the next T step() calls.  T: 1 .. 96
+        (None: the planner's horizon); only: uint8 [B], the other envs' rows are left as they are (zeros in a fresh buffer); out: a
+        float32 [B, T, A, 4] device tensor to write into (16 * B * T * A bytes the caller keeps).  score_plans(forecast=) takes the
+        result."""
+        T = int(self.planner.horizon) if T is None else T
+        if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
+            raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
+        shape = (self.num_envs, int(T), self.A, 4)
+        if out is None:
+            out = (torch.empty if only is None else torch.zeros)(shape, dtype=torch.float32, device=self.torch_device)
+        elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+        if only is not None:
+            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
+        return self._forecast(out, only)
+
+    def score_plans(self, seq, knot_len=None, tail=0, only=None, forecast=None):
         """how each of N action sequences per ego fares on the state as it is (tde_score_plans with self.planner's horizon, margin,
         v_target and weights) -> (cost float32 [B, N], fail_step int32 [B, N]) on the device.  seq: float32 [B, N, K, 2] device tensor
         of (acceleration, steering) knots, contiguous (raises otherwise: no copy is made); knot k holds knot_len steps (None:
         ceil(horizon / K)), the last one to the end of the horizon; then `tail` steps of full braking.  fail_step is the first step
         off the road, on a predicted box of another agent or on a red stop line, horizon + tail + 1 for a safe sequence; a lower cost
-        is better and any earlier failure costs more than any later one.  only: uint8 [B]; the other rows are not written."""
+        is better and any earlier failure costs more than any later one.  only: uint8 [B]; the other rows are not written.
+        forecast: a contiguous float32 [B, T >= horizon + tail, A, 4] device tensor of the other agents' (x, y, psi, v) per step -
+        forecast_agents()'s, or any predictor's in that layout - judged through tde_score_plans_forecast; None: constant velocity."""
         N, K, knot_len, tail = ops.check_plan_set(seq, self.num_envs, self.planner.horizon, knot_len, tail)
+        if forecast is not None:
+            ops.check_forecast(forecast, self.num_envs, self.A, int(self.planner.horizon) + tail)
         if only is not None:
             only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         cost = torch.zeros((self.num_envs, N), dtype=torch.float32, device=self.torch_device)
         fail_step = torch.zeros((self.num_envs, N), dtype=torch.int32, device=self.torch_device)
-        self._score_plans(seq, knot_len, tail, only, cost, fail_step, None, None)
+        self._score_plans(seq, knot_len, tail, only, cost, fail_step, None, None, forecast)
         return cost, fail_step
 
-    def _plan_refined(self, out, only, diag):
+    def _plan_refined(self, out, only, diag, forecast=None):
         """plan_actions() under self.plan_refine (config.PlanRefine states the rounds): device work only, no synchronisation"""
         pl, pr = self.planner, self.plan_refine
         B, nc, K, R = self.num_envs, pl.n_candidates, int(pr.knots), int(pr.rounds)
@@ -920,7 +974,7 @@ class BatchedWaypointEnv:
             self._refine = rf
         rf = self._refine
         knot_len, tail = -(-int(pl.horizon) // K), int(pr.tail)
-        self._score_plans(rf["seq0"], knot_len, tail, only, rf["cost0"], rf["fail0"], out, diag)
+        self._score_plans(rf["seq0"], knot_len, tail, only, rf["cost0"], rf["fail0"], out, diag, forecast)
         seqs = rf["seq0"]
         for r in range(R):
             # (rows outside `only` keep an older winner in diag: clamped, their candidates are built and never judged)
@@ -931,7 +985,7 @@ class BatchedWaypointEnv:
             for k in range(K):
                 cv[:, k, :, k, :] = torch.minimum(torch.maximum(w[:, k, None, :] + rf["delta"][r][None], rf["lo"]), rf["hi"])
             seqs = rf["cand"]
-            self._score_plans(seqs, knot_len, tail, only, rf["cost"], rf["fail"], out, diag)
+            self._score_plans(seqs, knot_len, tail, only, rf["cost"], rf["fail"], out, diag, forecast)
 
     def _render1(self, out, only=None):
         """single-frame raster of every (or the masked) view into `out`"""

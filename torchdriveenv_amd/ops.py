@@ -311,16 +311,55 @@ def check_plan_set(seq, B, H, knot_len=None, tail=0):
     return N, K, int(knot_len), int(tail)
 
 
-def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, action=None, diag=None):
+def check_forecast(forecast, B, A, need):
+    """the shape checks of a forecast that need no GPU: float32 [B, T, A, 4], contiguous (no silent copy), need <= T <=
+    FORECAST_MAX_T -> T"""
+    if not torch.is_tensor(forecast) or forecast.dtype != torch.float32:
+        raise ValueError("forecast must be a float32 torch tensor")
+    if forecast.dim() != 4 or forecast.shape[0] != B or forecast.shape[2] != A or forecast.shape[3] != 4:
+        raise ValueError(f"forecast must be [B={B}, T, A={A}, 4], got {tuple(forecast.shape)}")
+    if not forecast.is_contiguous():
+        raise ValueError("forecast must be contiguous (no copy of it is made)")
+    T = int(forecast.shape[1])
+    if not int(need) <= T <= _abi.FORECAST_MAX_T:
+        raise ValueError(f"forecast: T must be in [{int(need)}, {_abi.FORECAST_MAX_T}] (horizon + tail steps are read), got {T}")
+    return T
+
+
+def forecast_agents(cfg, dworld, state, T, only=None, out=None):
+    """tde_forecast_agents: (x, y, psi, v) of every slot at each of the next T steps when nobody is in its cone -> float32 [B, T, A,
+    4] on the device (zeros for the ego and absent slots).  only: uint8 [B], the other envs' rows of `out` are left as they are;
+    out: a float32 [B, T, A, 4] device tensor to write into.  Asynchronous."""
+    L = _lib.load()
+    dev = torch.device(state.device)
+    if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
+        raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
+    T = int(T)
+    if out is None:
+        out = (torch.empty if only is None else torch.zeros)((state.B, T, state.A, 4), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (state.B, T, state.A, 4):
+        raise ValueError(f"out must be [B={state.B}, T={T}, A={state.A}, 4], got {tuple(out.shape)}")
+    po = _chk(out, torch.float32, state.B * T * state.A * 4, "out", dev)
+    pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
+    _lib.check(_call(dev, L.tde_forecast_agents, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), T, pm, po,
+                     _lib.current_stream(dev)), "tde_forecast_agents")
+    return out
+
+
+def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, action=None, diag=None,
+                forecast=None):
     """tde_score_plans: how each of N action sequences per env fares on the state as it is -> (cost float32 [B, N], fail_step int32
     [B, N]) on the device.  seq: float32 [B, N, K, 2] device tensor of (acceleration, steering) knots, contiguous; knot k holds for
     knot_len steps (None: ceil(horizon / K)), then `tail` steps of full braking; planner: config.Planner (or its tde_planner) for
     the horizon, margin, v_target and the weights.  fail_step == horizon + tail + 1: the sequence is safe.  only: uint8 [B], the
     other rows of every output are left as they are; action float32 [B, 2] / diag int32 [B, 4]: optional, receive the winner's first
-    action and its tde_plan_diag row.  Asynchronous."""
+    action and its tde_plan_diag row.  forecast: float32 [B, T >= horizon + tail, A, 4] device tensor, contiguous - the other agents'
+    (x, y, psi, v) per step (tde_score_plans_forecast; tde_forecast_agents' layout); None: tde_score_plans' constant velocity.
+    Asynchronous."""
     L = _lib.load()
     ps = planner if isinstance(planner, _abi.TdePlanner) else planner_struct(planner)
     N, K, knot_len, tail = check_plan_set(seq, state.B, ps.horizon, knot_len, tail)
+    fT = check_forecast(forecast, state.B, state.A, ps.horizon + tail) if forecast is not None else 0
     dev = torch.device(state.device)
     if cost is None:
         cost = torch.empty((state.B, N), dtype=torch.float32, device=dev)
@@ -332,6 +371,11 @@ def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=No
     pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
     pa = _chk(action, torch.float32, state.B * 2, "action", dev, optional=True)
     pd = _chk(diag, torch.int32, state.B * 4, "diag", dev, optional=True)
+    if forecast is not None:
+        pfc = _chk(forecast, torch.float32, state.B * fT * state.A * 4, "forecast", dev)
+        _lib.check(_call(dev, L.tde_score_plans_forecast, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps),
+                         C.byref(st), pm, pc, pf, pa, pd, pfc, fT, _lib.current_stream(dev)), "tde_score_plans_forecast")
+        return cost, fail_step
     _lib.check(_call(dev, L.tde_score_plans, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps), C.byref(st), pm, pc,
                      pf, pa, pd, _lib.current_stream(dev)), "tde_score_plans")
     return cost, fail_step
