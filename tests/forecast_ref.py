@@ -1,11 +1,10 @@
-"""float32 numpy restatement of tde_forecast_agents and tde_score_plans_forecast (include/tde_hip.h), the checker of the forecast
-tests: test infrastructure only, nothing in the package imports it.  Written like tests/planner_ref.py and tests/plan_set_ref.py and
-built on their helpers (obb_overlap, box_offroad, ordered, red_mask; the oracle's sincosf and bicycle): every expression is the
-header's, in float32.  Also the hand-made world of the environment-as-oracle tests (oracle_world), shared by the CPU and GPU tests."""
+"""float32 numpy restatement of tde_forecast_agents (include/tde_hip.h), the checker of the forecast tests: test infrastructure only,
+nothing in the package imports it.  Written like tests/planner_ref.py and tests/plan_set_ref.py (red_mask; the oracle's sincosf and
+bicycle): every expression is the header's, in float32.  tde_score_plans_forecast is restated by plan_set_ref.score(forecast=): the one
+judge, given these rows (forecast, constant_velocity) for the others' boxes; plan_routed puts the two together.  Also the hand-made world of the environment-as-oracle tests (oracle_world), shared by the CPU and GPU tests."""
 import numpy as np
 
 from oracle import oracle
-from tests.planner_ref import box_offroad, obb_overlap, ordered
 from tests.vector_obs_ref import red_mask
 from torchdriveenv_amd import _abi
 
@@ -123,163 +122,16 @@ def constant_velocity(cfg, world, st, T):
     return out
 
 
-def score(cfg, world, st, pl, seq, fc, knot_len=None, tail=0, only=None, cost=None, fail_step=None, out=None, diag=None):
-    """what tde_score_plans_forecast writes (the dict of plan_set_ref.score without `cause`): tde_score_plans' specification with the
-    box of present slot j at step h = (x, y, c, s, 0.5f * len_j + margin, 0.5f * wid_j + margin), (x, y, psi) = fc[e][h - 1][j]"""
-    B, A = len(st["scn"]), world.A
-    seq = np.asarray(seq, f32)
-    fc = np.asarray(fc, f32)
-    N, K = seq.shape[1], seq.shape[2]
-    H, T = int(pl.horizon), int(tail)
-    L = -(-H // K) if knot_len is None else int(knot_len)
-    HT = H + T
-    assert fc.shape[0] == B and fc.shape[2] == A and fc.shape[3] == 4 and HT <= fc.shape[1] <= _abi.FORECAST_MAX_T
-    r_cost = np.zeros((B, N), f32) if cost is None else np.array(cost, f32, copy=True).reshape(B, N)
-    r_f = np.zeros((B, N), np.int32) if fail_step is None else np.array(fail_step, np.int32, copy=True).reshape(B, N)
-    act = np.zeros((B, 2), f32) if out is None else np.array(out, f32, copy=True).reshape(B, 2)
-    dg = np.zeros(B, _abi.PLAN_DIAG_DTYPE) if diag is None else np.array(diag, copy=True).view(_abi.PLAN_DIAG_DTYPE).reshape(B)
-    res = dict(cost=r_cost, f=r_f, action=act, diag=dg)
-    envs = np.array([e for e in range(B) if only is None or only[e]], np.int64)
-    E = len(envs)
-    if E == 0:
-        return res
-    dt, margin = f32(cfg.dt), f32(pl.margin)
-    vt, wp_, ws_, wd_ = f32(pl.v_target), f32(pl.w_progress), f32(pl.w_speed), f32(pl.w_steer)
-    rr = f32(cfg.reach_radius)
-    box_a, box_d = f32(_abi.PLAN_BOX_ACCEL), f32(_abi.PLAN_BOX_STEER)
-    X, Y, P, V, LN, WD, LR = (np.asarray(st[n], f32).reshape(B, A)[envs] for n in ("x", "y", "psi", "v", "len", "wid", "lr"))
-    pres = np.asarray(st["present"]).reshape(B, A)[envs] != 0
-    scn_t, mp, wp = world.arrays["scn"], world.arrays["maps"], world.arrays["wp_xy"]
-    sidx = np.asarray(st["scn"])[envs].astype(np.int64)
-    maps = scn_t["map"][sidx].astype(np.int32)
-    wp_n = scn_t["wp_n"][sidx].astype(np.int64)
-    steps = np.asarray(st["steps"])[envs].astype(np.int64)
-    sq = seq[envs]
-    KA = np.fmin(np.fmax(sq[..., 0], -box_a), box_a).astype(f32)       # [E, N, K]; a NaN becomes the lower bound
-    KD = np.fmin(np.fmax(sq[..., 1], -box_d), box_d).astype(f32)
-    rep = lambda c: np.repeat(c[:, None], N, 1).astype(c.dtype)        # noqa: E731
-    x, y, psi, v = rep(X[:, 0]), rep(Y[:, 0]), rep(P[:, 0]), rep(V[:, 0])
-    lr0 = rep(LR[:, 0])
-    len0, wid0 = rep(LN[:, 0]), rep(WD[:, 0])
-    hl0, hw0 = f32(0.5) * len0, f32(0.5) * wid0
-    mapc = np.repeat(maps[:, None], N, 1)
-    hlo, hwo = f32(0.5) * LN[:, 1:] + margin, f32(0.5) * WD[:, 1:] + margin
-    po = pres[:, 1:]
-    FC = fc[envs]
-    ti = rep(np.asarray(st["target_idx"])[envs].astype(np.int64))
-    wpn = rep(wp_n)
-    sc_ = rep(sidx)
-    NW = wp.shape[1]
-
-    def target(ti_):
-        j = np.clip(ti_, 0, NW - 1)
-        return wp[sc_, j, 0].astype(f32), wp[sc_, j, 1].astype(f32)
-
-    def dist(wx_, wy_, x_, y_):
-        dx, dy = wx_ - x_, wy_ - y_
-        return np.sqrt(dx * dx + dy * dy)
-
-    wx, wy = target(ti)
-    has = ti < wpn
-    dp = np.where(has, dist(wx, wy, x, y), f32(0)).astype(f32)
-    gain, sv, dm = np.zeros((E, N), f32), np.zeros((E, N), f32), np.zeros((E, N), f32)
-    a1 = np.where(v + KA[..., 0] * dt < f32(0), f32(0), KA[..., 0]).astype(f32)
-    d1 = KD[..., 0].copy()
-    alive = np.ones((E, N), bool)
-    f = np.full((E, N), HT + 1, np.int64)
-    lights_on = bool(cfg.flags & _abi.F_TRAFFIC_LIGHTS)
-    stop = world.arrays["stoplines"]
-    d = KD[..., 0]
-    for h in range(1, HT + 1):
-        if not alive.any():
-            break
-        in_tail = h > H
-        if in_tail:
-            a = np.full((E, N), -box_a, f32)
-            alive &= ~(v + a * dt < f32(0))
-            if not alive.any():
-                break
-        else:
-            k = min((h - 1) // L, K - 1)
-            a, d = KA[..., k], KD[..., k]
-            dm = np.where(alive, np.fmax(dm, d * d), dm).astype(f32)
-        ah = np.where(v + a * dt < f32(0), f32(0), a).astype(f32)
-        ix = np.flatnonzero(alive.ravel())
-        xs, ys, ps, vs = (np.ascontiguousarray(q.ravel()[ix]) for q in (x, y, psi, v))
-        oracle.kinematics_step(xs, ys, ps, vs, np.ascontiguousarray(lr0.ravel()[ix]), np.ones(len(ix), np.uint8),
-                               np.ascontiguousarray(np.stack([ah.ravel()[ix], d.ravel()[ix]], -1)), float(dt))
-        for q, qs in ((x, xs), (y, ys), (psi, ps), (v, vs)):
-            q.ravel()[ix] = qs
-        sn, cs = oracle.sincosf(psi.ravel())
-        sn, cs = sn.reshape(E, N), cs.reshape(E, N)
-        off = np.zeros((E, N), bool)
-        off.ravel()[ix] = box_offroad(cfg, world, mapc.ravel()[ix], xs, ys, ps, len0.ravel()[ix], wid0.ravel()[ix])
-        # Others: the forecast rows of step h
-        bx, by = FC[:, h - 1, 1:, 0], FC[:, h - 1, 1:, 1]
-        So, Co = oracle.sincosf(np.ascontiguousarray(FC[:, h - 1, 1:, 2]).ravel())
-        So, Co = So.reshape(E, A - 1), Co.reshape(E, A - 1)
-        hit = np.zeros((E, N), bool)
-        for j in range(A - 1):
-            if not po[:, j].any():
-                continue
-            hj = obb_overlap(x, y, cs, sn, hl0, hw0, bx[:, j, None], by[:, j, None], Co[:, j, None], So[:, j, None], hlo[:, j, None],
-                             hwo[:, j, None])
-            hit |= hj & po[:, j, None]
-        red = np.zeros((E, N), bool)
-        if lights_on:
-            for i in range(E):
-                m = mp[maps[i]]
-                n_stop = int(m["n_stop"])
-                if n_stop <= 0 or int(m["cycle_steps"]) <= 0:
-                    continue
-                rm = red_mask(world, maps[i], steps[i] + h)
-                lines = stop[int(m["stop_base"]):int(m["stop_base"]) + n_stop]
-                lines = lines[((rm >> (lines["light"].astype(np.int64) & 31)) & 1) != 0]
-                if len(lines):
-                    hr = obb_overlap(x[i][:, None], y[i][:, None], cs[i][:, None], sn[i][:, None], hl0[i][:, None], hw0[i][:, None],
-                                     lines["x"][None], lines["y"][None], lines["c"][None], lines["s"][None], lines["hl"][None],
-                                     lines["hw"][None])
-                    red[i] = hr.any(1)
-        fail = off | hit | red
-        f[alive & fail] = h
-        alive &= ~fail
-        if in_tail:
-            continue
-        has = alive & (ti < wpn)
-        dn = dist(wx, wy, x, y)
-        gain = np.where(has, gain + (dp - dn), gain).astype(f32)
-        dp = np.where(has, dn, dp).astype(f32)
-        adv = has & (dn < rr)
-        ti = ti + adv
-        nwx, nwy = target(ti)
-        more = adv & (ti < wpn)
-        wx, wy = np.where(more, nwx, wx).astype(f32), np.where(more, nwy, wy).astype(f32)
-        dp = np.where(more, dist(wx, wy, x, y), dp).astype(f32)
-        ev = v - np.where(ti < wpn, vt, f32(0)).astype(f32)
-        sv = np.where(alive, sv + ev * ev, sv).astype(f32)
-    run = (ws_ * sv + wd_ * dm) - wp_ * gain
-    c = ((HT + 1 - f).astype(f32) * f32(_abi.PLAN_FAIL_UNIT) +
-         np.fmin(np.fmax(run + f32(_abi.PLAN_RUN_BIAS), f32(0)), f32(_abi.PLAN_RUN_MAX))).astype(f32)
-    key = (ordered(c.view(np.uint32)).astype(np.uint64) << np.uint64(32)) | np.arange(N)[None].astype(np.uint64)
-    win = key.argmin(1)
-    r = np.arange(E)
-    r_cost[envs], r_f[envs] = c, f
-    act[envs, 0], act[envs, 1] = a1[r, win], d1[r, win]
-    dg["winner"][envs], dg["fail_step"][envs], dg["cost"][envs] = win, f[r, win], c[r, win]
-    dg["n_safe"][envs] = (f == HT + 1).sum(1)
-    return res
-
-
 def plan_routed(cfg, world, st, pl, tail=0, only=None, out=None, diag=None):
     """BatchedWaypointEnv.plan_actions() under Planner(predict="route") without refinement rounds -> (action [B, 2], diag [B]): the
     lattice as one-knot sequences judged on tde_forecast_agents' rows of horizon + tail steps"""
-    from tests.plan_set_ref import lattice
+    from tests.plan_set_ref import lattice, score
 
     B = len(st["scn"])
     lat = lattice(pl)
     seq = np.ascontiguousarray(np.broadcast_to(lat[None, :, None, :], (B, len(lat), 1, 2)))
     fc = forecast(cfg, world, st, int(pl.horizon) + int(tail), only=only)
-    res = score(cfg, world, st, pl, seq, fc, int(pl.horizon), tail, only=only, out=out, diag=diag)
+    res = score(cfg, world, st, pl, seq, int(pl.horizon), tail, only=only, out=out, diag=diag, forecast=fc)
     return res["action"], res["diag"]
 
 

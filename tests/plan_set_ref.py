@@ -1,13 +1,12 @@
-"""float32 numpy restatement of tde_score_plans (include/tde_hip.h) and of the refinement rounds of config.PlanRefine, the checker
-of the plan-set tests: test infrastructure only, nothing in the package imports it.  Built on the helpers of tests/planner_ref.py
-(obb_overlap, box_offroad, ordered; the oracle's sincosf, bicycle and brute-force road predicate), and written the same way: every
-expression is the header's, in float32.  Also the module-level tables of inputs that the CPU tests prove meaningful and the GPU
-tests then run (CASES, tail_corridor)."""
+"""float32 numpy restatement of tde_score_plans and tde_score_plans_forecast (include/tde_hip.h; one `score`, forecast= chooses) and
+of the refinement rounds of config.PlanRefine, the checker of the plan-set and forecast tests: test infrastructure only, nothing in the
+package imports it.  Built on the helpers of tests/planner_ref.py (obb_overlap, box_offroad, ordered, red_hits; the oracle's sincosf,
+bicycle and brute-force road predicate), and written the same way: every expression is the header's, in float32.  Also the
+module-level tables of inputs that the CPU tests prove meaningful and the GPU tests then run (CASES, tail_corridor)."""
 import numpy as np
 
 from oracle import oracle
-from tests.planner_ref import box_offroad, obb_overlap, ordered
-from tests.vector_obs_ref import red_mask
+from tests.planner_ref import box_offroad, obb_overlap, ordered, red_hits
 from torchdriveenv_amd import _abi
 
 f32 = np.float32
@@ -20,9 +19,12 @@ def lattice(pl):
     return np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(f32)
 
 
-def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, out=None, diag=None):
+def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, out=None, diag=None, forecast=None):
     """what tde_score_plans writes -> dict(cost float32 [B, N], f int32 [B, N], action float32 [B, 2], diag PLAN_DIAG_DTYPE [B],
-    cause int8 [B, N]); rows with only[e] == 0 are those of `cost` / `fail_step` / `out` / `diag` (zeros without them)."""
+    cause int8 [B, N]); rows with only[e] == 0 are those of `cost` / `fail_step` / `out` / `diag` (zeros without them).  forecast (float32
+    [B, T, A, 4], horizon + tail <= T <= FORECAST_MAX_T): what tde_score_plans_forecast writes, the same specification with the box of
+    present slot j at step h = (x, y, c, s, 0.5f * len_j + margin, 0.5f * wid_j + margin), (x, y, psi) = forecast[e][h - 1][j]; without
+    one the others move on the constant-velocity line from the state."""
     B, A = len(st["scn"]), world.A
     seq = np.asarray(seq, f32)
     assert seq.ndim == 4 and seq.shape[0] == B and seq.shape[3] == 2
@@ -30,6 +32,8 @@ def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, 
     H, T = int(pl.horizon), int(tail)
     L = -(-H // K) if knot_len is None else int(knot_len)
     HT = H + T
+    fs = np.shape(forecast)
+    assert forecast is None or (fs[0] == B and fs[2:] == (A, 4) and HT <= fs[1] <= _abi.FORECAST_MAX_T)
     r_cost = np.zeros((B, N), f32) if cost is None else np.array(cost, f32, copy=True).reshape(B, N)
     r_f = np.zeros((B, N), np.int32) if fail_step is None else np.array(fail_step, np.int32, copy=True).reshape(B, N)
     act = np.zeros((B, 2), f32) if out is None else np.array(out, f32, copy=True).reshape(B, 2)
@@ -46,7 +50,7 @@ def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, 
     box_a, box_d = f32(_abi.PLAN_BOX_ACCEL), f32(_abi.PLAN_BOX_STEER)
     X, Y, P, V, LN, WD, LR = (np.asarray(st[n], f32).reshape(B, A)[envs] for n in ("x", "y", "psi", "v", "len", "wid", "lr"))
     pres = np.asarray(st["present"]).reshape(B, A)[envs] != 0
-    scn_t, mp, wp = world.arrays["scn"], world.arrays["maps"], world.arrays["wp_xy"]
+    scn_t, wp = world.arrays["scn"], world.arrays["wp_xy"]
     sidx = np.asarray(st["scn"])[envs].astype(np.int64)
     maps = scn_t["map"][sidx].astype(np.int32)
     wp_n = scn_t["wp_n"][sidx].astype(np.int64)
@@ -61,11 +65,23 @@ def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, 
     len0, wid0 = rep(LN[:, 0]), rep(WD[:, 0])
     hl0, hw0 = f32(0.5) * len0, f32(0.5) * wid0
     mapc = np.repeat(maps[:, None], N, 1)
-    So, Co = oracle.sincosf(P[:, 1:].ravel())
-    So, Co = So.reshape(E, A - 1), Co.reshape(E, A - 1)
-    ux, uy = (V[:, 1:] * Co) * dt, (V[:, 1:] * So) * dt
     hlo, hwo = f32(0.5) * LN[:, 1:] + margin, f32(0.5) * WD[:, 1:] + margin
     po = pres[:, 1:]
+    # boxes(h) -> (bx, by, Co, So), each [E, A - 1]: the others' centres and headings at step h
+    if forecast is None:
+        So0, Co0 = oracle.sincosf(P[:, 1:].ravel())
+        So0, Co0 = So0.reshape(E, A - 1), Co0.reshape(E, A - 1)
+        ux, uy = (V[:, 1:] * Co0) * dt, (V[:, 1:] * So0) * dt
+
+        def boxes(h):
+            fh = f32(h)
+            return X[:, 1:] + fh * ux, Y[:, 1:] + fh * uy, Co0, So0
+    else:
+        FC = np.asarray(forecast, f32)[envs]
+
+        def boxes(h):
+            So_, Co_ = oracle.sincosf(np.ascontiguousarray(FC[:, h - 1, 1:, 2]).ravel())
+            return FC[:, h - 1, 1:, 0], FC[:, h - 1, 1:, 1], Co_.reshape(E, A - 1), So_.reshape(E, A - 1)
     ti = rep(np.asarray(st["target_idx"])[envs].astype(np.int64))
     wpn = rep(wp_n)
     sc_ = rep(sidx)
@@ -89,7 +105,6 @@ def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, 
     f = np.full((E, N), HT + 1, np.int64)
     cause = np.zeros((E, N), np.int8)
     lights_on = bool(cfg.flags & _abi.F_TRAFFIC_LIGHTS)
-    stop = world.arrays["stoplines"]
     d = KD[..., 0]
     for h in range(1, HT + 1):
         if not alive.any():
@@ -115,8 +130,7 @@ def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, 
         sn, cs = sn.reshape(E, N), cs.reshape(E, N)
         off = np.zeros((E, N), bool)
         off.ravel()[ix] = box_offroad(cfg, world, mapc.ravel()[ix], xs, ys, ps, len0.ravel()[ix], wid0.ravel()[ix])
-        fh = f32(h)
-        bx, by = X[:, 1:] + fh * ux, Y[:, 1:] + fh * uy
+        bx, by, Co, So = boxes(h)
         hit = np.zeros((E, N), bool)
         for j in range(A - 1):                                          # (slot by slot: [E, N, A - 1] temporaries are large at N = 1024)
             if not po[:, j].any():
@@ -124,21 +138,7 @@ def score(cfg, world, st, pl, seq, knot_len=None, tail=0, only=None, cost=None, 
             hj = obb_overlap(x, y, cs, sn, hl0, hw0, bx[:, j, None], by[:, j, None], Co[:, j, None], So[:, j, None], hlo[:, j, None],
                              hwo[:, j, None])
             hit |= hj & po[:, j, None]
-        red = np.zeros((E, N), bool)
-        if lights_on:
-            for i in range(E):
-                m = mp[maps[i]]
-                n_stop = int(m["n_stop"])
-                if n_stop <= 0 or int(m["cycle_steps"]) <= 0:
-                    continue
-                rm = red_mask(world, maps[i], steps[i] + h)
-                lines = stop[int(m["stop_base"]):int(m["stop_base"]) + n_stop]
-                lines = lines[((rm >> (lines["light"].astype(np.int64) & 31)) & 1) != 0]
-                if len(lines):
-                    hr = obb_overlap(x[i][:, None], y[i][:, None], cs[i][:, None], sn[i][:, None], hl0[i][:, None], hw0[i][:, None],
-                                     lines["x"][None], lines["y"][None], lines["c"][None], lines["s"][None], lines["hl"][None],
-                                     lines["hw"][None])
-                    red[i] = hr.any(1)
+        red = red_hits(world, maps, steps, h, x, y, cs, sn, hl0, hw0) if lights_on else np.zeros((E, N), bool)
         fail = off | hit | red
         died = alive & fail
         f[died] = h
@@ -225,6 +225,14 @@ def random_knots(rng, B, N, K, wild=False):
     return seq
 
 
+def calm_knots(rng, seq):
+    """`seq` [B, N, K, 2] with a third of its sequences overwritten in place by ones that brake gently and steer little, so that some
+    are safe whatever the scene"""
+    calm = rng.random(seq.shape[:2]) < 0.35
+    seq[calm] = np.stack([rng.uniform(-1.0, 0.1, seq[calm].shape[:-1]), rng.uniform(-0.02, 0.02, seq[calm].shape[:-1])], -1).astype(f32)
+    return seq
+
+
 # name -> dict(world, B, seed, N, K, knot_len, tail, H, lights, steps, edge, squared, only, wild): the parametrised inputs of GPU tests
 # 2 and 3.  H = 32 throughout but where stated.  knot_len: K * knot_len > H cuts the last knot short, K * knot_len < H stretches it.
 CASES = {
@@ -292,10 +300,7 @@ def case_inputs(name, small_world=None):
         hs["x"][::A], hs["y"][::A] = x0.astype(f32), y0.astype(f32)
         hs["psi"][:2 * n * A:A] = rng.uniform(-3.14, 3.14, 2 * n).astype(f32)
     pl = Planner(horizon=c.get("H", 32))
-    seq = random_knots(rng, B, c["N"], c["K"], wild=bool(c.get("wild")))
-    # a fifth of the sequences brake gently and steer little, so that some are safe whatever the scene
-    calm = rng.random((B, c["N"])) < 0.35
-    seq[calm] = np.stack([rng.uniform(-1.0, 0.1, seq[calm].shape[:-1]), rng.uniform(-0.02, 0.02, seq[calm].shape[:-1])], -1).astype(f32)
+    seq = calm_knots(rng, random_knots(rng, B, c["N"], c["K"], wild=bool(c.get("wild"))))
     only = (rng.random(B) < 0.5).astype(np.uint8) if c.get("only") else None
     return cfg, world, hs, pl, seq, c["knot_len"], c["tail"], only
 

@@ -4,7 +4,8 @@ a config.Planner; every expression is the header's, in float32 (numpy rounds onc
 through the oracle's sincosf, the trajectories through the oracle's bicycle (kinematics_step: tde_oracle_bicycle per row), the road
 predicate through the oracle's brute force over the map's triangles (compute_offroad of the ego's box; point_near_mesh per corner
 under the squared reading).  The overlap test is tde_device.h's obb_overlap written out on arrays (obb_overlap below; the CPU tests
-hold it against oracle.obb_overlap)."""
+hold it against oracle.obb_overlap).  tests/plan_set_ref.py restates the plan judge on these helpers; of `plan` itself it shares
+the stop-line walk (red_hits) and nothing else, so that the tests which hold the two equal compare two statements."""
 import numpy as np
 
 from oracle import oracle
@@ -57,6 +58,27 @@ def ordered(bits):
     return np.where(b >> np.uint32(31), ~b, b ^ np.uint32(0x80000000)).astype(np.uint32)
 
 
+def red_hits(world, maps, steps, h, x, y, cs, sn, hl0, hw0):
+    """the stop-line walk of step h -> bool [E, n]: box (x, y, cs, sn, hl0, hw0)[i][c] overlaps a stop line of map maps[i] whose light
+    is red at step steps[i] + h; maps without stop lines or without a cycle are skipped"""
+    mp, stop = world.arrays["maps"], world.arrays["stoplines"]
+    red = np.zeros(x.shape, bool)
+    for i in range(len(maps)):
+        m = mp[maps[i]]
+        n_stop = int(m["n_stop"])
+        if n_stop <= 0 or int(m["cycle_steps"]) <= 0:
+            continue
+        rm = red_mask(world, maps[i], steps[i] + h)
+        lines = stop[int(m["stop_base"]):int(m["stop_base"]) + n_stop]
+        lines = lines[((rm >> (lines["light"].astype(np.int64) & 31)) & 1) != 0]
+        if len(lines):
+            hit = obb_overlap(x[i][:, None], y[i][:, None], cs[i][:, None], sn[i][:, None], hl0[i][:, None], hw0[i][:, None],
+                              lines["x"][None], lines["y"][None], lines["c"][None], lines["s"][None], lines["hl"][None],
+                              lines["hw"][None])
+            red[i] = hit.any(1)
+    return red
+
+
 def plan(cfg, world, st, pl, only=None, out=None, diag=None, detail=False):
     """what tde_plan_action writes: (action float32 [B, 2], diag PLAN_DIAG_DTYPE [B]); rows with only[e] == 0 are those of `out` /
     `diag` (zeros without them).  detail=True: also (f int [E, nc], cost float32 [E, nc]) of the planned envs."""
@@ -75,7 +97,7 @@ def plan(cfg, world, st, pl, only=None, out=None, diag=None, detail=False):
     rr = f32(cfg.reach_radius)
     X, Y, P, V, LN, WD, LR = (np.asarray(st[n], f32).reshape(B, A)[envs] for n in ("x", "y", "psi", "v", "len", "wid", "lr"))
     pres = np.asarray(st["present"]).reshape(B, A)[envs] != 0
-    scn_t, mp, wp = world.arrays["scn"], world.arrays["maps"], world.arrays["wp_xy"]
+    scn_t, wp = world.arrays["scn"], world.arrays["wp_xy"]
     sidx = np.asarray(st["scn"])[envs].astype(np.int64)
     maps = scn_t["map"][sidx].astype(np.int32)
     wp_n = scn_t["wp_n"][sidx].astype(np.int64)
@@ -118,7 +140,6 @@ def plan(cfg, world, st, pl, only=None, out=None, diag=None, detail=False):
     alive = np.ones((E, nc), bool)
     f = np.full((E, nc), H + 1, np.int64)
     lights_on = bool(cfg.flags & _abi.F_TRAFFIC_LIGHTS)
-    stop = world.arrays["stoplines"]
     for h in range(1, H + 1):
         if not alive.any():
             break
@@ -141,19 +162,7 @@ def plan(cfg, world, st, pl, only=None, out=None, diag=None, detail=False):
         fail |= (hit & po[:, None, :]).any(2)
         # (iii) red lines
         if lights_on:
-            for i in range(E):
-                m = mp[maps[i]]
-                n_stop = int(m["n_stop"])
-                if n_stop <= 0 or int(m["cycle_steps"]) <= 0:
-                    continue
-                rm = red_mask(world, maps[i], steps[i] + h)
-                lines = stop[int(m["stop_base"]):int(m["stop_base"]) + n_stop]
-                lines = lines[((rm >> (lines["light"].astype(np.int64) & 31)) & 1) != 0]
-                if len(lines):
-                    hit = obb_overlap(x[i][:, None], y[i][:, None], cs[i][:, None], sn[i][:, None], hl0[i][:, None], hw0[i][:, None],
-                                      lines["x"][None], lines["y"][None], lines["c"][None], lines["s"][None], lines["hl"][None],
-                                      lines["hw"][None])
-                    fail[i] |= hit.any(1)
+            fail |= red_hits(world, maps, steps, h, x, y, cs, sn, hl0, hw0)
         died = alive & fail
         f[died] = h
         alive &= ~fail

@@ -1,7 +1,8 @@
-"""CPU checks of tde_forecast_agents and tde_score_plans_forecast: known answers of the numpy restatement (tests/forecast_ref.py), the
-restatement held against the C oracle's step on a hand-made world in which no agent ever enters another's cone (the environment is
-the oracle: bit for bit, every step), the constant-velocity forecast giving plan_set_ref's bits, the new prototypes and constants
-against the header, and the argument checks that need no GPU."""
+"""CPU checks of tde_forecast_agents and tde_score_plans_forecast: known answers of the numpy restatement (tests/forecast_ref.py; the
+judge: plan_set_ref.score(forecast=)), the restatement held against the C oracle's step on a hand-made world in which no agent ever
+enters another's cone (the environment is the oracle: bit for bit, every step), the judge's forecast branch on a constant-velocity
+forecast giving its line branch's bits, the new prototypes and constants against the header, and the argument checks that need no
+GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -140,14 +141,14 @@ def test_constant_velocity_forecast_gives_plan_set_refs_bits(small_world, N, K, 
     pl = Planner()
     seq = S.random_knots(np.random.default_rng(5), 12, N, K)
     want = S.score(cfg, small_world, hs, pl, seq, None, tail)
-    got = Fr.score(cfg, small_world, hs, pl, seq, Fr.constant_velocity(cfg, small_world, hs, pl.horizon + tail), None, tail)
+    got = S.score(cfg, small_world, hs, pl, seq, None, tail, forecast=Fr.constant_velocity(cfg, small_world, hs, pl.horizon + tail))
     assert np.array_equal(got["f"], want["f"]) and np.array_equal(_bits(got["cost"]), _bits(want["cost"]))
     assert np.array_equal(_bits(got["action"]), _bits(want["action"])) and got["diag"].tobytes() == want["diag"].tobytes()
     assert (want["f"] < pl.horizon + tail + 1).any() and (want["f"] == pl.horizon + tail + 1).any()
     # and a forecast that differs is read: the others parked far away take every box failure with them
     away = Fr.constant_velocity(cfg, small_world, hs, pl.horizon + tail)
     away[..., 0] += f32(1e4)
-    assert (Fr.score(cfg, small_world, hs, pl, seq, away, None, tail)["f"] >= want["f"]).all()
+    assert (S.score(cfg, small_world, hs, pl, seq, None, tail, forecast=away)["f"] >= want["f"]).all()
 
 
 def test_real_forecasts_change_the_verdicts(small_world):

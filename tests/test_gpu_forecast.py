@@ -1,18 +1,18 @@
-"""tde_forecast_agents and tde_score_plans_forecast on the GPU against their numpy restatement (tests/forecast_ref.py), bit for bit and
-through both bindings: the forecast kernel at T = 96 on the junction, town and 128-slot worlds, from fresh and from driven states;
-the environment as the oracle (32 steps of the hand-made world of tests/test_forecast_cpu.py leave what the forecast said); the
-judge on a constant-velocity forecast against tde_score_plans; the judge on real forecasts against the restatement; plan_actions()
-under each Planner.predict; and graph capture."""
+"""tde_forecast_agents and tde_score_plans_forecast on the GPU against their numpy restatements (tests/forecast_ref.py; the judge:
+plan_set_ref.score(forecast=)), bit for bit and through both bindings: the forecast kernel at T = 96 on the junction, town and
+128-slot worlds, from fresh and from driven states; the environment as the oracle (32 steps of the hand-made world of
+tests/test_forecast_cpu.py leave what the forecast said); the judge on a constant-velocity forecast against tde_score_plans; the judge
+on real forecasts against the restatement; plan_actions() under each Planner.predict; and graph capture."""
 import numpy as np
 import pytest
 import torch
 
 from tests import forecast_ref as Fr
 from tests import plan_set_ref as S
+from tests.plan_gpu_util import bits, check_score_plans, on_device
 from torchdriveenv_amd import _abi, _ext, ops
 from torchdriveenv_amd.config import EnvConfig, Planner, PlanRefine
 from torchdriveenv_amd.env import BatchedWaypointEnv
-from torchdriveenv_amd.state import EnvState
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -20,10 +20,6 @@ T_MAX = _abi.FORECAST_MAX_T
 WORLDS = {"junctions": 64, "town": 32, "slots128": 8}          # world -> envs
 STATES = ("reset", "reset_coast_first", "driven")
 _cache = {}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _world(name, small_world, small_town):
@@ -67,18 +63,6 @@ def _state(wname, sname, small_world, small_town):
     return _cache[key]
 
 
-def _arrays(hs):
-    return hs.arrays if hasattr(hs, "arrays") else hs
-
-
-def _device(world, hs):
-    B = len(hs["scn"])
-    dw = world.to_device(DEV)
-    ds = EnvState(B, world.A, device=DEV)
-    ds.load({k: v for k, v in _arrays(hs).items() if v is not None})
-    return dw, ds
-
-
 def _want_forecast(wname, sname, small_world, small_town):
     key = (wname, sname, "fc")
     if key not in _cache:
@@ -103,7 +87,7 @@ def test_forecast_equals_the_restatement(small_world, small_town, wname, sname):
         rec = world.arrays["spawn"].reshape(-1, A)[hs["scn"]]
         out_mid = (rec["replay"] >= 0) & pres & (hs["steps"][:, None] < rec["replay_len"]) & (hs["steps"][:, None] + T_MAX > rec["replay_len"])
         assert out_mid.any()                                            # a replay record runs out inside the forecast
-    dw, ds = _device(world, hs)
+    dw, ds = on_device(world, hs)
     only = (np.arange(B) % 3 != 1).astype(np.uint8)
     m = torch.from_numpy(only).to(DEV)
     for binding in ("ctypes", "ext"):
@@ -118,12 +102,12 @@ def test_forecast_equals_the_restatement(small_world, small_town, wname, sname):
             h.forecast_agents(masked, m, int(cfg.flags))
         torch.cuda.synchronize()
         got = out.cpu().numpy()
-        bad = np.argwhere(_bits(got) != _bits(want))
+        bad = np.argwhere(bits(got) != bits(want))
         assert len(bad) == 0, (wname, sname, binding, len(bad), bad[:6].tolist(), got[tuple(bad[0][:3])], want[tuple(bad[0][:3])])
         gm = masked.cpu().numpy()
-        assert (gm[only == 0] == -7.0).all() and np.array_equal(_bits(gm[only != 0]), _bits(want[only != 0])), (wname, sname, binding)
+        assert (gm[only == 0] == -7.0).all() and np.array_equal(bits(gm[only != 0]), bits(want[only != 0])), (wname, sname, binding)
     short = ops.forecast_agents(cfg, dw, ds, 5)                         # a shorter forecast is the longer one's head
-    assert np.array_equal(_bits(short.cpu().numpy()), _bits(want[:, :5]))
+    assert np.array_equal(bits(short.cpu().numpy()), bits(want[:, :5]))
 
 
 # ---- 2. the environment as oracle -------------------------------------------------------------------------------------------------------
@@ -156,7 +140,7 @@ def test_constant_velocity_forecast_equals_score_plans(small_world, small_town, 
     cfg, world, hs = _state(wname, "driven", small_world, small_town)
     B = len(hs["scn"])
     pl = Planner()
-    dw, ds = _device(world, hs)
+    dw, ds = on_device(world, hs)
     fc = torch.from_numpy(Fr.constant_velocity(cfg, world, hs, pl.horizon + tail)).to(DEV)   # (c, s) = sincos_f32's values: the restatement's
     seq = torch.from_numpy(S.random_knots(np.random.default_rng(41), B, N, K)).to(DEV)
     res = []
@@ -188,33 +172,8 @@ def test_score_plans_forecast_equals_the_restatement(small_world, small_town, wn
     stride = {"junctions": 6, "town": 4, "slots128": 2}[wname]
     only = (np.arange(B) % stride == (N + K) % stride).astype(np.uint8)
     rng = np.random.default_rng(1000 * N + 10 * K + tail)
-    seq = S.random_knots(rng, B, N, K, wild=True)                       # knots outside the action box, one NaN knot per env
-    calm = rng.random((B, N)) < 0.35
-    seq[calm] = np.stack([rng.uniform(-1.0, 0.1, seq[calm].shape[:-1]), rng.uniform(-0.02, 0.02, seq[calm].shape[:-1])], -1).astype(np.float32)
-    c0, f0 = np.full((B, N), -5.0, np.float32), np.full((B, N), -9, np.int32)
-    a0, d0 = np.full((B, 2), -3.0, np.float32), np.full((B, 4), -7, np.int32)
-    want = Fr.score(cfg, world, hs, pl, seq, fc, None, tail, only=only, cost=c0, fail_step=f0, out=a0, diag=d0)
-    dw, ds = _device(world, hs)
-    m = torch.from_numpy(only).to(DEV)
-    dseq, dfc = torch.from_numpy(seq).to(DEV), torch.from_numpy(fc).to(DEV)
-    knot_len = -(-pl.horizon // K)
-    for binding in ("ctypes", "ext"):
-        cost, fail = torch.from_numpy(c0).to(DEV), torch.from_numpy(f0).to(DEV)
-        act, dg = torch.from_numpy(a0).to(DEV), torch.from_numpy(d0).to(DEV)
-        if binding == "ctypes":
-            ops.score_plans(cfg, dw, ds, pl, dseq, knot_len, tail, m, cost, fail, act, dg, forecast=dfc)
-        else:
-            _ext.env_handle(cfg, dw, ds).score_plans(dseq, knot_len, tail, cost, fail, int(pl.horizon), float(pl.v_target), float(pl.margin),
-                                                     float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), m, act, dg, int(cfg.flags), dfc)
-        torch.cuda.synchronize()
-        what = (wname, sname, N, K, tail, binding)
-        got_f, got_c = fail.cpu().numpy(), cost.cpu().numpy()
-        bad = np.argwhere(got_f != want["f"])
-        assert len(bad) == 0, (what, "fail_step", len(bad), bad[:6].tolist(), got_f[tuple(bad[0])], want["f"][tuple(bad[0])])
-        bad = np.argwhere(_bits(got_c) != _bits(want["cost"]))
-        assert len(bad) == 0, (what, "cost", len(bad), bad[:6].tolist(), got_c[tuple(bad[0])], want["cost"][tuple(bad[0])])
-        assert np.array_equal(dg.cpu().numpy().view(np.uint32), want["diag"].view(np.uint32).reshape(B, 4)), (what, "diag")
-        assert np.array_equal(_bits(act.cpu().numpy()), _bits(want["action"])), (what, "action")
+    seq = S.calm_knots(rng, S.random_knots(rng, B, N, K, wild=True))    # knots outside the action box, one NaN knot per env
+    check_score_plans(cfg, world, hs, pl, seq, -(-pl.horizon // K), tail, only=only, forecast=fc, what=(wname, sname, N, K, tail))
 
 
 # ---- 5. plan_actions() under each Planner.predict ---------------------------------------------------------------------------------------
@@ -243,7 +202,7 @@ def test_plan_actions_follows_planner_predict(small_world, binding):
                 assert env._plan_fc is None and env._plan_lat is None
             else:
                 wa, wd = Fr.plan_routed(env.tde_cfg, small_world, hs, env.planner, tail=40 if tailed else 0)
-                assert np.array_equal(_bits(a.cpu().numpy()), _bits(wa)), (binding, t, tailed)
+                assert np.array_equal(bits(a.cpu().numpy()), bits(wa)), (binding, t, tailed)
                 assert np.array_equal(d.cpu().numpy().view(np.uint32), wd.view(np.uint32).reshape(B, 4)), (binding, t, tailed)
                 assert tuple(env._plan_fc.shape) == (B, 72 if tailed else 32, small_world.A, 4)
             for _ in range(20):                                         # (a common drive, so that the three envs see the same kind of state)
@@ -257,7 +216,7 @@ def test_forecast_and_judge_are_graph_capturable(small_world, small_town):
     B, A, N, tail = len(hs["scn"]), world.A, 130, 40
     pl = Planner()
     T = pl.horizon + tail
-    dw, ds = _device(world, hs)
+    dw, ds = on_device(world, hs)
     seq = torch.from_numpy(S.random_knots(np.random.default_rng(3), B, N, 2)).to(DEV)
     bufs = [dict(fc=torch.zeros((B, T, A, 4), dtype=torch.float32, device=DEV), cost=torch.zeros((B, N), dtype=torch.float32, device=DEV),
                  fail=torch.zeros((B, N), dtype=torch.int32, device=DEV), act=torch.zeros((B, 2), dtype=torch.float32, device=DEV),

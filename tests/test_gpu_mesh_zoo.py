@@ -17,6 +17,7 @@ from tests import mesh_zoo as Z  # noqa: E402
 from tests import plan_set_ref as S  # noqa: E402
 from tests import planner_ref as P  # noqa: E402
 from tests import vector_obs_ref as V  # noqa: E402
+from tests.plan_gpu_util import bits, on_device  # noqa: E402
 from tests.scene_util import free_last_slot, oracle_scene_views  # noqa: E402
 from tests.test_gpu_parity import assert_state_equal, dev  # noqa: E402
 from torchdriveenv_amd import _abi, _lib, ops  # noqa: E402
@@ -35,10 +36,6 @@ SHAPE_IDS = IDS + ["fan-0.5-4x128", "roundabout-0.25-24x4", "islands-0.25-8x32"]
 PLANNED = [(n, c) for n in ("roundabout", "long_slivers", "far_ribbon") for c in Z.CELLS]
 K = 9                           # one zero-action step from the loaded poses, then 8 random-action steps
 _DEVICE_WORLDS = {}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _differ(got, want):
@@ -153,11 +150,11 @@ def test_step_and_rollout_in_every_role_split(name, cell, squared, b, a):
                 ops.env_step(cfg, dw, d, action=dacts[t])
                 r, dn, mg = per_step[t]
                 got = d["reward"].cpu().numpy()
-                assert np.array_equal(_bits(got), _bits(r)), f"{what}: {_differ(_bits(got), _bits(r))} rewards differ at step {t}"
+                assert np.array_equal(bits(got), bits(r)), f"{what}: {_differ(bits(got), bits(r))} rewards differ at step {t}"
                 got = d["done_bits"].cpu().numpy()
                 assert np.array_equal(got, dn), f"{what}: {_differ(got, dn)} done bits differ at step {t}"
                 got = d["magnitudes"].cpu().numpy()
-                assert np.array_equal(_bits(got), _bits(mg)), f"{what}: {_differ(_bits(got), _bits(mg))} magnitudes differ at step {t}"
+                assert np.array_equal(bits(got), bits(mg)), f"{what}: {_differ(bits(got), bits(mg))} magnitudes differ at step {t}"
                 if t in snaps:
                     assert_state_equal(snaps[t], d.host(), f"{what}, step {t}")
                     if d["obs"] is not None:
@@ -166,7 +163,7 @@ def test_step_and_rollout_in_every_role_split(name, cell, squared, b, a):
             _lib.kernel_override()
         hr, hd = oracle.env_rollout(cfg, world, _copy(hs0), acts)
         for t in range(K):
-            n_bad = _differ(_bits(hr[t]), _bits(per_step[t][0])) + _differ(hd[t], per_step[t][1])
+            n_bad = _differ(bits(hr[t]), bits(per_step[t][0])) + _differ(hd[t], per_step[t][1])
             assert n_bad == 0, f"{where}: the oracle's rollout and its steps differ in {n_bad} rewards / done bytes at step {t}"
         for form in {128: ("solo", None, "duo"), 32: ("solo", "duo", "trio"), 16: ("solo", "duo", "trio"), 4: ("solo", "duo")}[a]:
             what = f"{where}, rollout {form or 'auto'}"
@@ -176,7 +173,7 @@ def test_step_and_rollout_in_every_role_split(name, cell, squared, b, a):
             torch.cuda.synchronize()
             _lib.kernel_override()
             r, dn = r.cpu().numpy(), dn.cpu().numpy()
-            assert np.array_equal(_bits(r), _bits(hr)), f"{what}: {_differ(_bits(r), _bits(hr))} of {hr.size} rewards differ"
+            assert np.array_equal(bits(r), bits(hr)), f"{what}: {_differ(bits(r), bits(hr))} of {hr.size} rewards differ"
             assert np.array_equal(dn, hd), f"{what}: {_differ(dn, hd)} of {hd.size} done bytes differ"
             skip = ("done_bits", "magnitudes", "ep_return", "ep_final", "ep_final_len")
             assert_state_equal({k: v for k, v in snaps[K - 1].items() if k not in skip}, d.host(), what)
@@ -201,7 +198,7 @@ def test_magnitudes(name, cell, squared, near_range):
     d = _on_device(hs, with_obs=True)
     want = oracle.ego_infractions(cfg, world, hs)
     got = ops.ego_infractions(cfg, dw, d).cpu().numpy()
-    assert np.array_equal(_bits(got), _bits(want)), f"{where}: {_differ(_bits(got), _bits(want))} of {want.size} magnitudes differ"
+    assert np.array_equal(bits(got), bits(want)), f"{where}: {_differ(bits(got), bits(want))} of {want.size} magnitudes differ"
     assert (want[:, 0] > 300.0).any() and (want[:, 0] > 0).sum() > B // 4, where          # (egos 400 m away among them)
     mag = torch.zeros(B, 4, device=DEV)
     acts = _actions(B, seed=15)
@@ -214,7 +211,7 @@ def test_magnitudes(name, cell, squared, near_range):
         ops.env_step(cfg, dw, d, action=dev(acts[t]))
         ops.env_post_step(cfg_post, dw, d, mag)
         got = mag.cpu().numpy()
-        assert np.array_equal(_bits(got), _bits(want)), f"{where}: {_differ(_bits(got), _bits(want))} post-step magnitudes differ at step {t}"
+        assert np.array_equal(bits(got), bits(want)), f"{where}: {_differ(bits(got), bits(want))} post-step magnitudes differ at step {t}"
     assert_state_equal(hs.host(), d.host(), f"{where}: post_step")
 
 
@@ -267,9 +264,9 @@ def test_vector_obs(name, cell, squared, ray_step):
     hs = _loaded(world, cfg, B, seed=18)
     vo = VectorObs(k_neighbours=4, n_rays=16, ray_range=30.0, ray_step=ray_step, neighbour_radius=30.0)
     want = V.vector_obs(cfg, world, hs, vo)
-    got = ops.vector_obs(cfg, _device(world), _on_device(hs), vo).cpu().numpy()
-    assert np.array_equal(_bits(got), _bits(want)), (f"{Z.where(name, cell, squared)}, ray_step {ray_step}: "
-                                                     f"{_differ(_bits(got), _bits(want))} of {want.size} values differ")
+    got = ops.vector_obs(cfg, *on_device(world, hs), vo).cpu().numpy()
+    assert np.array_equal(bits(got), bits(want)), (f"{Z.where(name, cell, squared)}, ray_step {ray_step}: "
+                                                     f"{_differ(bits(got), bits(want))} of {want.size} values differ")
     road = want[:, vo.slices()["road"]]
     assert (road < vo.ray_range).any() and (road > ray_step).any()
 
@@ -295,14 +292,14 @@ def test_planner(name, cell):
     want_a, want_d = P.plan(cfg, world, hs, pl)
     out = torch.full((B, 2), -3.0, dtype=torch.float32, device=DEV)
     dg = torch.full((B, 4), -7, dtype=torch.int32, device=DEV)
-    ops.plan_action(cfg, _device(world), _on_device(hs), pl, out, None, dg)
+    ops.plan_action(cfg, *on_device(world, hs), pl, out, None, dg)
     got_a, got_d = out.cpu().numpy(), dg.cpu().numpy().view(_abi.PLAN_DIAG_DTYPE).reshape(B)
     where = Z.where(name, cell)
     for n in ("winner", "fail_step", "n_safe"):
         assert np.array_equal(got_d[n], want_d[n]), f"{where}: {_differ(got_d[n], want_d[n])} of {B} diag.{n} differ"
     got_c, want_c = got_d["cost"].view(np.uint32), want_d["cost"].view(np.uint32)
     assert np.array_equal(got_c, want_c), f"{where}: {_differ(got_c, want_c)} of {B} diag.cost differ"
-    assert np.array_equal(_bits(got_a), _bits(want_a)), f"{where}: {_differ(_bits(got_a), _bits(want_a))} of {want_a.size} action values differ"
+    assert np.array_equal(bits(got_a), bits(want_a)), f"{where}: {_differ(bits(got_a), bits(want_a))} of {want_a.size} action values differ"
     assert (want_d["n_safe"] > 0).any() and (want_d["n_safe"] < pl.n_candidates).any(), where
 
 
@@ -315,13 +312,11 @@ def test_plan_judge(name, cell, N):
     hs = _planner_state(world, cfg, seed=20)
     pl = Planner(horizon=16)
     rng = np.random.default_rng(21)
-    seq = S.random_knots(rng, B, N, 4)
-    calm = rng.random((B, N)) < 0.35
-    seq[calm] = np.stack([rng.uniform(-1.0, 0.1, seq[calm].shape[:-1]), rng.uniform(-0.02, 0.02, seq[calm].shape[:-1])], -1).astype(np.float32)
+    seq = S.calm_knots(rng, S.random_knots(rng, B, N, 4))
     want = S.score(cfg, world, hs, pl, seq, 4, 10)
-    cost, fail = ops.score_plans(cfg, _device(world), _on_device(hs), pl, dev(seq), 4, 10)
+    cost, fail = ops.score_plans(cfg, *on_device(world, hs), pl, dev(seq), 4, 10)
     got_c, got_f = cost.cpu().numpy(), fail.cpu().numpy()
     where = Z.where(name, cell) + f", N {N}"
     assert np.array_equal(got_f, want["f"]), f"{where}: {_differ(got_f, want['f'])} of {got_f.size} fail steps differ"
-    assert np.array_equal(_bits(got_c), _bits(want["cost"])), f"{where}: {_differ(_bits(got_c), _bits(want['cost']))} of {got_c.size} costs differ"
+    assert np.array_equal(bits(got_c), bits(want["cost"])), f"{where}: {_differ(bits(got_c), bits(want['cost']))} of {got_c.size} costs differ"
     assert (want["cause"] == S.OFFROAD).any() and (want["f"] == pl.horizon + 10 + 1).any(), where

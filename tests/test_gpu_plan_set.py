@@ -9,64 +9,14 @@ import torch
 
 from tests import plan_set_ref as S
 from tests import planner_ref as R
+from tests.plan_gpu_util import bits, check_score_plans, on_device
 from tests.test_gpu_planner import BEHAVIOUR_B, BEHAVIOUR_STEPS, WIDE, format_rows
-from torchdriveenv_amd import _abi, _ext, ops
+from torchdriveenv_amd import _abi, ops
 from torchdriveenv_amd.config import EnvConfig, Planner, PlanRefine
 from torchdriveenv_amd.env import BatchedWaypointEnv
-from torchdriveenv_amd.state import EnvState
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _arrays(hs):
-    return hs.arrays if hasattr(hs, "arrays") else hs
-
-
-def _check(cfg, world, hs, pl, seq, knot_len, tail, only=None, what=""):
-    """the kernel (both bindings) on the device copy of host state `hs` == the restatement, every output; rows outside `only` keep
-    what they held; returns the restatement's result"""
-    B, A = len(hs["scn"]), world.A
-    N = seq.shape[1]
-    c0, f0 = np.full((B, N), -5.0, np.float32), np.full((B, N), -9, np.int32)
-    a0, d0 = np.full((B, 2), -3.0, np.float32), np.full((B, 4), -7, np.int32)
-    want = S.score(cfg, world, hs, pl, seq, knot_len, tail, only=only, cost=c0, fail_step=f0, out=a0, diag=d0)
-    dw = world.to_device(DEV)
-    ds = EnvState(B, A, device=DEV)
-    ds.load({k: v for k, v in _arrays(hs).items() if v is not None})
-    m = torch.from_numpy(np.asarray(only, np.uint8)).to(DEV) if only is not None else None
-    dseq = torch.from_numpy(np.ascontiguousarray(seq)).to(DEV)
-    for binding in ("ctypes", "ext"):
-        cost, fail = torch.from_numpy(c0).to(DEV), torch.from_numpy(f0).to(DEV)
-        act, dg = torch.from_numpy(a0).to(DEV), torch.from_numpy(d0).to(DEV)
-        if binding == "ctypes":
-            ops.score_plans(cfg, dw, ds, pl, dseq, knot_len, tail, m, cost, fail, act, dg)
-        else:
-            _ext.env_handle(cfg, dw, ds).score_plans(dseq, int(knot_len), int(tail), cost, fail, int(pl.horizon), float(pl.v_target),
-                                                     float(pl.margin), float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), m, act,
-                                                     dg, int(cfg.flags))
-        torch.cuda.synchronize()
-        got_f, got_c = fail.cpu().numpy(), cost.cpu().numpy()
-        bad = np.argwhere(got_f != want["f"])
-        assert len(bad) == 0, (what, binding, "fail_step", len(bad), bad[:6].tolist(), got_f[tuple(bad[0])], want["f"][tuple(bad[0])])
-        bad = np.argwhere(_bits(got_c) != _bits(want["cost"]))
-        assert len(bad) == 0, (what, binding, "cost", len(bad), bad[:6].tolist(), got_c[tuple(bad[0])], want["cost"][tuple(bad[0])])
-        got_d = dg.cpu().numpy().view(_abi.PLAN_DIAG_DTYPE).reshape(B)
-        for n in ("winner", "fail_step", "n_safe"):
-            bad = np.flatnonzero(got_d[n] != want["diag"][n])
-            assert len(bad) == 0, (what, binding, n, bad[:8].tolist(), got_d[bad[:4]], want["diag"][bad[:4]])
-        assert np.array_equal(got_d["cost"].view(np.uint32), want["diag"]["cost"].view(np.uint32)), (what, binding, "diag cost")
-        assert np.array_equal(_bits(act.cpu().numpy()), _bits(want["action"])), (what, binding, "action")
-        # without action / diag the same costs are written
-        cost2, fail2 = torch.from_numpy(c0).to(DEV), torch.from_numpy(f0).to(DEV)
-        if binding == "ctypes":
-            ops.score_plans(cfg, dw, ds, pl, dseq, knot_len, tail, m, cost2, fail2)
-            assert torch.equal(cost2.view(torch.int32), cost.view(torch.int32)) and torch.equal(fail2, fail), (what, "no diag")
-    return want
 
 
 # ---- 1. the construction equality -----------------------------------------------------------------------------------------------------
@@ -76,19 +26,17 @@ def _as_plan_action(cfg, world, hs, pl, what):
     B = len(hs["scn"])
     lat = S.lattice(pl)
     seq = np.ascontiguousarray(np.broadcast_to(lat[None, :, None, :], (B, len(lat), 1, 2)))
-    want = _check(cfg, world, hs, pl, seq, pl.horizon, 0, what=what)
+    want = check_score_plans(cfg, world, hs, pl, seq, pl.horizon, 0, what=what)
     act, dg, f, cost = R.plan(cfg, world, hs, pl, detail=True)
-    assert np.array_equal(want["f"], f) and np.array_equal(_bits(want["cost"]), _bits(cost)), what
-    assert np.array_equal(_bits(want["action"]), _bits(act)) and all(np.array_equal(want["diag"][n].view(np.uint32), dg[n].view(np.uint32))
+    assert np.array_equal(want["f"], f) and np.array_equal(bits(want["cost"]), bits(cost)), what
+    assert np.array_equal(bits(want["action"]), bits(act)) and all(np.array_equal(want["diag"][n].view(np.uint32), dg[n].view(np.uint32))
                                                                       for n in dg.dtype.names), what
-    dw = world.to_device(DEV)
-    ds = EnvState(B, world.A, device=DEV)
-    ds.load({k: v for k, v in _arrays(hs).items() if v is not None})
+    dw, ds = on_device(world, hs)
     out = torch.zeros((B, 2), dtype=torch.float32, device=DEV)
     d = torch.zeros((B, 4), dtype=torch.int32, device=DEV)
     ops.plan_action(cfg, dw, ds, pl, out, None, d)
     torch.cuda.synchronize()
-    assert np.array_equal(_bits(out.cpu().numpy()), _bits(want["action"])), what
+    assert np.array_equal(bits(out.cpu().numpy()), bits(want["action"])), what
     assert np.array_equal(d.cpu().numpy().view(np.uint32), want["diag"].view(np.uint32).reshape(B, 4)), what
 
 
@@ -126,7 +74,7 @@ def test_lattice_sequences_equal_plan_action_on_128_crowded_slots():
     _as_plan_action(cfg, world, hs, Planner(), "crowded")
     # and a team of wavefronts over the same 127 rows
     seq = S.random_knots(rng, B, 130, 2)
-    _check(cfg, world, hs, Planner(), seq, 16, 10, what="crowded team")
+    check_score_plans(cfg, world, hs, Planner(), seq, 16, 10, what="crowded team")
 
 
 # ---- 2. seeded random knot sequences --------------------------------------------------------------------------------------------------
@@ -134,7 +82,7 @@ def test_lattice_sequences_equal_plan_action_on_128_crowded_slots():
 @pytest.mark.parametrize("name", list(S.CASES))
 def test_random_knot_sequences(small_world, name):
     cfg, world, hs, pl, seq, knot_len, tail, only = S.case_inputs(name, small_world)
-    _check(cfg, world, hs, pl, seq, knot_len, tail, only=only, what=name)
+    check_score_plans(cfg, world, hs, pl, seq, knot_len, tail, only=only, what=name)
 
 
 # ---- 3. the tail's known answer -------------------------------------------------------------------------------------------------------
@@ -143,7 +91,7 @@ def test_brake_tail_known_answer():
     cfg, world, st, pl, seq = S.tail_corridor()
     H = pl.horizon
     for tail in (0, 40, 64):
-        got = _check(cfg, world, st, pl, seq, H, tail, what=("tail", tail))
+        got = check_score_plans(cfg, world, st, pl, seq, H, tail, what=("tail", tail))
         f = got["f"][0]
         if tail == 0:
             assert f[0] == H + 1 and f[1] == H + 1
@@ -176,12 +124,12 @@ def test_refined_plan_equals_the_restatement_and_its_cost_never_rises(small_worl
         torch.cuda.synchronize()
         want_a, want_d, costs = S.refine(env.tde_cfg, small_world, env.state.host(), env.planner, pr)
         got_d = _diag(d)
-        assert np.array_equal(_bits(a.cpu().numpy()), _bits(want_a)), rounds
+        assert np.array_equal(bits(a.cpu().numpy()), bits(want_a)), rounds
         assert np.array_equal(got_d.view(np.uint32), want_d.view(np.uint32)), rounds
         per_round.append(got_d["cost"].copy())
-        assert len(costs) == rounds + 1 and np.array_equal(_bits(costs[-1]), _bits(got_d["cost"]))
+        assert len(costs) == rounds + 1 and np.array_equal(bits(costs[-1]), bits(got_d["cost"]))
     for r in (1, 2):
-        assert (R.ordered(_bits(per_round[r])) <= R.ordered(_bits(per_round[r - 1]))).all(), r
+        assert (R.ordered(bits(per_round[r])) <= R.ordered(bits(per_round[r - 1]))).all(), r
     assert (per_round[2] < per_round[0]).any()                        # refinement finds something on this batch
 
 
@@ -206,7 +154,7 @@ def test_refined_plan_with_an_only_mask(small_world):
     env.plan_actions()                                                # (leaves older winners in the diag rows of the masked call)
     a = env.plan_actions(out=out, only=torch.from_numpy(only).to(DEV))
     want_a, _, _ = S.refine(env.tde_cfg, small_world, env.state.host(), env.planner, pr, only=only, out=np.full((B, 2), -3.0, np.float32))
-    assert np.array_equal(_bits(a.cpu().numpy()), _bits(want_a))
+    assert np.array_equal(bits(a.cpu().numpy()), bits(want_a))
 
 
 def test_states_reached_under_the_refined_planners_own_actions(small_world):
@@ -217,7 +165,7 @@ def test_states_reached_under_the_refined_planners_own_actions(small_world):
         a, d = env.plan_actions(diag=True)
         if t % 50 == 0:
             want_a, want_d, _ = S.refine(env.tde_cfg, small_world, env.state.host(), env.planner, pr)
-            assert np.array_equal(_bits(a.cpu().numpy()), _bits(want_a)), t
+            assert np.array_equal(bits(a.cpu().numpy()), bits(want_a)), t
             assert np.array_equal(_diag(d).view(np.uint32), want_d.view(np.uint32)), t
         env.step(a)
 
@@ -234,7 +182,7 @@ def test_two_shards_equal_the_unsharded_batch_refined(small_world):
         for t in range(30):
             aa, da = one.plan_actions(diag=True)
             ab, db = two.plan_actions(diag=True)
-            assert aa.shape == (B, 2) and np.array_equal(_bits(aa), _bits(ab)) and np.array_equal(da, db), t
+            assert aa.shape == (B, 2) and np.array_equal(bits(aa), bits(ab)) and np.array_equal(da, db), t
             one.step(aa), two.step(ab)
     finally:
         two.close()
@@ -260,7 +208,7 @@ def test_env_score_plans_surface(small_world):
     cost, fail = env.score_plans(seq, tail=8)
     assert cost.shape == (16, 5) and cost.dtype == torch.float32 and fail.dtype == torch.int32 and fail.is_cuda
     want = S.score(env.tde_cfg, small_world, env.state.host(), env.planner, seq.cpu().numpy(), None, 8)
-    assert np.array_equal(fail.cpu().numpy(), want["f"]) and np.array_equal(_bits(cost.cpu().numpy()), _bits(want["cost"]))
+    assert np.array_equal(fail.cpu().numpy(), want["f"]) and np.array_equal(bits(cost.cpu().numpy()), bits(want["cost"]))
     with pytest.raises(ValueError):
         env.score_plans(seq.permute(0, 2, 1, 3))
     with pytest.raises(ValueError):

@@ -8,12 +8,11 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import oracle
-from tests import planner_ref as R
-from torchdriveenv_amd import _abi, _ext, ops
+from tests import plan_set_ref as S
+from tests.plan_gpu_util import bits, check_plan_action
+from torchdriveenv_amd import _abi
 from torchdriveenv_amd.config import EnvConfig, Planner
 from torchdriveenv_amd.env import BatchedWaypointEnv
-from torchdriveenv_amd.state import EnvState
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,66 +21,12 @@ WIDE = Planner(accelerations=(-1.0, -0.6, -0.3, 0.0, 0.2, 0.4, 0.7, 1.0), steeri
                horizon=20, v_target=7.0, margin=0.5, w_progress=2.0, w_speed=0.1, w_steer=4.0)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _arrays(hs):
-    return hs.arrays if hasattr(hs, "arrays") else hs
-
-
-def _check(cfg, world, hs, pl, only=None, what=""):
-    """the kernel (both bindings) on the device copy of host state `hs` == the restatement; returns (actions, diag) of the latter"""
-    B, A = len(hs["scn"]), world.A
-    fill = only is not None
-    act0 = np.full((B, 2), -3.0, np.float32)
-    dg0 = np.full((B, 4), -7, np.int32)
-    want_a, want_d = R.plan(cfg, world, hs, pl, only=only, out=act0 if fill else None, diag=dg0 if fill else None)
-    dw = world.to_device(DEV)
-    ds = EnvState(B, A, device=DEV)
-    ds.load({k: v for k, v in _arrays(hs).items() if v is not None})
-    m = torch.from_numpy(np.asarray(only, np.uint8)).to(DEV) if only is not None else None
-    for binding in ("ctypes", "ext"):
-        out = torch.full((B, 2), -3.0, dtype=torch.float32, device=DEV)
-        dg = torch.full((B, 4), -7, dtype=torch.int32, device=DEV)
-        if binding == "ctypes":
-            ops.plan_action(cfg, dw, ds, pl, out, m, dg)
-        else:
-            _ext.env_handle(cfg, dw, ds).plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings],
-                                                     int(pl.horizon), float(pl.v_target), float(pl.margin), float(pl.w_progress),
-                                                     float(pl.w_speed), float(pl.w_steer), m, dg, int(cfg.flags))
-        torch.cuda.synchronize()
-        got_a = out.cpu().numpy()
-        got_d = dg.cpu().numpy().view(_abi.PLAN_DIAG_DTYPE).reshape(B)
-        for n in ("winner", "fail_step", "n_safe"):
-            bad = np.flatnonzero(got_d[n] != want_d[n])
-            assert len(bad) == 0, (what, binding, n, bad[:8].tolist(), got_d[bad[:4]], want_d[bad[:4]])
-        assert np.array_equal(got_d["cost"].view(np.uint32), want_d["cost"].view(np.uint32)), (what, binding, "cost")
-        bad = np.argwhere(_bits(got_a) != _bits(want_a))
-        assert len(bad) == 0, (what, binding, bad[:8].tolist(), got_a[bad[0][0]], want_a[bad[0][0]])
-    return want_a, want_d
-
-
-def _reset_state(cfg, world, B, episode=0):
-    hs = EnvState(B, world.A)
-    hs["episode"][...] = episode
-    oracle.env_reset(cfg, world, hs)
-    return hs
-
-
-def _lights_cfg(world, **kw):
-    cfg = _abi.default_config(**kw)
-    if world.has_lights:
-        cfg.flags |= _abi.F_TRAFFIC_LIGHTS
-    return cfg
-
-
 @pytest.mark.parametrize("pl", [Planner(), WIDE, Planner(horizon=1), Planner(accelerations=(0.0,), steerings=(0.0,), horizon=32)],
                          ids=["default", "wide64", "h1", "one"])
 def test_junction_world_at_16_slots(small_world, pl):
-    cfg = _lights_cfg(small_world, seed=3)
-    hs = _reset_state(cfg, small_world, 192)
-    act, dg = _check(cfg, small_world, hs, pl, what="junctions")
+    cfg = S.lights_cfg(small_world, seed=3)
+    hs = S.reset_state(cfg, small_world, 192)
+    act, dg = check_plan_action(cfg, small_world, hs, pl, what="junctions")
     if pl.n_candidates > 1 and pl.horizon > 1:
         assert len(np.unique(dg["winner"])) > 3 and (dg["n_safe"] > 0).any() and (dg["n_safe"] < pl.n_candidates).any()
 
@@ -100,8 +45,8 @@ def test_states_reached_under_the_planners_own_actions(small_world, binding):
         a, d = env.plan_actions(diag=True)
         if t % 25 == 0:
             hs = env.state.host()
-            want_a, want_d = _check(env.tde_cfg, small_world, hs, pl, what=("loop", t))
-            assert np.array_equal(_bits(a.cpu().numpy()), _bits(want_a)), t
+            want_a, want_d = check_plan_action(env.tde_cfg, small_world, hs, pl, what=("loop", t))
+            assert np.array_equal(bits(a.cpu().numpy()), bits(want_a)), t
             assert np.array_equal(d.cpu().numpy().view(_abi.PLAN_DIAG_DTYPE).reshape(B)["winner"], want_d["winner"]), t
             unsafe += int((want_d["n_safe"] < pl.n_candidates).sum())
             safe += int((want_d["n_safe"] > 0).sum())
@@ -110,22 +55,22 @@ def test_states_reached_under_the_planners_own_actions(small_world, binding):
 
 
 def test_towns_large_grid(small_town, town):
-    cfg = _lights_cfg(small_town, seed=4)
-    hs = _reset_state(cfg, small_town, 96)
+    cfg = S.lights_cfg(small_town, seed=4)
+    hs = S.reset_state(cfg, small_town, 96)
     hs["steps"][...] = np.arange(96) * 3
-    _check(cfg, small_town, hs, Planner(), what="town")
+    check_plan_action(cfg, small_town, hs, Planner(), what="town")
     assert town.arrays["maps"]["nx"].max() * town.arrays["maps"]["ny"].max() > 2 ** 21       # (TDE_WORLD_LARGE_GRID)
-    cfg = _lights_cfg(town, seed=6)
-    _check(cfg, town, _reset_state(cfg, town, 24), Planner(horizon=16), what="town 1 km")
+    cfg = S.lights_cfg(town, seed=6)
+    check_plan_action(cfg, town, S.reset_state(cfg, town, 24), Planner(horizon=16), what="town 1 km")
 
 
 def test_128_crowded_slots():
     from torchdriveenv_amd.synth import synthetic_world
 
     world = synthetic_world(n_scn=4, A=128, seed=5, n_maps=2)
-    cfg = _lights_cfg(world, seed=5)
+    cfg = S.lights_cfg(world, seed=5)
     B, A = 32, 128
-    hs = _reset_state(cfg, world, B)
+    hs = S.reset_state(cfg, world, B)
     rng = np.random.default_rng(7)
     x, y = hs["x"].reshape(B, A), hs["y"].reshape(B, A)
     # every slot present, scattered within 40 m of the ego but not on it, moving
@@ -136,15 +81,15 @@ def test_128_crowded_slots():
     hs["v"].reshape(B, A)[:, 1:] = rng.uniform(0, 12, (B, A - 1)).astype(np.float32)
     hs["present"][...] = 1
     for pl in (Planner(), WIDE):
-        act, dg = _check(cfg, world, hs, pl, what="crowded")
+        act, dg = check_plan_action(cfg, world, hs, pl, what="crowded")
         assert (dg["fail_step"] <= pl.horizon).any()
 
 
 def test_lights_across_phase_changes(small_world):
-    cfg = _lights_cfg(small_world, seed=11)
+    cfg = S.lights_cfg(small_world, seed=11)
     assert cfg.flags & _abi.F_TRAFFIC_LIGHTS
     B, A = 128, small_world.A
-    hs = _reset_state(cfg, small_world, B)
+    hs = S.reset_state(cfg, small_world, B)
     # half of the egos a few metres in front of a stop line of their map, heading across it
     mp, stop = small_world.arrays["maps"], small_world.arrays["stoplines"]
     m = small_world.map_of_scn()[hs["scn"]]
@@ -161,15 +106,15 @@ def test_lights_across_phase_changes(small_world):
     seen = []
     for k in (0, 40, 79, 80, 95, 120, 145, 159, 160, 400):
         hs["steps"][...] = k
-        act, dg = _check(cfg, small_world, hs, Planner(), what=("lights", k))
+        act, dg = check_plan_action(cfg, small_world, hs, Planner(), what=("lights", k))
         seen.append(int(dg["n_safe"].sum()))
     assert len(set(seen)) > 1                                        # which candidates are safe changes with the phase
 
 
 def test_egos_near_the_grid_edge_and_offroad(small_world):
-    cfg = _lights_cfg(small_world, seed=12)
+    cfg = S.lights_cfg(small_world, seed=12)
     B, A = 192, small_world.A
-    hs = _reset_state(cfg, small_world, B)
+    hs = S.reset_state(cfg, small_world, B)
     mp = small_world.arrays["maps"]
     m = small_world.map_of_scn()[hs["scn"]]
     ox, oy = mp["ox"][m], mp["oy"][m]
@@ -186,17 +131,17 @@ def test_egos_near_the_grid_edge_and_offroad(small_world):
     x0[2 * n:] += rng.uniform(3.0, 9.0, B - 2 * n)
     hs["x"][::A], hs["y"][::A] = x0.astype(np.float32), y0.astype(np.float32)
     hs["psi"][::A] = rng.uniform(-3.14, 3.14, B).astype(np.float32)
-    act, dg = _check(cfg, small_world, hs, Planner(), what="edge")
+    act, dg = check_plan_action(cfg, small_world, hs, Planner(), what="edge")
     assert (dg["n_safe"][b] == 0).all() and (dg["fail_step"][b] == 1).all()      # off the grid: every candidate fails at once
     assert (dg["fail_step"][2 * n:] > 1).any()
 
 
 def test_only_masks_leave_the_other_rows(small_world):
-    cfg = _lights_cfg(small_world, seed=8)
-    hs = _reset_state(cfg, small_world, 100)
+    cfg = S.lights_cfg(small_world, seed=8)
+    hs = S.reset_state(cfg, small_world, 100)
     only = (np.random.default_rng(0).random(100) < 0.3).astype(np.uint8)
-    _check(cfg, small_world, hs, Planner(horizon=12), only=only, what="only")
-    _check(cfg, small_world, hs, Planner(horizon=12), only=np.zeros(100, np.uint8), what="none")
+    check_plan_action(cfg, small_world, hs, Planner(horizon=12), only=only, what="only")
+    check_plan_action(cfg, small_world, hs, Planner(horizon=12), only=np.zeros(100, np.uint8), what="none")
 
 
 @pytest.mark.parametrize("squared", [False, True])
@@ -205,9 +150,9 @@ def test_both_threshold_readings(squared):
     from torchdriveenv_amd.world import effective_offroad_distance
 
     world = synthetic_world(n_scn=8, A=16, seed=0, n_maps=2, threshold=effective_offroad_distance(0.5, squared))
-    cfg = _lights_cfg(world, seed=3, offroad_threshold=0.5, offroad_threshold_squared=int(squared))
-    hs = _reset_state(cfg, world, 8 if squared else 64)               # (the squared reading's checker walks the mesh per corner)
-    act, dg = _check(cfg, world, hs, Planner(horizon=10 if squared else 32), what=("squared", squared))
+    cfg = S.lights_cfg(world, seed=3, offroad_threshold=0.5, offroad_threshold_squared=int(squared))
+    hs = S.reset_state(cfg, world, 8 if squared else 64)               # (the squared reading's checker walks the mesh per corner)
+    act, dg = check_plan_action(cfg, world, hs, Planner(horizon=10 if squared else 32), what=("squared", squared))
     assert (dg["n_safe"] > 0).any()
 
 
@@ -224,7 +169,7 @@ def test_two_shards_equal_the_unsharded_batch(small_world):
         for t in range(40):
             aa, da = one.plan_actions(diag=True)
             ab, db = two.plan_actions(diag=True)
-            assert aa.shape == (B, 2) and np.array_equal(_bits(aa), _bits(ab)) and np.array_equal(da, db), t
+            assert aa.shape == (B, 2) and np.array_equal(bits(aa), bits(ab)) and np.array_equal(da, db), t
             _, _, d1, _ = one.step(aa)
             _, _, d2, _ = two.step(ab)
             assert np.array_equal(d1, d2)

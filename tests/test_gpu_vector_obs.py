@@ -8,7 +8,9 @@ import torch
 
 from oracle import oracle
 from tests import near_field_ref as NF
+from tests import plan_set_ref as S
 from tests import vector_obs_ref as R
+from tests.plan_gpu_util import bits, on_device
 from torchdriveenv_amd import _abi, _ext, ops
 from torchdriveenv_amd.config import EnvConfig, VectorObs
 from torchdriveenv_amd.env import BatchedWaypointEnv
@@ -18,17 +20,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def _check(cfg, world, hs, vo, only=None, what=""):
     """the kernel (both bindings) on the device copy of host state `hs` == the restatement; returns the rows"""
-    B, A = len(hs["scn"]), world.A
+    B = len(hs["scn"])
     want = R.vector_obs(cfg, world, hs, vo, only=only, out=np.full((B, vo.dim), -3.0, np.float32) if only is not None else None)
-    dw = world.to_device(DEV)
-    ds = EnvState(B, A, device=DEV)
-    ds.load({k: v for k, v in hs.arrays.items() if v is not None})
+    dw, ds = on_device(world, hs)
     rd = torch.from_numpy(vo.ray_directions()).to(DEV)
     m = torch.from_numpy(np.asarray(only, np.uint8)).to(DEV) if only is not None else None
     for binding in ("ctypes", "ext"):
@@ -40,23 +36,9 @@ def _check(cfg, world, hs, vo, only=None, what=""):
                                                     vo.ray_step, m, int(cfg.flags))
         torch.cuda.synchronize()
         got = out.cpu().numpy()
-        bad = np.argwhere(_bits(got) != _bits(want))
+        bad = np.argwhere(bits(got) != bits(want))
         assert len(bad) == 0, (what, binding, bad[:8].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
     return want
-
-
-def _reset_state(cfg, world, B, episode=0):
-    hs = EnvState(B, world.A)
-    hs["episode"][...] = episode
-    oracle.env_reset(cfg, world, hs)
-    return hs
-
-
-def _lights_cfg(world, **kw):
-    cfg = _abi.default_config(**kw)
-    if world.has_lights:
-        cfg.flags |= _abi.F_TRAFFIC_LIGHTS
-    return cfg
 
 
 VOS = [VectorObs(), VectorObs(k_neighbours=16, n_rays=64, ray_range=30.0, ray_step=0.25, neighbour_radius=80.0),
@@ -65,8 +47,8 @@ VOS = [VectorObs(), VectorObs(k_neighbours=16, n_rays=64, ray_range=30.0, ray_st
 
 @pytest.mark.parametrize("v", range(len(VOS)))
 def test_junction_world_at_16_slots(small_world, v):
-    cfg = _lights_cfg(small_world, seed=3)
-    hs = _reset_state(cfg, small_world, 256)
+    cfg = S.lights_cfg(small_world, seed=3)
+    hs = S.reset_state(cfg, small_world, 256)
     rows = _check(cfg, small_world, hs, VOS[v], what="junctions")
     vo = VOS[v]
     sl = vo.slices()
@@ -77,7 +59,7 @@ def test_junction_world_at_16_slots(small_world, v):
 def test_validation_world_and_only_masks(tmp_path):
     world, _ = NF.validation_world(0, 16, tmp_path)
     cfg = _abi.default_config(seed=8)
-    hs = _reset_state(cfg, world, 200)
+    hs = S.reset_state(cfg, world, 200)
     _check(cfg, world, hs, VectorObs(), what="validation")
     only = (np.random.default_rng(0).random(200) < 0.3).astype(np.uint8)
     _check(cfg, world, hs, VectorObs(), only=only, what="validation only")
@@ -85,8 +67,8 @@ def test_validation_world_and_only_masks(tmp_path):
 
 
 def test_town_large_grid(small_town):
-    cfg = _lights_cfg(small_town, seed=4)
-    hs = _reset_state(cfg, small_town, 128)
+    cfg = S.lights_cfg(small_town, seed=4)
+    hs = S.reset_state(cfg, small_town, 128)
     hs["steps"][...] = np.arange(128) * 3
     rows = _check(cfg, small_town, hs, VectorObs(n_rays=48), what="town")
     assert (rows[:, VectorObs(n_rays=48).slices()["road"]] < 50.0).any()
@@ -94,8 +76,8 @@ def test_town_large_grid(small_town):
 
 def test_town_reference_size_large_grid(town):
     assert town.arrays["maps"]["nx"].max() * town.arrays["maps"]["ny"].max() > 2 ** 21       # (TDE_WORLD_LARGE_GRID)
-    cfg = _lights_cfg(town, seed=6)
-    hs = _reset_state(cfg, town, 64)
+    cfg = S.lights_cfg(town, seed=6)
+    hs = S.reset_state(cfg, town, 64)
     _check(cfg, town, hs, VectorObs(k_neighbours=4, n_rays=16), what="town 1 km")
 
 
@@ -103,9 +85,9 @@ def test_128_crowded_slots():
     from torchdriveenv_amd.synth import synthetic_world
 
     world = synthetic_world(n_scn=4, A=128, seed=5, n_maps=2)
-    cfg = _lights_cfg(world, seed=5)
+    cfg = S.lights_cfg(world, seed=5)
     B, A = 64, 128
-    hs = _reset_state(cfg, world, B)
+    hs = S.reset_state(cfg, world, B)
     rng = np.random.default_rng(7)
     x, y = hs["x"].reshape(B, A), hs["y"].reshape(B, A)
     # every slot present, scattered within 40 m of the ego; a few exact distance ties
@@ -122,10 +104,10 @@ def test_128_crowded_slots():
 
 
 def test_lights_across_phase_changes(small_world):
-    cfg = _lights_cfg(small_world, seed=11)
+    cfg = S.lights_cfg(small_world, seed=11)
     assert cfg.flags & _abi.F_TRAFFIC_LIGHTS
     B = 256
-    hs = _reset_state(cfg, small_world, B)
+    hs = S.reset_state(cfg, small_world, B)
     vo = VectorObs(n_rays=64, ray_range=60.0)
     seen = []
     for k in (0, 40, 79, 80, 95, 120, 145, 159, 160, 400):
@@ -136,9 +118,9 @@ def test_lights_across_phase_changes(small_world):
 
 
 def test_egos_near_the_grid_edge_and_offroad(small_world):
-    cfg = _lights_cfg(small_world, seed=12)
+    cfg = S.lights_cfg(small_world, seed=12)
     B, A = 192, small_world.A
-    hs = _reset_state(cfg, small_world, B)
+    hs = S.reset_state(cfg, small_world, B)
     mp = small_world.arrays["maps"]
     m = small_world.map_of_scn()[hs["scn"]]
     ox, oy = mp["ox"][m], mp["oy"][m]
@@ -176,7 +158,7 @@ def test_closed_loop_with_auto_reset_and_near_field(tmp_path, binding):
     obs = env.reset()
     oracle.env_reset(c, world, hs)
     NF.spawn(c, world, tab, hs)
-    assert np.array_equal(_bits(obs.cpu().numpy()), _bits(R.vector_obs(c, world, hs, vo)))
+    assert np.array_equal(bits(obs.cpu().numpy()), bits(R.vector_obs(c, world, hs, vo)))
     rng = np.random.default_rng(4)
     respawned = 0
     for t in range(50):
@@ -187,7 +169,7 @@ def test_closed_loop_with_auto_reset_and_near_field(tmp_path, binding):
         done = (hs["terminated"] | hs["truncated"]).astype(np.uint8)
         NF.spawn(c, world, tab, hs, done)
         respawned += int(done.sum())
-        assert np.array_equal(_bits(obs.cpu().numpy()), _bits(R.vector_obs(c, world, hs, vo))), t
+        assert np.array_equal(bits(obs.cpu().numpy()), bits(R.vector_obs(c, world, hs, vo))), t
     assert respawned > 0
     # masked reset: only the masked rows change
     before = obs.clone()
@@ -197,7 +179,7 @@ def test_closed_loop_with_auto_reset_and_near_field(tmp_path, binding):
     keep = mask == 0
     assert torch.equal(obs[torch.from_numpy(keep).to(DEV)], before[torch.from_numpy(keep).to(DEV)])
     hs2 = env.state.host()
-    assert np.array_equal(_bits(obs.cpu().numpy()), _bits(R.vector_obs(c, world, hs2, vo)))
+    assert np.array_equal(bits(obs.cpu().numpy()), bits(R.vector_obs(c, world, hs2, vo)))
 
 
 def test_vec_env_terminal_observations(small_world):
@@ -208,7 +190,7 @@ def test_vec_env_terminal_observations(small_world):
     ref = BatchedWaypointEnv(cfg, small_world, num_envs=B, device=DEV, obs_mode="vector", vector_obs=vo, auto_reset=False)
     o1 = venv.reset()
     o2 = ref.reset().cpu().numpy()
-    assert o1.shape == (B, vo.dim) and o1.dtype == np.float32 and np.array_equal(_bits(o1), _bits(o2))
+    assert o1.shape == (B, vo.dim) and o1.dtype == np.float32 and np.array_equal(bits(o1), bits(o2))
     rng = np.random.default_rng(9)
     n_done = 0
     for t in range(40):
@@ -222,9 +204,9 @@ def test_vec_env_terminal_observations(small_world):
             post = ref.reset(mask=torch.from_numpy(done.astype(np.uint8)).to(DEV)).cpu().numpy()
         else:
             post = pre
-        assert np.array_equal(_bits(o1), _bits(post)), t
+        assert np.array_equal(bits(o1), bits(post)), t
         for i in np.flatnonzero(done):
-            assert np.array_equal(_bits(infos[i]["terminal_observation"]), _bits(pre[i])), (t, i)
+            assert np.array_equal(bits(infos[i]["terminal_observation"]), bits(pre[i])), (t, i)
         n_done += int(done.sum())
     assert n_done > 0
 
@@ -239,16 +221,16 @@ def test_two_shards_equal_the_unsharded_batch(small_world):
     two = ShardedBatchedEnv(cfg, small_world, B, n_shards=2, devices=[0, 0], obs_mode="vector", vector_obs=vo)
     try:
         oa, ob = one.reset(), two.reset()
-        assert ob.shape == (B, vo.dim) and ob.dtype == np.float32 and np.array_equal(_bits(oa), _bits(ob))
+        assert ob.shape == (B, vo.dim) and ob.dtype == np.float32 and np.array_equal(bits(oa), bits(ob))
         rng = np.random.default_rng(3)
         n_done = 0
         for t in range(40):
             acts = np.stack([rng.uniform(-1, 1, B), rng.uniform(-0.3, 0.3, B)], -1).astype(np.float32)
             oa, ra, da, ia = one.step(acts)
             ob, rb, db, ib = two.step(acts)
-            assert np.array_equal(_bits(oa), _bits(ob)) and np.array_equal(da, db), t
+            assert np.array_equal(bits(oa), bits(ob)) and np.array_equal(da, db), t
             for i in np.nonzero(da)[0]:
-                assert np.array_equal(_bits(ia[i]["terminal_observation"]), _bits(ib[i]["terminal_observation"]))
+                assert np.array_equal(bits(ia[i]["terminal_observation"]), bits(ib[i]["terminal_observation"]))
             n_done += int(da.sum())
         assert n_done > 0
     finally:
