@@ -359,6 +359,42 @@ TDE_API int tde_score_plans_forecast(const tde_config *cfg, const tde_world *wor
                                      const tde_plan_set *set, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
                                      tde_plan_diag *diag, const float *forecast, int32_t forecast_T, void *stream);
 
+/* Forecast of the whole scene under caller-given ego actions, with the controller's leader sweep kept: for every env with only[e] != 0
+ * (uint8 [B]; NULL: all envs), every slot j - the ego included - and h = 1..T, out[e][h - 1][j] = (x, y, psi, v) of slot j at
+ * environment_steps = state.steps[e] + h when the ego (slot 0) takes ego_action[e][h - 1] at step h (out: DEVICE float32 [B][T][A][4],
+ * tde_forecast_agents' layout except that ROW 0 HOLDS THE EGO'S POSE; absent slots get four zeros; envs with only[e] == 0 are not
+ * touched).  No reference counterpart.  This is the motion half of tde_env_step - every present slot acts on the scene of step h - 1,
+ * then moves - without its judging half: no collision, offroad or stop-line verdict, no reward, no termination, no re-spawn.  None of
+ * those feeds back into motion while an episode lasts, so row h equals, bit for bit and for every slot, what the h-th tde_env_step
+ * with these ego actions leaves in the state as long as the env has not re-spawned.  Rows past an episode's end describe the scene as
+ * if the episode had gone on.  The state is not written; the first-step gap cache is not consulted (it holds the same bits).  Every
+ * expression is float32 with one rounding per written operation (no contraction); bicycle, sincos_f32, the controller, its leader
+ * sweep and the stop-line gap are the step's own (tde_device.h, tde_kernels.h: npc_action, npc_act_of_gap, red_line_gap; the oracle's
+ * tde_npc_action); tests/forecast_scene_ref.py restates this in numpy.
+ * Env e, slot j: everything tde_forecast_agents reads (F, s, m, dt; x, y, psi, v, len, lr, vdes, inv_lr, wp, rec, route, route_n,
+ * replay, replay_len, (tx, ty)) and wid_j; hl_j = 0.5f * len_j, hw_j = 0.5f * wid_j; slot 0 has no route and no replay record.
+ * For h = 1..T, k = state.steps[e] + h, (sp_j, cp_j) = sincos_f32(psi_j) of every slot, all read from the scene of step h - 1 (the
+ * state itself at h = 1) before any slot moves:
+ *   Action       slot 0: (acc, beta) = ego_action[e][h - 1] as given - no clamp, no scaling -, (0, 0) when ego_action is NULL (the ego
+ *                coasts).  Slot i >= 1: tde_forecast_agents' Action line for line - has_target, the (0, 0) exceptions without TDE_F_NPC
+ *                and at k == 1 without TDE_F_NPC_FIRST_STEP, the no-target brake, beta, red_gap, vd, acc - except
+ *                  gap = fminf(lead, red_gap), lead = the least g (fminf from 1e30f) over the present slots j != i of the env, slot 0
+ *                  included, that are taken: ex = x_j - x_i, ey = y_j - y_i, fj = ex*cp_i + ey*sp_i, lj = ey*cp_i - ex*sp_i, al =
+ *                  fabsf(lj), halfw = npc_lane_half + hw_j, hd = cp_i*cp_j + sp_i*sp_j, g = fj - (hl_i + hl_j);
+ *                  inlane = al < halfw; cone = j < i and fj < npc_cone_range and al < halfw + npc_cone_k * fj and hd > -0.5f;
+ *                  taken = fj > 0.0f and (inlane or cone).
+ *   Bicycle, Replay, Route   tde_forecast_agents' (slot 0: the bicycle only).
+ *   Row          out[e][h - 1][j] = (x, y, psi, v), slot 0 included.
+ * One lane per (env, slot), env-major, 256-thread workgroups, the T steps a loop in registers; the env's rows live in the step's LDS
+ * tile with two tile syncs per step (up to 64 slots an env sits inside one wavefront; at 128 it spans two); at every step the lanes of
+ * an env store A consecutive 16-byte rows.  tde_score_plans_forecast reads the result unchanged (it ignores row 0).  Reads state
+ * only.  Rejected: NULL cfg / world / state / out, T outside [1, TDE_FORECAST_MAX_T], config.dt not finite or <= 0, the NULL state /
+ * world arrays tde_forecast_agents rejects, world.maps NULL with TDE_F_OFFROAD or TDE_F_TRAFFIC_LIGHTS.  An empty batch returns 0
+ * before any launch.  No allocation, no synchronisation (graph-capturable). */
+TDE_API int tde_forecast_scene(const tde_config *cfg, const tde_world *world, const tde_state *state, int32_t T,
+                               const float *ego_action /* DEVICE [B][T][2] (acc, steer), or NULL */, const uint8_t *only,
+                               float *out /* DEVICE [B][T][A][4] */, void *stream);
+
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 
 /* Offroad grid index of ONE drivable mesh - what the simulator prepares once per map from the road mesh it is constructed

@@ -234,7 +234,7 @@ def check_vector_obs(vo):
     return vo
 
 
-PLANNER_PREDICT = ("constant", "route")
+PLANNER_PREDICT = ("constant", "route", "queue")
 
 
 @dataclass
@@ -259,7 +259,19 @@ class Planner:
                      nobody (tests/test_gpu_forecast.py) but ignores queues and yielding, and it does not pay yet: on the junction
                      world with lights (512 envs x 400 steps) collision-ended episodes rise from 117 to 244 of ~1040 (with a 40-step
                      tail from 95 to 159) while red-light ends fall from 37 to 9 and offroad ends from 18 to 6
-                     (profiles/forecast_behaviour.txt)"""
+                     (profiles/forecast_behaviour.txt); or "queue": tde_forecast_scene once per call with
+                     the ego coasting - the same rules with the controller's leader sweep kept, so an NPC that queues behind another
+                     car or behind the ego is forecast where the step will put it (bit for bit while the ego does coast:
+                     tests/test_gpu_forecast_scene.py) - and then "route"'s path exactly.  EXPERIMENTAL and opt-in as well.
+                     In the same setting (junction world with lights, 512 envs x 400 steps, seed 7; episodes / infraction ends /
+                     offroad / collision / red light / waypoints per episode):
+                       constant          1035 / 172 / 18 / 117 / 37 / 4.472      constant + tail 40   1032 / 121 / 7 /  95 / 21 / 4.032
+                       route             1062 / 258 /  6 / 244 /  9 / 4.427      route + tail 40      1044 / 166 / 2 / 159 /  6 / 4.090
+                       queue             1028 /  31 /  5 /  18 /  9 / 4.621      queue + tail 40      1026 /  23 / 3 /  15 /  6 / 4.129
+                     so collisions do fall, against "route" and against "constant" - one seed of one world, and NPCs that would
+                     react to the ego's chosen action are still forecast against a coasting ego; no test asserts a ranking.  It
+                     costs 5 - 6 % per step(plan_actions()) over "route" at 8192 x 16
+                     (profiles/forecast_scene_behaviour.txt, profiles/forecast_scene_kernel_stats.txt)"""
     accelerations: tuple = (-1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0)
     steerings: tuple = (-0.3, -0.2, -0.1, 0.0, 0.1, 0.2, 0.3)
     horizon: int = 32

@@ -603,6 +603,26 @@ int tde_forecast_agents(const tde_config *cfg, const tde_world *world, const tde
     return tde_host::launch_forecast_agents(cfg, world, st, T, only, out, stream);
 }
 
+int tde_forecast_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const float *ego_action,
+                       const uint8_t *only, float *out, void *stream)
+{
+    int rc = check_env_args("tde_forecast_scene", cfg, world, st);
+    if (rc) return rc;
+    if (!out) return bad("tde_forecast_scene: NULL argument");
+    if (T < 1 || T > TDE_FORECAST_MAX_T) return bad("tde_forecast_scene: T must be in [1, TDE_FORECAST_MAX_T]");
+    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_forecast_scene: config.dt must be finite and > 0");
+    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
+        !st->steps || !world->spawn || !world->scn)
+        return bad("tde_forecast_scene: a required state / world pointer is NULL");
+    if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad("tde_forecast_scene: world.route_xy is NULL");
+    if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad("tde_forecast_scene: world.replay_states is NULL");
+    if ((cfg->flags & (TDE_F_TRAFFIC_LIGHTS | TDE_F_OFFROAD)) && !world->maps) return bad("tde_forecast_scene: world.maps is NULL");
+    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
+        return bad("tde_forecast_scene: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if (st->B <= 0) return 0;
+    return tde_host::launch_forecast_scene(cfg, world, st, T, ego_action, only, out, stream);
+}
+
 int tde_env_reset_render(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask,
                          const tde_render *rd, void *stream)
 {

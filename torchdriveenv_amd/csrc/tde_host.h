@@ -114,6 +114,9 @@ int launch_score_plans(const tde_config *cfg, const tde_world *world, const tde_
 // tde_forecast.hip: forecast_agents_kernel (tde_forecast_agents; arguments checked by the caller)
 int launch_forecast_agents(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const uint8_t *only, float *out,
                            void *stream);
+// tde_forecast_scene.hip: forecast_scene_kernel<A, LIGHTS> (tde_forecast_scene; arguments checked by the caller)
+int launch_forecast_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const float *ego_action,
+                          const uint8_t *only, float *out, void *stream);
 
 }  // namespace tde_host
 

@@ -26,4 +26,5 @@
 #include "tde_planner.hip"
 #include "tde_plan_set.hip"
 #include "tde_forecast.hip"
+#include "tde_forecast_scene.hip"
 #endif

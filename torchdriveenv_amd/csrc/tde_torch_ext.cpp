@@ -418,6 +418,29 @@ class EnvHandle {
                  "tde_forecast_agents");
     }
 
+    // tde_forecast_scene: out float32 [B, T, A, 4] = (x, y, psi, v) of every slot, the ego included, at each of the next T steps under
+    // ego_actions (float32 [B, T, 2], contiguous; none: the ego coasts), the leader sweep kept (rows of envs outside `only` untouched)
+    void forecast_scene(const at::Tensor &out, const std::optional<at::Tensor> &ego_actions, const std::optional<at::Tensor> &only, int64_t flags)
+    {
+        TORCH_CHECK(out.dim() == 4 && out.size(0) == state_.B && out.size(2) == state_.A && out.size(3) == 4,
+                    "forecast_scene: out must be [B, T, A, 4]");
+        const int64_t T = out.size(1);
+        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, out.numel(), "out", dev_)));
+        const float *pa = nullptr;
+        if (ego_actions) {
+            const at::Tensor &ea = *ego_actions;
+            TORCH_CHECK(ea.dim() == 3 && ea.size(0) == state_.B && ea.size(1) == T && ea.size(2) == 2, "forecast_scene: ego_actions must be [B, T, 2]");
+            TORCH_CHECK(ea.is_contiguous(), "forecast_scene: ego_actions must be contiguous (no copy of it is made)");
+            pa = static_cast<const float *>(dev_ptr(ea, at::kFloat, (int64_t)state_.B * T * 2, "ego_actions", dev_));
+        }
+        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        cfg_.flags = static_cast<uint32_t>(flags);
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_forecast_scene(&cfg_, &world_, &state_, (int32_t)T, pa, m, p,
+                                    c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                 "tde_forecast_scene");
+    }
+
     // tde_ego_infractions: float32 [B, 4] = the ego's (offroad, collision, overlap count, 0) magnitudes of the state as it is (gym_env.py:427-428)
     void ego_infractions(const at::Tensor &out, int64_t flags)
     {
@@ -594,6 +617,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
              py::arg("fail_step"), py::arg("horizon"), py::arg("v_target"), py::arg("margin"), py::arg("w_progress"), py::arg("w_speed"),
              py::arg("w_steer"), py::arg("only"), py::arg("action"), py::arg("diag"), py::arg("flags"), py::arg("forecast") = py::none())
         .def("forecast_agents", &EnvHandle::forecast_agents, py::arg("out"), py::arg("only"), py::arg("flags"))
+        .def("forecast_scene", &EnvHandle::forecast_scene, py::arg("out"), py::arg("ego_actions"), py::arg("only"), py::arg("flags"))
         .def_property_readonly("flags", &EnvHandle::flags)
         .def_property_readonly("num_envs", &EnvHandle::num_envs)
         .def_property_readonly("agents_per_env", &EnvHandle::agents_per_env);

@@ -644,7 +644,7 @@ class BatchedWaypointEnv:
                                   _box(-np.inf, np.inf, (self.vector_obs.dim if obs_mode == "vector" else 8,), np.float32))
         self._vobs = self._ray_dir = None
         self._plan_out = self._plan_diag = self._plan_struct = self._refine = None
-        self._plan_fc = self._plan_lat = None          # planner.predict == "route": the forecast buffer, the lattice as one-knot sequences
+        self._plan_fc = self._plan_lat = None          # planner.predict == "route" / "queue": the forecast buffer, the lattice as one-knot sequences
         if obs_mode == "vector":
             self._vobs = torch.zeros((self.num_envs, self.vector_obs.dim), dtype=torch.float32, device=self.torch_device)
             self._ray_dir = torch.from_numpy(self.vector_obs.ray_directions()).to(self.torch_device)
@@ -845,7 +845,8 @@ class BatchedWaypointEnv:
         buffer, overwritten by the next call); only: uint8 [B] on the device, the other rows are left as they are; diag=True: returns
         (actions, int32 [B, 4] rows of winner, fail_step, the cost's float32 bits, n_safe - n_safe == 0: no candidate is safe).
         With planner.predict == "route" the other agents are where tde_forecast_agents puts them (one forecast per call, horizon + tail
-        steps) and the lattice is judged as one-knot sequences by tde_score_plans_forecast; "constant" (default) is the path as it was."""
+        steps) and the lattice is judged as one-knot sequences by tde_score_plans_forecast; with "queue" they are where tde_forecast_scene
+        puts them while the ego coasts (the leader sweep kept), judged the same way; "constant" (default) is the path as it was."""
         if out is None:
             if self._plan_out is None:
                 self._plan_out = torch.zeros((self.num_envs, 2), dtype=torch.float32, device=self.torch_device)
@@ -859,11 +860,11 @@ class BatchedWaypointEnv:
             only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         pl = self.planner
         fc = None
-        if pl.predict == "route":
+        if pl.predict in ("route", "queue"):
             T = int(pl.horizon) + (int(self.plan_refine.tail) if self.plan_refine is not None else 0)
             if self._plan_fc is None:
                 self._plan_fc = torch.zeros((self.num_envs, T, self.A, 4), dtype=torch.float32, device=self.torch_device)
-            fc = self._forecast(self._plan_fc, only)
+            fc = self._forecast(self._plan_fc, only) if pl.predict == "route" else self._forecast_scene(self._plan_fc, None, only)
         if self.plan_refine is not None:
             if self._plan_diag is None:
                 self._plan_diag = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.torch_device)
@@ -910,6 +911,40 @@ class BatchedWaypointEnv:
         else:
             ops.forecast_agents(self.tde_cfg, self.dworld, self.state, out.shape[1], only, out)
         return out
+
+    def _forecast_scene(self, out, ego_actions, only):
+        """tde_forecast_scene into `out` (float32 [B, T, A, 4]) through the env's binding (arguments already checked) -> out"""
+        if self._h is not None:
+            self._h.forecast_scene(out, ego_actions, only, int(self.tde_cfg.flags))
+        else:
+            ops.forecast_scene(self.tde_cfg, self.dworld, self.state, out.shape[1], ego_actions, only, out)
+        return out
+
+    def forecast_scene(self, T=None, ego_actions=None, only=None, out=None):
+        """where the environment's own rules put EVERY agent, the ego included, at each of the next T steps when the ego takes
+        `ego_actions` (tde_forecast_scene) -> float32 [B, T, A, 4] on the device: row [e, h - 1, j] = (x, y, psi, v) of slot j at
+        environment step steps[e] + h; row 0 is the ego's pose; zeros for absent slots.  Unlike forecast_agents() the controller's leader
+        sweep is kept: NPCs queue behind one another and behind the ego, so the next T step() calls with these actions leave exactly
+        these rows, bit for bit, for as long as the env does not re-spawn (nothing is judged here: rows past an episode's end go on
+        as if it had not ended).  T: 1 .. 96 (None: the planner's horizon); ego_actions: a contiguous float32 [B, T, 2] device tensor of
+        (acceleration, steering), taken as given - no clamp, no scaling; None: the ego coasts; only: uint8 [B], the other envs' rows
+        are left as they are (zeros in a fresh buffer); out: a float32 [B, T, A, 4] device tensor to write into.  The state is not
+        written.  score_plans(forecast=) takes the result (it ignores row 0)."""
+        T = int(self.planner.horizon) if T is None else T
+        if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
+            raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
+        shape = (self.num_envs, int(T), self.A, 4)
+        if ego_actions is not None:
+            ops.check_ego_actions(ego_actions, self.num_envs, int(T))
+            if ego_actions.device != self.torch_device:
+                raise ValueError(f"ego_actions is on {ego_actions.device}, expected {self.torch_device}")
+        if out is None:
+            out = (torch.empty if only is None else torch.zeros)(shape, dtype=torch.float32, device=self.torch_device)
+        elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+        if only is not None:
+            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
+        return self._forecast_scene(out, ego_actions, only)
 
     def forecast_agents(self, T=None, only=None, out=None):
         """where the environment's own rules put every other agent at each of the next T steps when nobody is in its cone

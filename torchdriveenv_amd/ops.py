@@ -346,6 +346,41 @@ def forecast_agents(cfg, dworld, state, T, only=None, out=None):
     return out
 
 
+def check_ego_actions(ego_actions, B, T):
+    """the shape checks of forecast_scene's ego actions that need no GPU: float32 [B, T, 2], contiguous (no silent copy)"""
+    if not torch.is_tensor(ego_actions) or ego_actions.dtype != torch.float32:
+        raise ValueError("ego_actions must be a float32 torch tensor")
+    if tuple(ego_actions.shape) != (int(B), int(T), 2):
+        raise ValueError(f"ego_actions must be [B={int(B)}, T={int(T)}, 2], got {tuple(ego_actions.shape)}")
+    if not ego_actions.is_contiguous():
+        raise ValueError("ego_actions must be contiguous (no copy of it is made)")
+
+
+def forecast_scene(cfg, dworld, state, T, ego_actions=None, only=None, out=None):
+    """tde_forecast_scene: (x, y, psi, v) of every slot, the ego (row 0) included, at each of the next T steps with the controller's
+    leader sweep kept -> float32 [B, T, A, 4] on the device (zeros for absent slots): what T calls of tde_env_step with these ego
+    actions leave in the state while no env re-spawns.  ego_actions: float32 [B, T, 2] device tensor of (acceleration, steering),
+    contiguous, taken as given; None: the ego coasts.  only: uint8 [B], the other envs' rows of `out` are left as they are; out: a
+    float32 [B, T, A, 4] device tensor to write into.  Asynchronous."""
+    L = _lib.load()
+    dev = torch.device(state.device)
+    if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
+        raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
+    T = int(T)
+    if ego_actions is not None:
+        check_ego_actions(ego_actions, state.B, T)
+    if out is None:
+        out = (torch.empty if only is None else torch.zeros)((state.B, T, state.A, 4), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (state.B, T, state.A, 4):
+        raise ValueError(f"out must be [B={state.B}, T={T}, A={state.A}, 4], got {tuple(out.shape)}")
+    po = _chk(out, torch.float32, state.B * T * state.A * 4, "out", dev)
+    pa = _chk(ego_actions, torch.float32, state.B * T * 2, "ego_actions", dev, optional=True)
+    pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
+    _lib.check(_call(dev, L.tde_forecast_scene, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), T, pa, pm, po,
+                     _lib.current_stream(dev)), "tde_forecast_scene")
+    return out
+
+
 def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, action=None, diag=None,
                 forecast=None):
     """tde_score_plans: how each of N action sequences per env fares on the state as it is -> (cost float32 [B, N], fail_step int32
