@@ -46,10 +46,11 @@ def _batch(A):
     return {4: 65, 16: 33, 64: km._small_B(64)(_cu()), 128: 3}[A]
 
 
-def _mid_episode_state(cfg, world, B, seed):
+def _mid_episode_state(cfg, world, B, seed, **over):
     """25 oracle steps under random ego actions with auto-reset, then every fourth env reset again (step 0: the first-step rule) and
-    every other env's step counter moved on (the lights' phase and the replay records follow it)"""
-    drive = S.lights_cfg(world, seed=seed, terminated_at_infraction=1)
+    every other env's step counter moved on (the lights' phase and the replay records follow it).  over: tde_config fields of the drive
+    (tests/test_gpu_config_zoo.py)"""
+    drive = S.lights_cfg(world, seed=seed, terminated_at_infraction=1, **over)
     drive.flags = cfg.flags | _abi.F_AUTORESET
     hs = S.reset_state(drive, world, B)
     rng = np.random.default_rng(seed)

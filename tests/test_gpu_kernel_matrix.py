@@ -22,8 +22,8 @@ from torchdriveenv_amd.state import EnvState  # noqa: E402
 from torchdriveenv_amd.synth import synthetic_town, synthetic_world  # noqa: E402
 
 DEV = "cuda:0"
-T = 30                  # steps per group (max_steps 20: every env re-spawns at least once)
-CHECK = (0, 2, T - 1)   # steps after which the whole state is compared
+T = 30                  # steps per group (max_steps 20: every env re-spawns at least once); the whole state is compared after
+                        # the steps of _check_steps(T)
 AGENT_KEYS = set(_abi.STATE_AGENT_F32 + _abi.STATE_AGENT_I32 + _abi.STATE_AGENT_U8)
 CACHE_KEYS = {"slot_cache", "env_cache", "act_cache"}
 GROUPS = km.groups()
@@ -67,7 +67,11 @@ def _slices(B, cuts):
     return out
 
 
-def _actions(B, seed):
+def _check_steps(T):
+    return (0, 2, T - 1)
+
+
+def _actions(B, seed, T=T):
     """[T, B, 2]: half the egos drive on steadily (they reach the stop lines), half swerve (offroad, collisions)"""
     rng = np.random.default_rng(seed)
     careful = (np.arange(B) % 2) == 0
@@ -92,14 +96,15 @@ def _cut(arrays, A, lo, hi, skip=()):
 
 
 class _Oracle:
-    """the oracle on slices of the batch: per step the rewards, done bits, magnitudes; the whole state after the CHECK steps"""
+    """the oracle on slices of the batch: per step the rewards, done bits, magnitudes; the whole state after the check steps
+    (of a run of T steps: the first, the third and the last)"""
 
-    def __init__(self, cfg, world, A, slices, actions):
-        self.slices, self.A = slices, A
+    def __init__(self, cfg, world, A, slices, actions, T=T):
+        self.slices, self.A, self.T, self.check = slices, A, T, _check_steps(T)
         self.reward = np.zeros((T, actions.shape[1]), np.float32)
         self.done = np.zeros((T, actions.shape[1]), np.uint8)
         self.mag = np.zeros((T, actions.shape[1], 4), np.float32)
-        self.reset, self.snap = {}, {t: {} for t in CHECK}
+        self.reset, self.snap = {}, {t: {} for t in self.check}
         for lo, hi in slices:
             c = _abi.TdeConfig.from_buffer_copy(cfg)
             c.env_base = lo
@@ -110,7 +115,7 @@ class _Oracle:
                 hs["action"][...] = actions[t, lo:hi]
                 oracle.env_step(c, world, hs)
                 self.reward[t, lo:hi], self.done[t, lo:hi], self.mag[t, lo:hi] = hs["reward"], hs["done_bits"], hs["magnitudes"]
-                if t in CHECK:
+                if t in self.check:
                     self.snap[t][lo] = hs.host()
 
     def events(self):
@@ -131,7 +136,7 @@ class _Oracle:
                 assert np.array_equal(mag[lo:hi].view(np.uint32), self.mag[t, lo:hi].view(np.uint32)), f"magnitudes: {where} [{lo}, {hi}) step {t}"
 
 
-def _step_case(c, cfg, dw, B, A, acts, want):
+def _step_case(c, cfg, dw, B, A, acts, want, T=T):
     where = c.id()
     d = EnvState(B, A, device=DEV, with_obs=c.obs, with_magnitudes=c.mag, with_cache=c.cache)
     ops.env_reset(cfg, dw, d)
@@ -151,7 +156,7 @@ def _step_case(c, cfg, dw, B, A, acts, want):
             mag = mag2 if post else d["magnitudes"]
             want.check_step(t, d["reward"].cpu().numpy(), d["done_bits"].cpu().numpy(), where,
                             None if mag is None else mag.cpu().numpy())
-            if t in CHECK:
+            if t in _check_steps(T):
                 want.check_state(d.host(), t, where, skip=("magnitudes",))
                 if c.obs:
                     got, ref = d["obs"], ops.state_obs(dw, d)
@@ -160,7 +165,7 @@ def _step_case(c, cfg, dw, B, A, acts, want):
         _lib.kernel_override()
 
 
-def _rollout_case(c, cfg, dw, B, A, acts, want):
+def _rollout_case(c, cfg, dw, B, A, acts, want, T=T):
     where = c.id()
     d = EnvState(B, A, device=DEV, with_episode=False, with_magnitudes=False)
     ops.env_reset(cfg, dw, d)

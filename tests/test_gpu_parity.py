@@ -147,7 +147,9 @@ def assert_state_equal(hs, ds, where):
         if k == "info":
             # float64 info terms: bit-exact except psi_reward (column 2), whose float64 cosine is libm on the CPU and the
             # kernel's cos_heading_f64 on the GPU - both faithfully rounded, so the term may differ by one ulp of the
-            # cosine times the penalty (test_reward_cos_bits_agree_between_libm_and_ocml quantifies it)
+            # cosine times the penalty (test_reward_cos_bits_agree_between_libm_and_ocml quantifies it).  The bound below is that
+            # product for heading_penalty <= 25 (1 - cos lies in [0, 2]: an ulp there is at most 2.2e-16, times 25 = 5.6e-15); the
+            # config zoo (tests/config_zoo.py) keeps every heading_penalty at or below 25, so it holds there unchanged
             a2, b2 = np.asarray(a).reshape(-1, 4), np.asarray(b).reshape(-1, 4)
             for col in (0, 1, 3):
                 assert np.array_equal(a2[:, col].view(np.uint64), b2[:, col].view(np.uint64)), f"info[{col}] differs at {where}"
