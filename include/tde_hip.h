@@ -395,6 +395,40 @@ TDE_API int tde_forecast_scene(const tde_config *cfg, const tde_world *world, co
                                const float *ego_action /* DEVICE [B][T][2] (acc, steer), or NULL */, const uint8_t *only,
                                float *out /* DEVICE [B][T][A][4] */, void *stream);
 
+/* tde_score_plans with every sequence judged in a scene that reacts to it: for every env with only[e] != 0 (uint8 [B]; NULL: all envs)
+ * and every sequence n, a scene of its own in which the ego takes that sequence's actions and every other slot runs the controller with
+ * its leader sweep over THAT scene - tde_forecast_scene's rule - while the ego's box is judged against it step by step.  Arguments and
+ * outputs are tde_score_plans'.  No reference counterpart.  Every line of the tde_score_plans specification holds (Knots, Horizon,
+ * Brake tail, Cost, Winner, `only`, action, diag) except
+ *   Others      for sequence n of env e the other agents are where tde_forecast_scene (above; every float32 expression is stated there)
+ *               puts them with T = H + tail and the ego actions ego_action[h - 1] = (a_h, d_h) for h in 1..H - a_h the clamped knot
+ *               acceleration after the no-reverse rule (0.0f when v + a * dt < 0.0f), d_h the clamped knot steering - and (-1.0f, d_H)
+ *               at the tail steps for as long as the sequence is still judged.  At horizon or tail step h the box of present slot
+ *               j >= 1 (presence, len_j and wid_j from the state) is (x, y, c, s, 0.5f * len_j + margin, 0.5f * wid_j + margin) with
+ *               (x, y, psi) = that scene's row h and (s, c) = sincos_f32(psi): tde_score_plans_forecast's Others.
+ *   Ego         the judged trajectory is tde_score_plans' Trajectory - bicycle(x, y, psi, v, inv_lr, a_h, d_h, dt) with inv_lr = 1.0f /
+ *               lr_0 from the state as it is - and the ego's row of the scene is that pose: the same bicycle on the same inputs as
+ *               tde_forecast_scene's slot 0.  Should the two ever differ in a bit, the judge's expression is the specification.  An
+ *               absent slot 0 is judged all the same (tde_score_plans reads no presence of the ego); the others do not see it.
+ * Contract: cost[e][n] and fail_step[e][n] equal, bit for bit, what tde_score_plans_forecast returns for sequence n alone when given
+ * tde_forecast_scene(T = H + tail, ego_action = n's effective actions) as its forecast.  Rows after a sequence has failed or stands
+ * are never read, so what its scene does after that is unspecified.  With margin = 0 fail_step is the step at which tde_env_step
+ * would end the episode by an infraction (collision, offroad, red line) if those actions were taken; the three predicates are the
+ * step's own (obb_overlap, the offroad test of the four corners, tde_tl_violation's expression).  The first-step gap cache is not
+ * consulted.  tests/plan_scene_ref.py restates this by composition in numpy.
+ * One lane per (env, sequence, slot), sequence-major inside an env, 256-thread workgroups, the scene's rows in the step's LDS tile
+ * with two tile syncs per step; no forecast is written.  With action or diag != NULL a second kernel on the same stream (one
+ * wavefront per env) reduces cost and fail_step to the Winner.  Reads state only.  Rejected: everything tde_score_plans and
+ * tde_forecast_scene reject (NULL cfg / world / state / plan / set / set.seq / cost / fail_step, N, K, knot_len, tail and horizon out
+ * of range, v_target / margin / a weight negative or not finite, config.dt not finite or <= 0, a NULL array among the state's x, y,
+ * psi, v, len, wid, lr, vdes, route_wp, present, scn, steps, target_idx or the world's tables), and a launch grid that is too large:
+ * B * N * A must not exceed TDE_PLAN_SCENE_MAX_LANES = 2^31 - 256 lanes.  An empty batch returns 0 before any launch.  No allocation,
+ * no synchronisation (graph-capturable). */
+#define TDE_PLAN_SCENE_MAX_LANES 2147483392LL
+TDE_API int tde_score_plans_scene(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_planner *plan,
+                                  const tde_plan_set *set, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
+                                  tde_plan_diag *diag, void *stream);
+
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 
 /* Offroad grid index of ONE drivable mesh - what the simulator prepares once per map from the road mesh it is constructed

@@ -166,6 +166,7 @@ class TdePlanSet(C.Structure):
 
 PLAN_MAX_SET, PLAN_MAX_TAIL = 1024, 64
 FORECAST_MAX_T = PLAN_MAX_H + PLAN_MAX_TAIL      # TDE_FORECAST_MAX_T: steps of tde_forecast_agents / tde_forecast_scene / tde_score_plans_forecast
+PLAN_SCENE_MAX_LANES = 2**31 - 256                # TDE_PLAN_SCENE_MAX_LANES (tde_hip.h): B * N * A of tde_score_plans_scene
 PLAN_BOX_ACCEL, PLAN_BOX_STEER = 1.0, 0.3
 
 LAYER_BLANK = 5

@@ -344,6 +344,37 @@ def check_plan_refine(pr, planner=None):
     return pr
 
 
+@dataclass
+class PlanReact:
+    """plan_actions() with every lattice candidate judged in a scene that reacts to it (tde_score_plans_scene, include/tde_hip.h):
+    the candidates are one-knot sequences; for each of them the other agents run the controller - leader sweep included - against
+    the ego that takes THAT candidate, where Planner(predict="queue") forecasts them once against a coasting ego.  A follower then
+    brakes for a candidate that brakes, and an NPC yields - or does not - to a candidate that pulls out in front of it.
+      tail           brake-tail steps after the horizon, 0 .. 64 (PlanRefine's tail; there are no refinement rounds here)
+    Needs Planner(predict="constant") (the scene replaces the prediction) and excludes plan_refine.
+    EXPERIMENTAL and opt-in: on the junction world with lights (512 envs x 400 steps, seed 7) collision-ended episodes fall from 18 to
+    14 against predict="queue" (with the 40-step tail from 15 to 12) but infraction ends as a whole do not move (31 -> 32, 23 -> 21),
+    at 6.4 (4.6) times the time per step(plan_actions()) at 8192 x 16: it does not clearly pay as a planner setting
+    (profiles/plan_scene_behaviour.txt, profiles/plan_scene_kernel_stats.txt).  The primitive behind it -
+    score_plans(react=True), an exact look-ahead of the environment - stands on its exactness tests."""
+    tail: int = 40
+
+
+def check_plan_react(pr, planner=None, plan_refine=None):
+    """validate a PlanReact (a dict is accepted as PlanReact(**dict)) against the Planner and PlanRefine it comes with; returns it"""
+    if isinstance(pr, dict):
+        pr = PlanReact(**pr)
+    if not isinstance(pr, PlanReact):
+        raise TypeError("plan_react must be a PlanReact (or a dict of its fields)")
+    if isinstance(pr.tail, bool) or int(pr.tail) != pr.tail or not (0 <= int(pr.tail) <= 64):
+        raise ValueError("plan_react: tail must be an integer in [0, 64]")
+    if plan_refine is not None:
+        raise ValueError("plan_react with plan_refine: the scene judge has no refinement rounds (choose one)")
+    if planner is not None and planner.predict != "constant":
+        raise ValueError(f"plan_react needs Planner(predict='constant'): the scene replaces the prediction, got {planner.predict!r}")
+    return pr
+
+
 def check_planner(pl):
     """validate a Planner (tde_plan_action rejects the same); returns it (a dict is accepted as Planner(**dict))"""
     import numpy as np

@@ -623,6 +623,37 @@ int tde_forecast_scene(const tde_config *cfg, const tde_world *world, const tde_
     return tde_host::launch_forecast_scene(cfg, world, st, T, ego_action, only, out, stream);
 }
 
+int tde_score_plans_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
+                          const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream)
+{
+    int rc = check_env_args("tde_score_plans_scene", cfg, world, st);
+    if (rc) return rc;
+    if (!pl || !ps || !ps->seq || !cost || !fail_step) return bad("tde_score_plans_scene: NULL argument");
+    if (ps->N < 1 || ps->N > TDE_PLAN_MAX_SET) return bad("tde_score_plans_scene: N must be in [1, TDE_PLAN_MAX_SET]");
+    if (ps->K < 1 || ps->K > TDE_PLAN_MAX_H) return bad("tde_score_plans_scene: K must be in [1, TDE_PLAN_MAX_H]");
+    if (ps->knot_len < 1) return bad("tde_score_plans_scene: knot_len must be >= 1");
+    if (ps->tail < 0 || ps->tail > TDE_PLAN_MAX_TAIL) return bad("tde_score_plans_scene: tail must be in [0, TDE_PLAN_MAX_TAIL]");
+    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return bad("tde_score_plans_scene: horizon must be in [1, TDE_PLAN_MAX_H]");
+    const float nn[5] = {pl->v_target, pl->margin, pl->w_progress, pl->w_speed, pl->w_steer};
+    for (int i = 0; i < 5; ++i)
+        if (!(nn[i] >= 0.0f && nn[i] <= FLT_MAX))
+            return bad("tde_score_plans_scene: v_target, margin and the weights must be finite and >= 0");
+    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_score_plans_scene: config.dt must be finite and > 0");
+    // what the judge reads (tde_score_plans) and what the scene reads (tde_forecast_scene)
+    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
+        !st->steps || !st->target_idx || !world->maps || !world->scn || !world->spawn || !world->wp_xy || !world->cell_word ||
+        !world->cell_cls2 || !world->cell_coarse || !world->cell_tri)
+        return bad("tde_score_plans_scene: a required state / world pointer is NULL");
+    if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad("tde_score_plans_scene: world.route_xy is NULL");
+    if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad("tde_score_plans_scene: world.replay_states is NULL");
+    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
+        return bad("tde_score_plans_scene: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if (st->B <= 0) return 0;
+    if ((int64_t)st->B * ps->N * st->A > TDE_PLAN_SCENE_MAX_LANES)
+        return bad("tde_score_plans_scene: B * N * A exceeds TDE_PLAN_SCENE_MAX_LANES (the launch grid)");
+    return tde_host::launch_score_plans_scene(cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream);
+}
+
 int tde_env_reset_render(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask,
                          const tde_render *rd, void *stream)
 {

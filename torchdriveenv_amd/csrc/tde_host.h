@@ -117,6 +117,9 @@ int launch_forecast_agents(const tde_config *cfg, const tde_world *world, const 
 // tde_forecast_scene.hip: forecast_scene_kernel<A, LIGHTS> (tde_forecast_scene; arguments checked by the caller)
 int launch_forecast_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const float *ego_action,
                           const uint8_t *only, float *out, void *stream);
+// tde_plan_scene.hip: score_plans_scene_kernel<A, LIGHTS> and plan_scene_winner_kernel (tde_score_plans_scene; arguments checked by the caller)
+int launch_score_plans_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
+                             const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream);
 
 }  // namespace tde_host
 

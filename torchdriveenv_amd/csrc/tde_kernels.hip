@@ -27,4 +27,5 @@
 #include "tde_plan_set.hip"
 #include "tde_forecast.hip"
 #include "tde_forecast_scene.hip"
+#include "tde_plan_scene.hip"
 #endif

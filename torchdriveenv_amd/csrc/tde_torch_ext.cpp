@@ -363,6 +363,25 @@ class EnvHandle {
                      const std::optional<at::Tensor> &only, const std::optional<at::Tensor> &action,
                      const std::optional<at::Tensor> &diag, int64_t flags, const std::optional<at::Tensor> &forecast)
     {
+        score_plans_any(seq, knot_len, tail, cost, fail_step, horizon, v_target, margin, w_progress, w_speed, w_steer, only, action, diag, flags,
+                        forecast, false);
+    }
+
+    // tde_score_plans_scene: score_plans' arguments, tensor checks and outputs; every sequence is judged in a scene that reacts to it
+    void score_plans_scene(const at::Tensor &seq, int64_t knot_len, int64_t tail, const at::Tensor &cost, const at::Tensor &fail_step,
+                           int64_t horizon, double v_target, double margin, double w_progress, double w_speed, double w_steer,
+                           const std::optional<at::Tensor> &only, const std::optional<at::Tensor> &action,
+                           const std::optional<at::Tensor> &diag, int64_t flags)
+    {
+        score_plans_any(seq, knot_len, tail, cost, fail_step, horizon, v_target, margin, w_progress, w_speed, w_steer, only, action, diag, flags,
+                        std::nullopt, true);
+    }
+
+    void score_plans_any(const at::Tensor &seq, int64_t knot_len, int64_t tail, const at::Tensor &cost, const at::Tensor &fail_step,
+                         int64_t horizon, double v_target, double margin, double w_progress, double w_speed, double w_steer,
+                         const std::optional<at::Tensor> &only, const std::optional<at::Tensor> &action,
+                         const std::optional<at::Tensor> &diag, int64_t flags, const std::optional<at::Tensor> &forecast, bool scene)
+    {
         TORCH_CHECK(seq.dim() == 4 && seq.size(0) == state_.B && seq.size(3) == 2, "score_plans: seq must be [B, N, K, 2]");
         TORCH_CHECK(seq.is_contiguous(), "score_plans: seq must be contiguous (no copy of it is made)");
         const int64_t N = seq.size(1), K = seq.size(2);
@@ -397,6 +416,12 @@ class EnvHandle {
             check_rc(tde_score_plans_forecast(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d, pfc, (int32_t)fc.size(1),
                                               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
                      "tde_score_plans_forecast");
+            return;
+        }
+        if (scene) {
+            check_rc(tde_score_plans_scene(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d,
+                                           c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+                     "tde_score_plans_scene");
             return;
         }
         check_rc(tde_score_plans(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d,
@@ -616,6 +641,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         .def("score_plans", &EnvHandle::score_plans, py::arg("seq"), py::arg("knot_len"), py::arg("tail"), py::arg("cost"),
              py::arg("fail_step"), py::arg("horizon"), py::arg("v_target"), py::arg("margin"), py::arg("w_progress"), py::arg("w_speed"),
              py::arg("w_steer"), py::arg("only"), py::arg("action"), py::arg("diag"), py::arg("flags"), py::arg("forecast") = py::none())
+        .def("score_plans_scene", &EnvHandle::score_plans_scene, py::arg("seq"), py::arg("knot_len"), py::arg("tail"), py::arg("cost"),
+             py::arg("fail_step"), py::arg("horizon"), py::arg("v_target"), py::arg("margin"), py::arg("w_progress"), py::arg("w_speed"),
+             py::arg("w_steer"), py::arg("only"), py::arg("action"), py::arg("diag"), py::arg("flags"))
         .def("forecast_agents", &EnvHandle::forecast_agents, py::arg("out"), py::arg("only"), py::arg("flags"))
         .def("forecast_scene", &EnvHandle::forecast_scene, py::arg("out"), py::arg("ego_actions"), py::arg("only"), py::arg("flags"))
         .def_property_readonly("flags", &EnvHandle::flags)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _abi, ops
-from .config import (EnvConfig, NearField, Planner, VectorObs, WaypointSuite, check_near_field, check_plan_refine, check_planner, check_vector_obs,
+from .config import (EnvConfig, NearField, Planner, VectorObs, WaypointSuite, check_near_field, check_plan_react, check_plan_refine, check_planner, check_vector_obs,
                      render_flags, to_tde_config, validate)
 from .state import EnvState
 from .video import VideoRecorder
@@ -540,7 +540,7 @@ class BatchedWaypointEnv:
     def __init__(self, cfg: EnvConfig, data, num_envs, agents_per_env=16, device=None, obs_mode="birdview",
                  frame_stack=1, auto_reset=True, with_info=True, background=None, env_base=0, binding="ext",
                  info_magnitudes=True, road_meshes=None, near_range=None, traffic_lights=None, start_headings=None, light_radius=150.0,
-                 heading_samples=16, near_field=None, vector_obs=None, planner=None, plan_refine=None):
+                 heading_samples=16, near_field=None, vector_obs=None, planner=None, plan_refine=None, plan_react=None):
         """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp), "ctypes" = through
         the ctypes binding of the same C-ABI (ops.py); both call the very same entry points of libtde_hip.so.
         info_magnitudes (default): info["offroad"] / info["collision"] hold the MAGNITUDES the reference reports there (ref
@@ -562,10 +562,14 @@ class BatchedWaypointEnv:
         float32 [B, vector_obs.dim] (tde_vector_obs), taken after every reset, step and re-spawn (after the near-field spawner).
         planner: the config.Planner (or a dict of its fields) of plan_actions() (None: Planner()).
         plan_refine: a config.PlanRefine (or a dict of its fields): plan_actions() then judges the lattice with a brake tail and
-        refines the winner knot by knot through tde_score_plans.  None (default): plan_actions() is tde_plan_action as it was."""
+        refines the winner knot by knot through tde_score_plans.  None (default): plan_actions() is tde_plan_action as it was.
+        plan_react: a config.PlanReact (or a dict of its fields): plan_actions() then judges every lattice candidate in a scene that
+        reacts to it (tde_score_plans_scene).  Not with plan_refine, and only with Planner(predict="constant").  None (default):
+        nothing changes."""
         validate(cfg)
         self.planner = check_planner(planner if planner is not None else Planner())
         self.plan_refine = check_plan_refine(plan_refine, self.planner) if plan_refine is not None else None
+        self.plan_react = check_plan_react(plan_react, self.planner, self.plan_refine) if plan_react is not None else None
         if near_field is not None and not isinstance(near_field, NearFieldTable):
             near_field = check_near_field(near_field, cfg)
         if near_field is not None and cfg.ego_only:
@@ -846,7 +850,9 @@ class BatchedWaypointEnv:
         (actions, int32 [B, 4] rows of winner, fail_step, the cost's float32 bits, n_safe - n_safe == 0: no candidate is safe).
         With planner.predict == "route" the other agents are where tde_forecast_agents puts them (one forecast per call, horizon + tail
         steps) and the lattice is judged as one-knot sequences by tde_score_plans_forecast; with "queue" they are where tde_forecast_scene
-        puts them while the ego coasts (the leader sweep kept), judged the same way; "constant" (default) is the path as it was."""
+        puts them while the ego coasts (the leader sweep kept), judged the same way; "constant" (default) is the path as it was.
+        With self.plan_react the lattice is judged as one-knot sequences by tde_score_plans_scene (every candidate in a scene that
+        reacts to it) with plan_react.tail steps of brake tail."""
         if out is None:
             if self._plan_out is None:
                 self._plan_out = torch.zeros((self.num_envs, 2), dtype=torch.float32, device=self.torch_device)
@@ -859,6 +865,10 @@ class BatchedWaypointEnv:
         if only is not None:
             only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         pl = self.planner
+        if self.plan_react is not None:
+            la = self._plan_lattice()
+            self._score_plans(la["seq"], int(pl.horizon), int(self.plan_react.tail), only, la["cost"], la["fail"], out, d, react=True)
+            return (out, d) if diag else out
         fc = None
         if pl.predict in ("route", "queue"):
             T = int(pl.horizon) + (int(self.plan_refine.tail) if self.plan_refine is not None else 0)
@@ -871,14 +881,7 @@ class BatchedWaypointEnv:
             self._plan_refined(out, only, self._plan_diag, fc)
             return (out, self._plan_diag) if diag else out
         if fc is not None:
-            if self._plan_lat is None:
-                B, nc, dev = self.num_envs, pl.n_candidates, self.torch_device
-                acc, ste = pl.tables()
-                lat = np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(np.float32)      # [nc, 2]: candidate i = ia * n_s + is
-                self._plan_lat = {"seq": torch.from_numpy(lat).to(dev)[None, :, None, :].expand(B, nc, 1, 2).contiguous(),
-                                  "cost": torch.zeros((B, nc), dtype=torch.float32, device=dev),
-                                  "fail": torch.zeros((B, nc), dtype=torch.int32, device=dev)}
-            la = self._plan_lat
+            la = self._plan_lattice()
             self._score_plans(la["seq"], int(pl.horizon), 0, only, la["cost"], la["fail"], out, d, fc)
             return (out, d) if diag else out
         if self._h is not None:
@@ -891,9 +894,33 @@ class BatchedWaypointEnv:
             ops.plan_action(self.tde_cfg, self.dworld, self.state, self._plan_struct, out, only, d)
         return (out, d) if diag else out
 
-    def _score_plans(self, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast=None):
-        """tde_score_plans (forecast: tde_score_plans_forecast) through the env's binding (arguments already checked)"""
+    def _plan_lattice(self):
+        """the planner's lattice as one-knot sequences [B, nc, 1, 2] with their cost / fail_step buffers (made once)"""
+        if self._plan_lat is None:
+            pl = self.planner
+            B, nc, dev = self.num_envs, pl.n_candidates, self.torch_device
+            acc, ste = pl.tables()
+            lat = np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(np.float32)      # [nc, 2]: candidate i = ia * n_s + is
+            self._plan_lat = {"seq": torch.from_numpy(lat).to(dev)[None, :, None, :].expand(B, nc, 1, 2).contiguous(),
+                              "cost": torch.zeros((B, nc), dtype=torch.float32, device=dev),
+                              "fail": torch.zeros((B, nc), dtype=torch.int32, device=dev)}
+        return self._plan_lat
+
+    def _score_plans(self, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast=None, react=False):
+        """tde_score_plans (forecast: tde_score_plans_forecast; react: tde_score_plans_scene) through the env's binding (arguments
+        already checked)"""
         pl = self.planner
+        if react:
+            if self._h is not None:
+                self._h.score_plans_scene(seq, knot_len, tail, cost, fail_step, int(pl.horizon), float(pl.v_target), float(pl.margin),
+                                          float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, action, diag,
+                                          int(self.tde_cfg.flags))
+            else:
+                if self._plan_struct is None:
+                    self._plan_struct = ops.planner_struct(pl)
+                ops.score_plans_scene(self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step,
+                                      action, diag)
+            return
         if self._h is not None:
             self._h.score_plans(seq, knot_len, tail, cost, fail_step, int(pl.horizon), float(pl.v_target), float(pl.margin),
                                 float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, action, diag, int(self.tde_cfg.flags),
@@ -966,7 +993,7 @@ class BatchedWaypointEnv:
             only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         return self._forecast(out, only)
 
-    def score_plans(self, seq, knot_len=None, tail=0, only=None, forecast=None):
+    def score_plans(self, seq, knot_len=None, tail=0, only=None, forecast=None, react=False):
         """how each of N action sequences per ego fares on the state as it is (tde_score_plans with self.planner's horizon, margin,
         v_target and weights) -> (cost float32 [B, N], fail_step int32 [B, N]) on the device.  seq: float32 [B, N, K, 2] device tensor
         of (acceleration, steering) knots, contiguous (raises otherwise: no copy is made); knot k holds knot_len steps (None:
@@ -974,15 +1001,22 @@ class BatchedWaypointEnv:
         off the road, on a predicted box of another agent or on a red stop line, horizon + tail + 1 for a safe sequence; a lower cost
         is better and any earlier failure costs more than any later one.  only: uint8 [B]; the other rows are not written.
         forecast: a contiguous float32 [B, T >= horizon + tail, A, 4] device tensor of the other agents' (x, y, psi, v) per step -
-        forecast_agents()'s, or any predictor's in that layout - judged through tde_score_plans_forecast; None: constant velocity."""
+        forecast_agents()'s, or any predictor's in that layout - judged through tde_score_plans_forecast; None: constant velocity.
+        react=True: every sequence is judged in a scene of its own in which the other agents run the controller against the ego that
+        follows it (tde_score_plans_scene; no forecast is materialised): with planner.margin == 0 fail_step is the step at which
+        step() would end the episode by an infraction under those actions.  Not together with forecast=."""
+        if react and forecast is not None:
+            raise ValueError("score_plans: react=True builds its own scene per sequence; forecast= cannot be given with it")
         N, K, knot_len, tail = ops.check_plan_set(seq, self.num_envs, self.planner.horizon, knot_len, tail)
+        if react and self.num_envs * N * self.A > _abi.PLAN_SCENE_MAX_LANES:
+            raise ValueError(f"score_plans: react=True needs num_envs * N * A <= {_abi.PLAN_SCENE_MAX_LANES}")
         if forecast is not None:
             ops.check_forecast(forecast, self.num_envs, self.A, int(self.planner.horizon) + tail)
         if only is not None:
             only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         cost = torch.zeros((self.num_envs, N), dtype=torch.float32, device=self.torch_device)
         fail_step = torch.zeros((self.num_envs, N), dtype=torch.int32, device=self.torch_device)
-        self._score_plans(seq, knot_len, tail, only, cost, fail_step, None, None, forecast)
+        self._score_plans(seq, knot_len, tail, only, cost, fail_step, None, None, forecast, react=bool(react))
         return cost, fail_step
 
     def _plan_refined(self, out, only, diag, forecast=None):
@@ -1415,13 +1449,13 @@ class WaypointSuiteEnv(_GymEnvBase):
     metadata = {"render_modes": ["video", "rgb_array"], "render_fps": 10}
 
     def __init__(self, cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None,
-                 video_camera="map", background=None, near_field=None, planner=None, plan_refine=None):
+                 video_camera="map", background=None, near_field=None, planner=None, plan_refine=None, plan_react=None):
         """render_mode="video": every reset() and step() records a video_res x video_res frame at video_fov metres across (the
         reference's BirdviewRecordingWrapper, gym_env.py:295-297) from `video_camera` ("map": the centre of the map, heading pi/2;
         "ego"; or (x, y, psi)); get_birdviews() returns them, close() writes video_filename (video.save_video).
         background / near_field: the background-traffic files and the near-field traffic of every reset, as BatchedWaypointEnv
         takes them (the reference's background mode: gym_env.py:200-238).  planner / plan_refine: the config.Planner and the optional
-        config.PlanRefine of expert_action()."""
+        config.PlanRefine / config.PlanReact of expert_action()."""
         self.config = cfg
         if cfg.render_mode == "video":               # the batched env renders rgb_array; the frames are recorded here
             cfg = dataclasses.replace(cfg, render_mode="rgb_array")
@@ -1430,7 +1464,7 @@ class WaypointSuiteEnv(_GymEnvBase):
         self._env = BatchedWaypointEnv(cfg, data, num_envs=1, agents_per_env=agents_per_env, obs_mode="birdview",
                                        frame_stack=1, auto_reset=False, info_magnitudes=True, road_meshes=road_meshes,
                                        traffic_lights=traffic_lights, start_headings=start_headings, background=background,
-                                       near_field=near_field, planner=planner, plan_refine=plan_refine)
+                                       near_field=near_field, planner=planner, plan_refine=plan_refine, plan_react=plan_react)
         self.torch_device = self._env.torch_device
         self.render_mode = self.config.render_mode
         self._video = None
@@ -1585,7 +1619,7 @@ class SingleAgentWrapper(_GymWrapperBase):
 
 
 def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_lights=None, start_headings=None, video_camera="map",
-         background=None, near_field=None, planner=None, plan_refine=None):
+         background=None, near_field=None, planner=None, plan_refine=None, plan_react=None):
     """what gym.make('torchdriveenv-v0', args={'cfg': cfg, 'data': data}) returns in the reference (ref __init__.py:10).
     `road_meshes`, `traffic_lights`, `start_headings`: what the reference takes from torchdrivesim's map config of the location
     (`find_map_config`: road mesh ref gym_env.py:184, stop lines + light controller :181-189, lanelet directions :359) - see
@@ -1595,7 +1629,7 @@ def make(cfg: EnvConfig, data, agents_per_env=8, road_meshes=None, traffic_light
     return SingleAgentWrapper(WaypointSuiteEnv(cfg=cfg, data=data, agents_per_env=agents_per_env, road_meshes=road_meshes,
                                                traffic_lights=traffic_lights, start_headings=start_headings,
                                                video_camera=video_camera, background=background, near_field=near_field,
-                                               planner=planner, plan_refine=plan_refine))
+                                               planner=planner, plan_refine=plan_refine, plan_react=plan_react))
 
 
 if gym is not None:  # pragma: no cover

@@ -416,6 +416,33 @@ def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=No
     return cost, fail_step
 
 
+def score_plans_scene(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, action=None, diag=None):
+    """tde_score_plans_scene: score_plans with every sequence judged in a scene of its own, in which the other agents run the
+    controller - leader sweep included - against the ego that follows THAT sequence (no forecast is materialised) -> (cost float32
+    [B, N], fail_step int32 [B, N]) on the device.  Arguments and outputs are score_plans' (there is no forecast=).  With
+    planner.margin == 0 fail_step is the step at which env_step would end the episode by an infraction under those actions.
+    B * N * A is bounded by PLAN_SCENE_MAX_LANES.  Asynchronous."""
+    L = _lib.load()
+    ps = planner if isinstance(planner, _abi.TdePlanner) else planner_struct(planner)
+    N, K, knot_len, tail = check_plan_set(seq, state.B, ps.horizon, knot_len, tail)
+    if state.B * N * state.A > _abi.PLAN_SCENE_MAX_LANES:
+        raise ValueError(f"B * N * A = {state.B * N * state.A} exceeds {_abi.PLAN_SCENE_MAX_LANES} (the launch grid of tde_score_plans_scene)")
+    dev = torch.device(state.device)
+    if cost is None:
+        cost = torch.empty((state.B, N), dtype=torch.float32, device=dev)
+    if fail_step is None:
+        fail_step = torch.empty((state.B, N), dtype=torch.int32, device=dev)
+    st = _abi.TdePlanSet(_chk(seq, torch.float32, state.B * N * K * 2, "seq", dev), N, K, knot_len, tail)
+    pc = _chk(cost, torch.float32, state.B * N, "cost", dev)
+    pf = _chk(fail_step, torch.int32, state.B * N, "fail_step", dev)
+    pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
+    pa = _chk(action, torch.float32, state.B * 2, "action", dev, optional=True)
+    pd = _chk(diag, torch.int32, state.B * 4, "diag", dev, optional=True)
+    _lib.check(_call(dev, L.tde_score_plans_scene, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps), C.byref(st), pm,
+                     pc, pf, pa, pd, _lib.current_stream(dev)), "tde_score_plans_scene")
+    return cost, fail_step
+
+
 def render_ego(cfg, dworld, state, H=64, W=64, fov=35.0, n_stack=1, out=None, layers=None, phase=0, flags=0,
                fresh=None, only=None):
     """render_egocentric() of every env's ego -> uint8 [B, 3*n_stack, H, W] on device (ref gym_env.py:122-124).

@@ -249,7 +249,7 @@ class ShardedBatchedEnv:
 
     def plan_actions(self, diag=False):
         """the sampling planner's actions of every shard on its current state (BatchedWaypointEnv.plan_actions; planner= and
-        plan_refine= are env keywords; with Planner(predict="route" / "queue") every shard forecasts its own envs' agents) in global env order: float32 [B, 2], what step() takes; diag=True: (actions, int32 [B, 4] diag rows)"""
+        plan_refine= / plan_react= are env keywords; with Planner(predict="route" / "queue") every shard forecasts its own envs' agents) in global env order: float32 [B, 2], what step() takes; diag=True: (actions, int32 [B, 4] diag rows)"""
         np = self._np
         parts = self._all("plan")
         act = np.concatenate([p[0] for p in parts])
