@@ -214,6 +214,131 @@ def test_library_rejects_bad_arguments():
                              fail.ctypes.data, None, None, None) == 0
 
 
+# What each entry point of the planner / forecast family refuses as NULL, name by name (written from the entry points' checks; the
+# library's own grouping is "what the judge reads" and "what the scene controller reads").  `free`: a pointer it does not ask for.
+_JUDGE_STATE = ("x", "y", "psi", "v", "len", "wid", "lr", "present", "scn", "steps", "target_idx")
+_SCENE_STATE = ("x", "y", "psi", "v", "len", "wid", "lr", "vdes", "route_wp", "present", "scn", "steps")
+_JUDGE_WORLD = ("maps", "scn", "wp_xy", "cell_word", "cell_cls2", "cell_coarse", "cell_tri")
+_REQUIRED = {
+    "tde_plan_action": dict(state=_JUDGE_STATE, world=_JUDGE_WORLD, free=("vdes", "route_wp"), wfree=("spawn", "route_xy", "replay_states")),
+    "tde_score_plans": dict(state=_JUDGE_STATE, world=_JUDGE_WORLD, free=("vdes", "route_wp"), wfree=("spawn", "route_xy", "replay_states")),
+    "tde_score_plans_forecast": dict(state=_JUDGE_STATE, world=_JUDGE_WORLD, free=("vdes", "route_wp"),
+                                     wfree=("spawn", "route_xy", "replay_states")),
+    # (world.maps: not without lights)
+    "tde_forecast_agents": dict(state=_SCENE_STATE, world=("spawn", "scn"), free=("target_idx",), wfree=("maps", "wp_xy", "cell_word"),
+                                routes=True),
+    # (world.maps: under lights or the offroad flag, which the default flags hold)
+    "tde_forecast_scene": dict(state=_SCENE_STATE, world=("spawn", "scn", "maps"), free=("target_idx",), wfree=("wp_xy", "cell_word"),
+                               routes=True),
+    "tde_score_plans_scene": dict(state=_SCENE_STATE + ("target_idx",), world=_JUDGE_WORLD + ("spawn",), free=("reached", "collided"),
+                                  wfree=("tri", "start_psi"), routes=True),
+}
+
+
+def test_every_planner_and_forecast_entry_point_holds_the_shared_checks():
+    """the checks the family shares, held to all callers at once: the same bad plan set, planner and dt are refused by each entry
+    point that takes them, under its own name; each required pointer is, one at a time; one it does not ask for is not.  Every call
+    is on an empty batch (B = 0): a refusal comes before that return, and a check that let something through launches nothing."""
+    from torchdriveenv_amd import _lib, ops
+    from torchdriveenv_amd.state import EnvState
+    from torchdriveenv_amd.synth import synthetic_world
+
+    L = _lib.load()
+    w = synthetic_world(n_scn=2, A=8, seed=0, n_maps=1)
+    good_cfg = _abi.default_config(seed=1)
+    assert good_cfg.flags & _abi.F_NPC and good_cfg.flags & _abi.F_REPLAY and good_cfg.flags & _abi.F_OFFROAD
+    assert not good_cfg.flags & _abi.F_TRAFFIC_LIGHTS
+    seq = np.zeros((4, 3, 2, 2), f32)
+    cost, fail = np.zeros((4, 3), f32), np.zeros((4, 3), np.int32)
+    out, act = np.zeros((4, 96, 8, 4), f32), np.zeros((4, 2), f32)
+
+    def state(null=None):
+        st = EnvState(4, 8)
+        st.struct.B = 0
+        if null is not None:
+            assert getattr(st.struct, null) is not None
+            setattr(st.struct, null, None)
+        return st
+
+    def world(null=None):
+        ws = _abi.TdeWorld.from_buffer_copy(w.host_struct())
+        if null is not None:
+            assert getattr(ws, null) is not None
+            setattr(ws, null, None)
+        return ws
+
+    def call(name, cfg=good_cfg, st=None, ws=None, pl=None, **over):
+        st, ws = st if st is not None else state(), ws if ws is not None else world()
+        pl = pl if pl is not None else ops.planner_struct(Planner())
+        ps = _abi.TdePlanSet(seq.ctypes.data, 3, 2, 16, 0)
+        for k, v in over.items():
+            setattr(ps, k, v)
+        a = (C.byref(cfg), C.byref(ws), C.byref(st.struct))
+        judged = (C.byref(pl), C.byref(ps), None, cost.ctypes.data, fail.ctypes.data, None, None)
+        if name == "tde_plan_action":
+            return L.tde_plan_action(*a, C.byref(pl), None, act.ctypes.data, None, None)
+        if name == "tde_score_plans":
+            return L.tde_score_plans(*a, *judged, None)
+        if name == "tde_score_plans_forecast":
+            return L.tde_score_plans_forecast(*a, *judged, out.ctypes.data, 96, None)
+        if name == "tde_score_plans_scene":
+            return L.tde_score_plans_scene(*a, *judged, None)
+        if name == "tde_forecast_agents":
+            return L.tde_forecast_agents(*a, 8, None, out.ctypes.data, None)
+        assert name == "tde_forecast_scene"
+        return L.tde_forecast_scene(*a, 8, None, None, out.ctypes.data, None)
+
+    def refused(name, fragment, **kw):
+        rc, err = call(name, **kw), L.tde_last_error()
+        assert rc != 0 and fragment in err and name.encode() + b":" in err, (name, fragment, sorted(kw), rc, err)
+
+    def planner(**over):
+        pl = ops.planner_struct(Planner())
+        for k, v in over.items():
+            setattr(pl, k, v)
+        return pl
+
+    assert sorted(_REQUIRED) == sorted(n for n in _lib.SYMBOLS if n.startswith(("tde_plan_", "tde_score_plans", "tde_forecast_")))
+    for name in _REQUIRED:
+        assert call(name) == 0, (name, L.tde_last_error())                # the good arguments, empty batch
+    # one plan set, one planner
+    for name in ("tde_score_plans", "tde_score_plans_forecast", "tde_score_plans_scene"):
+        for over, msg in ((dict(N=0), b"N must be in [1, TDE_PLAN_MAX_SET]"), (dict(K=33), b"K must be in [1, TDE_PLAN_MAX_H]"),
+                          (dict(knot_len=0), b"knot_len must be >= 1"), (dict(tail=65), b"tail must be in [0, TDE_PLAN_MAX_TAIL]")):
+            refused(name, msg, **over)
+    for name in ("tde_plan_action", "tde_score_plans", "tde_score_plans_forecast", "tde_score_plans_scene"):
+        refused(name, b"horizon must be in [1, TDE_PLAN_MAX_H]", pl=planner(horizon=0))
+        refused(name, b"v_target, margin and the weights must be finite and >= 0", pl=planner(margin=-0.1))
+    # one dt, the lights' tables, the controller's routes and records
+    lights = _abi.default_config(seed=1, flags=good_cfg.flags | _abi.F_TRAFFIC_LIGHTS)
+    for name, req in _REQUIRED.items():
+        for dt in (0.0, float("nan")):
+            refused(name, b"config.dt must be finite and > 0", cfg=_abi.default_config(seed=1, dt=dt))
+        for tab in ("stoplines", "phases"):
+            assert call(name, ws=world(tab)) == 0, (name, tab)
+            refused(name, b"TDE_F_TRAFFIC_LIGHTS without stop lines / phases", cfg=lights, ws=world(tab))
+        for tab, count, flag in (("route_xy", "n_routes", _abi.F_NPC), ("replay_states", "n_replay", _abi.F_REPLAY)):
+            assert w.ints[count] > 0
+            if req.get("routes"):
+                refused(name, b"world." + tab.encode() + b" is NULL", ws=world(tab))
+                assert call(name, cfg=_abi.default_config(seed=1, flags=good_cfg.flags & ~flag), ws=world(tab)) == 0, (name, tab)
+                none = world(tab)
+                setattr(none, count, 0)
+                assert call(name, ws=none) == 0, (name, tab)
+    refused("tde_forecast_agents", b"TDE_F_TRAFFIC_LIGHTS without stop lines / phases", cfg=lights, ws=world("maps"))
+    assert call("tde_forecast_scene", cfg=_abi.default_config(seed=1, flags=good_cfg.flags & ~_abi.F_OFFROAD), ws=world("maps")) == 0
+    # the pointer lists, name by name
+    for name, req in _REQUIRED.items():
+        for p in req["state"]:
+            refused(name, b"pointer is NULL", st=state(p))
+        for p in req["world"]:
+            refused(name, b"world.maps is NULL" if (name, p) == ("tde_forecast_scene", "maps") else b"pointer is NULL", ws=world(p))
+        for p in req["free"]:
+            assert call(name, st=state(p)) == 0, (name, p, L.tde_last_error())
+        for p in req["wfree"]:
+            assert call(name, ws=world(p)) == 0, (name, p, L.tde_last_error())
+
+
 def test_sequence_tensor_checks_need_no_gpu():
     import torch
 

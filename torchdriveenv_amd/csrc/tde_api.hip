@@ -16,7 +16,7 @@ static thread_local char g_err[tde_host::kErrLen] = "";
 char *tde_host::err_buf() { return g_err; }
 using tde_host::bad;
 using tde_host::cu_count;
-using tde_host::fail;
+using tde_host::launch_status;
 
 static bool pow2_le64(int A) { return A >= 1 && A <= TDE_MAX_AGENTS && (A & (A - 1)) == 0; }
 // (up to 64 slots an env lives inside one wavefront and every kernel form applies; 128 = TDE_MAX_AGENTS: an env spans two
@@ -51,8 +51,7 @@ int tde_kinematics_step(int64_t n, float *x, float *y, float *psi, float *v, con
     if (n <= 0) return 0;
     hipLaunchKernelGGL(tde::kinematics_kernel, dim3(blocks_for(n)), dim3(tde::kBlock), 0, (hipStream_t)stream, n, x, y,
                        psi, v, lr, present, action, dt);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_kinematics_step", e);
+    return launch_status("tde_kinematics_step");
 }
 
 int tde_compute_collision(int32_t B, int32_t A, const float *x, const float *y, const float *psi, const float *len,
@@ -64,8 +63,7 @@ int tde_compute_collision(int32_t B, int32_t A, const float *x, const float *y, 
     TDE_DISPATCH_A128(A, tde::collide_kernel<kA, false><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(
                           B, const_cast<float *>(x), const_cast<float *>(y), const_cast<float *>(psi), (float *)nullptr,
                           (const float *)nullptr, len, wid, present, (const float *)nullptr, 0.0f, out));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_compute_collision", e);
+    return launch_status("tde_compute_collision");
 }
 
 int tde_kin_collide_step(int32_t B, int32_t A, float *x, float *y, float *psi, float *v, const float *lr,
@@ -77,8 +75,7 @@ int tde_kin_collide_step(int32_t B, int32_t A, float *x, float *y, float *psi, f
     const unsigned nb = blocks_for((int64_t)B * A);
     TDE_DISPATCH_A128(A, tde::collide_kernel<kA, true><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(
                           B, x, y, psi, v, lr, len, wid, present, action, dt, collided));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_kin_collide_step", e);
+    return launch_status("tde_kin_collide_step");
 }
 
 int tde_compute_offroad(int32_t B, int32_t A, const float *x, const float *y, const float *psi, const float *len,
@@ -89,8 +86,7 @@ int tde_compute_offroad(int32_t B, int32_t A, const float *x, const float *y, co
     if (B <= 0) return 0;
     hipLaunchKernelGGL(tde::offroad_kernel, dim3(blocks_for((int64_t)B * A)), dim3(tde::kBlock), 0, (hipStream_t)stream,
                        B, A, x, y, psi, len, wid, present, *world, map_of_env, threshold, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_compute_offroad", e);
+    return launch_status("tde_compute_offroad");
 }
 
 int tde_waypoint_reward(const tde_config *cfg, int32_t n, const float *pre_x, const float *pre_y, const float *pre_psi,
@@ -105,8 +101,7 @@ int tde_waypoint_reward(const tde_config *cfg, int32_t n, const float *pre_x, co
     hipLaunchKernelGGL(tde::reward_kernel, dim3(blocks_for(n)), dim3(tde::kBlock), 0, (hipStream_t)stream, *cfg, n,
                        pre_x, pre_y, pre_psi, pre_v, x, y, psi, v, offroad, collided, tl_violation, wp_xy, wp_n, NW, scn,
                        steps, target_idx, reached, reward, terminated, truncated, info, info_reached);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_waypoint_reward", e);
+    return launch_status("tde_waypoint_reward");
 }
 
 static int check_env_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st)
@@ -135,8 +130,7 @@ int tde_env_reset(const tde_config *cfg, const tde_world *world, const tde_state
     if (st->B <= 0) return 0;
     const unsigned nb = blocks_for((int64_t)st->B * st->A);
     TDE_DISPATCH_A128(st->A, tde::env_reset_kernel<kA><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, mask));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_env_reset", e);
+    return launch_status("tde_env_reset");
 }
 
 // `load_slots`: the agent slots stepping on the device at the same time - the batch's own, or the whole batch's when this is one
@@ -166,8 +160,7 @@ static int first_gaps_launch(const tde_config *cfg, const tde_world *world, void
             if (m.load(std::memory_order_relaxed) == word) return 0;
     const unsigned nb = blocks_for((int64_t)world->n_scn * world->A);
     TDE_DISPATCH_A128(world->A, tde::first_gap_kernel<kA><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, hash | 1u));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("tde_first_gaps", e);
+    if (const int rc = launch_status("tde_first_gaps")) return rc;
     g_fg_memo[g_fg_next.fetch_add(1, std::memory_order_relaxed) % 16].store(word, std::memory_order_relaxed);
     return 0;
 }
@@ -439,8 +432,7 @@ int tde_render_ego(const tde_config *cfg, const tde_world *world, const tde_stat
     const unsigned ng = (unsigned)((st->B + vpg - 1) / vpg);
     if (rd->H == 64 && rd->W == 64) tde::render_views_kernel<64><<<ng, tde::kWave * tde::kViewsPerGroup, 0, (hipStream_t)stream>>>(ra, st->B);
     else tde::render_views_kernel<0><<<ng, tde::kWave * tde::kViewsPerGroup, 0, (hipStream_t)stream>>>(ra, st->B);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_render_ego", e);
+    return launch_status("tde_render_ego");
 }
 
 int tde_render_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_scene_view *views,
@@ -507,72 +499,105 @@ int tde_vector_obs(const tde_config *cfg, const tde_world *world, const tde_stat
     return tde_host::launch_vector_obs(cfg, world, st, vo, only, out, stream);
 }
 
-int tde_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const uint8_t *only,
-                    float *action, tde_plan_diag *diag, void *stream)
+// ---- the planner / forecast family (tde_plan_action, tde_score_plans*, tde_forecast_*): each host-side rule stated once, `fn` names
+// the entry point in the message; an entry point is the list of the pieces that apply to it plus its own one-off rules -----------------
+static int bad_in(const char *fn, const char *msg)
 {
-    int rc = check_env_args("tde_plan_action", cfg, world, st);
-    if (rc) return rc;
-    if (!pl || !action) return bad("tde_plan_action: NULL argument");
-    if (pl->n_a < 1 || pl->n_s < 1 || pl->n_a > TDE_PLAN_MAX_CAND || pl->n_s > TDE_PLAN_MAX_CAND || pl->n_a * pl->n_s > TDE_PLAN_MAX_CAND)
-        return bad("tde_plan_action: n_a and n_s must be >= 1 with n_a * n_s <= TDE_PLAN_MAX_CAND");
-    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return bad("tde_plan_action: horizon must be in [1, TDE_PLAN_MAX_H]");
-    for (int i = 0; i < pl->n_a; ++i)
-        if (!(pl->accel[i] >= -1.0f && pl->accel[i] <= 1.0f)) return bad("tde_plan_action: an acceleration outside [-1, 1]");
-    for (int i = 0; i < pl->n_s; ++i)
-        if (!(pl->steer[i] >= -0.3f && pl->steer[i] <= 0.3f)) return bad("tde_plan_action: a steering outside [-0.3, 0.3]");
+    snprintf(g_err, sizeof(g_err), "%s: %s", fn, msg);
+    return (int)hipErrorInvalidValue;
+}
+
+static int check_plan_set(const char *fn, const tde_plan_set *ps)
+{
+    if (ps->N < 1 || ps->N > TDE_PLAN_MAX_SET) return bad_in(fn, "N must be in [1, TDE_PLAN_MAX_SET]");
+    if (ps->K < 1 || ps->K > TDE_PLAN_MAX_H) return bad_in(fn, "K must be in [1, TDE_PLAN_MAX_H]");
+    if (ps->knot_len < 1) return bad_in(fn, "knot_len must be >= 1");
+    if (ps->tail < 0 || ps->tail > TDE_PLAN_MAX_TAIL) return bad_in(fn, "tail must be in [0, TDE_PLAN_MAX_TAIL]");
+    return 0;
+}
+
+static int check_planner_scalars(const char *fn, const tde_planner *pl)
+{
+    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return bad_in(fn, "horizon must be in [1, TDE_PLAN_MAX_H]");
     const float nn[5] = {pl->v_target, pl->margin, pl->w_progress, pl->w_speed, pl->w_steer};
     for (int i = 0; i < 5; ++i)
-        if (!(nn[i] >= 0.0f && nn[i] <= FLT_MAX))
-            return bad("tde_plan_action: v_target, margin and the weights must be finite and >= 0");
-    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_plan_action: config.dt must be finite and > 0");
+        if (!(nn[i] >= 0.0f && nn[i] <= FLT_MAX)) return bad_in(fn, "v_target, margin and the weights must be finite and >= 0");
+    return 0;
+}
+
+static int check_dt(const char *fn, const tde_config *cfg)
+{
+    return cfg->dt > 0.0f && cfg->dt <= FLT_MAX ? 0 : bad_in(fn, "config.dt must be finite and > 0");
+}
+
+static int check_lights(const char *fn, const tde_config *cfg, const tde_world *world)
+{
+    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases)) return bad_in(fn, "TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    return 0;
+}
+
+// what the plan judge reads: the ego's pose and box, the others' as they are, the waypoints, the road's grid index, the lights' tables
+static int check_judge_reads(const char *fn, const tde_config *cfg, const tde_world *world, const tde_state *st)
+{
     if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->present || !st->scn || !st->steps ||
         !st->target_idx || !world->maps || !world->scn || !world->wp_xy || !world->cell_word || !world->cell_cls2 || !world->cell_coarse ||
         !world->cell_tri)
-        return bad("tde_plan_action: a required state / world pointer is NULL");
-    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
-        return bad("tde_plan_action: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+        return bad_in(fn, "a required state / world pointer is NULL");
+    return check_lights(fn, cfg, world);
+}
+
+// what the scene's controller reads: every agent's pose, box, desired speed and route position, the spawn records, the NPCs' routes
+// and the replayed agents' records where there are any (which of world.maps and the lights' tables it needs is the entry point's to say)
+static int check_scene_reads(const char *fn, const tde_config *cfg, const tde_world *world, const tde_state *st)
+{
+    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
+        !st->steps || !world->spawn || !world->scn)
+        return bad_in(fn, "a required state / world pointer is NULL");
+    if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad_in(fn, "world.route_xy is NULL");
+    if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad_in(fn, "world.replay_states is NULL");
+    return 0;
+}
+
+int tde_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const uint8_t *only,
+                    float *action, tde_plan_diag *diag, void *stream)
+{
+    const char *fn = "tde_plan_action";
+    int rc = check_env_args(fn, cfg, world, st);
+    if (rc) return rc;
+    if (!pl || !action) return bad_in(fn, "NULL argument");
+    if (pl->n_a < 1 || pl->n_s < 1 || pl->n_a > TDE_PLAN_MAX_CAND || pl->n_s > TDE_PLAN_MAX_CAND || pl->n_a * pl->n_s > TDE_PLAN_MAX_CAND)
+        return bad_in(fn, "n_a and n_s must be >= 1 with n_a * n_s <= TDE_PLAN_MAX_CAND");
+    for (int i = 0; i < pl->n_a; ++i)
+        if (!(pl->accel[i] >= -1.0f && pl->accel[i] <= 1.0f)) return bad_in(fn, "an acceleration outside [-1, 1]");
+    for (int i = 0; i < pl->n_s; ++i)
+        if (!(pl->steer[i] >= -0.3f && pl->steer[i] <= 0.3f)) return bad_in(fn, "a steering outside [-0.3, 0.3]");
+    if ((rc = check_planner_scalars(fn, pl)) || (rc = check_dt(fn, cfg)) || (rc = check_judge_reads(fn, cfg, world, st))) return rc;
     if (st->B <= 0) return 0;
     return tde_host::launch_plan_action(cfg, world, st, pl, only, action, diag, stream);
 }
 
-// tde_score_plans and tde_score_plans_forecast (forecast != NULL): one set of checks, `what` names the entry point in the messages
-static int score_plans_checked(const char *what, const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl,
+// tde_score_plans, tde_score_plans_forecast (forecast != NULL) and tde_score_plans_scene (scene: the judge's reads AND the scene's)
+static int score_plans_checked(const char *fn, const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl,
                                const tde_plan_set *ps, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
-                               tde_plan_diag *diag, void *stream, const float *forecast, int32_t forecast_T)
+                               tde_plan_diag *diag, void *stream, const float *forecast, int32_t forecast_T, bool scene)
 {
-    const auto badw = [what](const char *msg) {
-        snprintf(g_err, sizeof(g_err), "%s: %s", what, msg);
-        return (int)hipErrorInvalidValue;
-    };
-    int rc = check_env_args(what, cfg, world, st);
+    int rc = check_env_args(fn, cfg, world, st);
     if (rc) return rc;
-    if (!pl || !ps || !ps->seq || !cost || !fail_step) return badw("NULL argument");
-    if (ps->N < 1 || ps->N > TDE_PLAN_MAX_SET) return badw("N must be in [1, TDE_PLAN_MAX_SET]");
-    if (ps->K < 1 || ps->K > TDE_PLAN_MAX_H) return badw("K must be in [1, TDE_PLAN_MAX_H]");
-    if (ps->knot_len < 1) return badw("knot_len must be >= 1");
-    if (ps->tail < 0 || ps->tail > TDE_PLAN_MAX_TAIL) return badw("tail must be in [0, TDE_PLAN_MAX_TAIL]");
-    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return badw("horizon must be in [1, TDE_PLAN_MAX_H]");
-    const float nn[5] = {pl->v_target, pl->margin, pl->w_progress, pl->w_speed, pl->w_steer};
-    for (int i = 0; i < 5; ++i)
-        if (!(nn[i] >= 0.0f && nn[i] <= FLT_MAX))
-            return badw("v_target, margin and the weights must be finite and >= 0");
-    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return badw("config.dt must be finite and > 0");
+    if (!pl || !ps || !ps->seq || !cost || !fail_step) return bad_in(fn, "NULL argument");
+    if ((rc = check_plan_set(fn, ps)) || (rc = check_planner_scalars(fn, pl)) || (rc = check_dt(fn, cfg))) return rc;
     if (forecast && (forecast_T < pl->horizon + ps->tail || forecast_T > TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL))
-        return badw("forecast_T must be in [horizon + tail, TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL]");
-    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->present || !st->scn || !st->steps ||
-        !st->target_idx || !world->maps || !world->scn || !world->wp_xy || !world->cell_word || !world->cell_cls2 || !world->cell_coarse ||
-        !world->cell_tri)
-        return badw("a required state / world pointer is NULL");
-    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
-        return badw("TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+        return bad_in(fn, "forecast_T must be in [horizon + tail, TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL]");
+    if ((rc = check_judge_reads(fn, cfg, world, st)) || (scene && (rc = check_scene_reads(fn, cfg, world, st)))) return rc;
     if (st->B <= 0) return 0;
-    return tde_host::launch_score_plans(cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, forecast, forecast_T);
+    if (!scene) return tde_host::launch_score_plans(cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, forecast, forecast_T);
+    if ((int64_t)st->B * ps->N * st->A > TDE_PLAN_SCENE_MAX_LANES) return bad_in(fn, "B * N * A exceeds TDE_PLAN_SCENE_MAX_LANES (the launch grid)");
+    return tde_host::launch_score_plans_scene(cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream);
 }
 
 int tde_score_plans(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
                     const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream)
 {
-    return score_plans_checked("tde_score_plans", cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, nullptr, 0);
+    return score_plans_checked("tde_score_plans", cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, nullptr, 0, false);
 }
 
 int tde_score_plans_forecast(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl,
@@ -581,24 +606,27 @@ int tde_score_plans_forecast(const tde_config *cfg, const tde_world *world, cons
 {
     if (!forecast) return bad("tde_score_plans_forecast: forecast is NULL");
     return score_plans_checked("tde_score_plans_forecast", cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, forecast,
-                               forecast_T);
+                               forecast_T, false);
+}
+
+int tde_score_plans_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
+                          const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream)
+{
+    return score_plans_checked("tde_score_plans_scene", cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream, nullptr, 0, true);
 }
 
 int tde_forecast_agents(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const uint8_t *only, float *out,
                         void *stream)
 {
-    int rc = check_env_args("tde_forecast_agents", cfg, world, st);
+    const char *fn = "tde_forecast_agents";
+    int rc = check_env_args(fn, cfg, world, st);
     if (rc) return rc;
-    if (!out) return bad("tde_forecast_agents: NULL argument");
-    if (T < 1 || T > TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL) return bad("tde_forecast_agents: T must be in [1, TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL]");
-    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_forecast_agents: config.dt must be finite and > 0");
-    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
-        !st->steps || !world->spawn || !world->scn)
-        return bad("tde_forecast_agents: a required state / world pointer is NULL");
-    if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad("tde_forecast_agents: world.route_xy is NULL");
-    if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad("tde_forecast_agents: world.replay_states is NULL");
-    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->maps || !world->stoplines || !world->phases))
-        return bad("tde_forecast_agents: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if (!out) return bad_in(fn, "NULL argument");
+    if (T < 1 || T > TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL) return bad_in(fn, "T must be in [1, TDE_PLAN_MAX_H + TDE_PLAN_MAX_TAIL]");
+    if ((rc = check_dt(fn, cfg)) || (rc = check_scene_reads(fn, cfg, world, st))) return rc;
+    // (world.maps holds the stop lines' ranges: read under lights only)
+    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && !world->maps) return bad_in(fn, "TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if ((rc = check_lights(fn, cfg, world))) return rc;
     if (st->B <= 0) return 0;
     return tde_host::launch_forecast_agents(cfg, world, st, T, only, out, stream);
 }
@@ -606,52 +634,16 @@ int tde_forecast_agents(const tde_config *cfg, const tde_world *world, const tde
 int tde_forecast_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, int32_t T, const float *ego_action,
                        const uint8_t *only, float *out, void *stream)
 {
-    int rc = check_env_args("tde_forecast_scene", cfg, world, st);
+    const char *fn = "tde_forecast_scene";
+    int rc = check_env_args(fn, cfg, world, st);
     if (rc) return rc;
-    if (!out) return bad("tde_forecast_scene: NULL argument");
-    if (T < 1 || T > TDE_FORECAST_MAX_T) return bad("tde_forecast_scene: T must be in [1, TDE_FORECAST_MAX_T]");
-    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_forecast_scene: config.dt must be finite and > 0");
-    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
-        !st->steps || !world->spawn || !world->scn)
-        return bad("tde_forecast_scene: a required state / world pointer is NULL");
-    if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad("tde_forecast_scene: world.route_xy is NULL");
-    if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad("tde_forecast_scene: world.replay_states is NULL");
-    if ((cfg->flags & (TDE_F_TRAFFIC_LIGHTS | TDE_F_OFFROAD)) && !world->maps) return bad("tde_forecast_scene: world.maps is NULL");
-    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
-        return bad("tde_forecast_scene: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if (!out) return bad_in(fn, "NULL argument");
+    if (T < 1 || T > TDE_FORECAST_MAX_T) return bad_in(fn, "T must be in [1, TDE_FORECAST_MAX_T]");
+    if ((rc = check_dt(fn, cfg)) || (rc = check_scene_reads(fn, cfg, world, st))) return rc;
+    if ((cfg->flags & (TDE_F_TRAFFIC_LIGHTS | TDE_F_OFFROAD)) && !world->maps) return bad_in(fn, "world.maps is NULL");
+    if ((rc = check_lights(fn, cfg, world))) return rc;
     if (st->B <= 0) return 0;
     return tde_host::launch_forecast_scene(cfg, world, st, T, ego_action, only, out, stream);
-}
-
-int tde_score_plans_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
-                          const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream)
-{
-    int rc = check_env_args("tde_score_plans_scene", cfg, world, st);
-    if (rc) return rc;
-    if (!pl || !ps || !ps->seq || !cost || !fail_step) return bad("tde_score_plans_scene: NULL argument");
-    if (ps->N < 1 || ps->N > TDE_PLAN_MAX_SET) return bad("tde_score_plans_scene: N must be in [1, TDE_PLAN_MAX_SET]");
-    if (ps->K < 1 || ps->K > TDE_PLAN_MAX_H) return bad("tde_score_plans_scene: K must be in [1, TDE_PLAN_MAX_H]");
-    if (ps->knot_len < 1) return bad("tde_score_plans_scene: knot_len must be >= 1");
-    if (ps->tail < 0 || ps->tail > TDE_PLAN_MAX_TAIL) return bad("tde_score_plans_scene: tail must be in [0, TDE_PLAN_MAX_TAIL]");
-    if (pl->horizon < 1 || pl->horizon > TDE_PLAN_MAX_H) return bad("tde_score_plans_scene: horizon must be in [1, TDE_PLAN_MAX_H]");
-    const float nn[5] = {pl->v_target, pl->margin, pl->w_progress, pl->w_speed, pl->w_steer};
-    for (int i = 0; i < 5; ++i)
-        if (!(nn[i] >= 0.0f && nn[i] <= FLT_MAX))
-            return bad("tde_score_plans_scene: v_target, margin and the weights must be finite and >= 0");
-    if (!(cfg->dt > 0.0f && cfg->dt <= FLT_MAX)) return bad("tde_score_plans_scene: config.dt must be finite and > 0");
-    // what the judge reads (tde_score_plans) and what the scene reads (tde_forecast_scene)
-    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
-        !st->steps || !st->target_idx || !world->maps || !world->scn || !world->spawn || !world->wp_xy || !world->cell_word ||
-        !world->cell_cls2 || !world->cell_coarse || !world->cell_tri)
-        return bad("tde_score_plans_scene: a required state / world pointer is NULL");
-    if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad("tde_score_plans_scene: world.route_xy is NULL");
-    if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad("tde_score_plans_scene: world.replay_states is NULL");
-    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
-        return bad("tde_score_plans_scene: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
-    if (st->B <= 0) return 0;
-    if ((int64_t)st->B * ps->N * st->A > TDE_PLAN_SCENE_MAX_LANES)
-        return bad("tde_score_plans_scene: B * N * A exceeds TDE_PLAN_SCENE_MAX_LANES (the launch grid)");
-    return tde_host::launch_score_plans_scene(cfg, world, st, pl, ps, only, cost, fail_step, action, diag, stream);
 }
 
 int tde_env_reset_render(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask,
@@ -715,8 +707,7 @@ int tde_ego_infractions(const tde_config *cfg, const tde_world *world, const tde
     if (st->B <= 0) return 0;
     const unsigned nb = (unsigned)((st->B + (tde::kBlock / tde::kWave) - 1) / (tde::kBlock / tde::kWave));
     tde::ego_infractions_kernel<<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_ego_infractions", e);
+    return launch_status("tde_ego_infractions");
 }
 
 int tde_env_post_step(const tde_config *cfg, const tde_world *world, const tde_state *st, float *magnitudes, void *stream)
@@ -727,8 +718,7 @@ int tde_env_post_step(const tde_config *cfg, const tde_world *world, const tde_s
     if (!st->terminated || !st->truncated || !st->collided || !st->offroad) return bad("tde_env_post_step: the state lacks the step's flag arrays");
     const unsigned nb = (unsigned)((st->B + (tde::kBlock / tde::kWave) - 1) / (tde::kBlock / tde::kWave));
     TDE_DISPATCH_A128(st->A, tde::env_post_step_kernel<kA><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, magnitudes));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_env_post_step", e);
+    return launch_status("tde_env_post_step");
 }
 
 int tde_first_gaps(const tde_config *cfg, const tde_world *world, void *stream)
@@ -745,8 +735,7 @@ int tde_state_obs(const tde_world *world, const tde_state *st, float *out, void 
     if (!st->x || !st->y || !st->psi || !st->v || !st->scn || !st->target_idx || !st->steps || !world->scn || !world->wp_xy)
         return bad("tde_state_obs: a required state / world pointer is NULL");
     tde::state_obs_kernel<<<blocks_for(st->B), tde::kBlock, 0, (hipStream_t)stream>>>(*world, *st, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("tde_state_obs", e);
+    return launch_status("tde_state_obs");
 }
 
 }  // extern "C"

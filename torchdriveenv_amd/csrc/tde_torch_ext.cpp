@@ -37,6 +37,13 @@ const void *dev_ptr(const at::Tensor &t, at::ScalarType dt, int64_t numel, const
     return t.data_ptr();
 }
 
+// the checked pointer as the C-ABI types it, and the launch stream: torch's current HIP stream of the device
+template <typename T> T *ptr(const at::Tensor &t, at::ScalarType dt, int64_t numel, const char *name, const at::Device &dev)
+{
+    return static_cast<T *>(const_cast<void *>(dev_ptr(t, dt, numel, name, dev)));
+}
+void *cur_stream(const at::Device &dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
+
 // ---- typed carriers of the C-ABI's argument structs -----------------------------------------------------------------
 // Round 4: the extension no longer takes raw addresses.  A Config is built from the BYTES of a tde_config (length checked),
 // a World and an EnvHandle from NAMED device tensors (dtype / device / contiguity / size checked against the struct's
@@ -201,18 +208,18 @@ class EnvHandle {
     void step(const at::Tensor &action, int64_t flags)
     {
         tde_state st = state_;
-        st.action = static_cast<const float *>(dev_ptr(action, at::kFloat, 2 * (int64_t)state_.B, "action", dev_));
+        st.action = ptr<const float>(action, at::kFloat, 2 * (int64_t)state_.B, "action", dev_);
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_env_step(&cfg_, &world_, &st, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_env_step");
+        check_rc(tde_env_step(&cfg_, &world_, &st, cur_stream(dev_)), "tde_env_step");
     }
 
     void reset(const std::optional<at::Tensor> &mask, int64_t flags)
     {
         cfg_.flags = static_cast<uint32_t>(flags);
-        const uint8_t *m = mask ? static_cast<const uint8_t *>(dev_ptr(*mask, at::kByte, state_.B, "mask", dev_)) : nullptr;
+        const uint8_t *m = mask_ptr(mask, "mask");
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_env_reset(&cfg_, &world_, &state_, m, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_env_reset");
+        check_rc(tde_env_reset(&cfg_, &world_, &state_, m, cur_stream(dev_)), "tde_env_reset");
     }
 
     void rollout(const at::Tensor &actions, const at::Tensor &reward, const at::Tensor &done, int64_t flags)
@@ -221,13 +228,13 @@ class EnvHandle {
         TORCH_CHECK(actions.dim() == 3 && actions.size(1) == state_.B && actions.size(2) == 2, "actions must be [K, B, 2]");
         const int64_t K = actions.size(0);
         tde_rollout ro;
-        ro.actions = static_cast<const float *>(dev_ptr(actions, at::kFloat, K * state_.B * 2, "actions", dev_));
-        ro.reward = static_cast<float *>(const_cast<void *>(dev_ptr(reward, at::kFloat, K * state_.B, "reward", dev_)));
-        ro.done = static_cast<uint8_t *>(const_cast<void *>(dev_ptr(done, at::kByte, K * state_.B, "done", dev_)));
+        ro.actions = ptr<const float>(actions, at::kFloat, K * state_.B * 2, "actions", dev_);
+        ro.reward = ptr<float>(reward, at::kFloat, K * state_.B, "reward", dev_);
+        ro.done = ptr<uint8_t>(done, at::kByte, K * state_.B, "done", dev_);
         ro.K = static_cast<int32_t>(K);
         ro.ldb = 0;
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_env_rollout(&cfg_, &world_, &state_, &ro, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_env_rollout");
+        check_rc(tde_env_rollout(&cfg_, &world_, &state_, &ro, cur_stream(dev_)), "tde_env_rollout");
     }
 
     // tde_env_step_render: the timestep + the birdview as streams.size() sub-batches, each on its own stream (raw hipStream_t
@@ -237,20 +244,20 @@ class EnvHandle {
                      const std::optional<at::Tensor> &fresh, const std::vector<int64_t> &streams)
     {
         tde_state st = state_;
-        st.action = static_cast<const float *>(dev_ptr(action, at::kFloat, 2 * (int64_t)state_.B, "action", dev_));
+        st.action = ptr<const float>(action, at::kFloat, 2 * (int64_t)state_.B, "action", dev_);
         cfg_.flags = static_cast<uint32_t>(flags);
         const int64_t ns = n_stack > 1 ? n_stack : 1;
         tde_render rd{};
         if (out) {
-            rd.out = static_cast<uint8_t *>(const_cast<void *>(dev_ptr(*out, at::kByte, state_.B * 3 * ns * H * W, "out", dev_)));
+            rd.out = ptr<uint8_t>(*out, at::kByte, state_.B * 3 * ns * H * W, "out", dev_);
             rd.H = static_cast<int32_t>(H);
             rd.W = static_cast<int32_t>(W);
             rd.fov = static_cast<float>(fov);
             rd.n_stack = static_cast<int32_t>(n_stack);
-            rd.layers = layers ? static_cast<uint8_t *>(const_cast<void *>(dev_ptr(*layers, at::kByte, state_.B * ns * H * W, "layers", dev_))) : nullptr;
+            rd.layers = opt<uint8_t>(layers, at::kByte, state_.B * ns * H * W, "layers");
             rd.phase = static_cast<int32_t>(phase);
             rd.flags = static_cast<int32_t>(rflags);
-            rd.fresh = fresh ? static_cast<const uint8_t *>(dev_ptr(*fresh, at::kByte, state_.B, "fresh", dev_)) : nullptr;
+            rd.fresh = mask_ptr(fresh, "fresh");
             rd.only = nullptr;
         }
         TORCH_CHECK(!streams.empty() && streams.size() <= 16, "streams: 1 to 16 raw stream handles");
@@ -265,18 +272,18 @@ class EnvHandle {
     {
         const int64_t ns = n_stack > 1 ? n_stack : 1;
         tde_render rd;
-        rd.out = static_cast<uint8_t *>(const_cast<void *>(dev_ptr(out, at::kByte, state_.B * 3 * ns * H * W, "out", dev_)));
+        rd.out = ptr<uint8_t>(out, at::kByte, state_.B * 3 * ns * H * W, "out", dev_);
         rd.H = static_cast<int32_t>(H);
         rd.W = static_cast<int32_t>(W);
         rd.fov = static_cast<float>(fov);
         rd.n_stack = static_cast<int32_t>(n_stack);
-        rd.layers = layers ? static_cast<uint8_t *>(const_cast<void *>(dev_ptr(*layers, at::kByte, state_.B * ns * H * W, "layers", dev_))) : nullptr;
+        rd.layers = opt<uint8_t>(layers, at::kByte, state_.B * ns * H * W, "layers");
         rd.phase = static_cast<int32_t>(phase);
         rd.flags = static_cast<int32_t>(flags);
-        rd.fresh = fresh ? static_cast<const uint8_t *>(dev_ptr(*fresh, at::kByte, state_.B, "fresh", dev_)) : nullptr;
-        rd.only = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        rd.fresh = mask_ptr(fresh, "fresh");
+        rd.only = mask_ptr(only, "only");
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_render_ego(&cfg_, &world_, &state_, &rd, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_render_ego");
+        check_rc(tde_render_ego(&cfg_, &world_, &state_, &rd, cur_stream(dev_)), "tde_render_ego");
     }
 
     // tde_env_reset_render: masked reset + the re-spawned views' first observation (their newest frame in place, older stack frames
@@ -287,22 +294,22 @@ class EnvHandle {
         cfg_.flags = static_cast<uint32_t>(flags);
         const int64_t ns = n_stack > 1 ? n_stack : 1;
         tde_render rd{};
-        rd.out = static_cast<uint8_t *>(const_cast<void *>(dev_ptr(out, at::kByte, state_.B * 3 * ns * H * W, "out", dev_)));
+        rd.out = ptr<uint8_t>(out, at::kByte, state_.B * 3 * ns * H * W, "out", dev_);
         rd.H = static_cast<int32_t>(H); rd.W = static_cast<int32_t>(W); rd.fov = static_cast<float>(fov);
         rd.n_stack = static_cast<int32_t>(n_stack);
-        rd.layers = layers ? static_cast<uint8_t *>(const_cast<void *>(dev_ptr(*layers, at::kByte, state_.B * ns * H * W, "layers", dev_))) : nullptr;
+        rd.layers = opt<uint8_t>(layers, at::kByte, state_.B * ns * H * W, "layers");
         rd.phase = static_cast<int32_t>(phase);
         rd.flags = static_cast<int32_t>(rflags);
-        const uint8_t *m = static_cast<const uint8_t *>(dev_ptr(mask, at::kByte, state_.B, "mask", dev_));
+        const uint8_t *m = ptr<const uint8_t>(mask, at::kByte, state_.B, "mask", dev_);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_env_reset_render(&cfg_, &world_, &state_, m, &rd, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_env_reset_render");
+        check_rc(tde_env_reset_render(&cfg_, &world_, &state_, m, &rd, cur_stream(dev_)), "tde_env_reset_render");
     }
 
     void state_obs(const at::Tensor &out)
     {
-        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, (int64_t)state_.B * 8, "out", dev_)));
+        float *p = ptr<float>(out, at::kFloat, (int64_t)state_.B * 8, "out", dev_);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_state_obs(&world_, &state_, p, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_state_obs");
+        check_rc(tde_state_obs(&world_, &state_, p, cur_stream(dev_)), "tde_state_obs");
     }
 
     // tde_vector_obs: float32 [B, D] (D = 10 + 9 k_nbr + 3 n_rays) of the envs in `only` (all without it); ray_dir float32 [n_rays, 2]
@@ -313,18 +320,17 @@ class EnvHandle {
         const int64_t D = TDE_VO_EGO + TDE_VO_NBR * k_nbr + TDE_VO_RAY * n_rays;
         struct tde_vector_obs vo;
         std::memset(&vo, 0, sizeof(vo));
-        vo.ray_dir = static_cast<const float *>(dev_ptr(ray_dir, at::kFloat, 2 * n_rays, "ray_dir", dev_));
+        vo.ray_dir = ptr<const float>(ray_dir, at::kFloat, 2 * n_rays, "ray_dir", dev_);
         vo.k_nbr = (int32_t)k_nbr;
         vo.n_rays = (int32_t)n_rays;
         vo.nbr_radius = (float)nbr_radius;
         vo.ray_range = (float)ray_range;
         vo.ray_step = (float)ray_step;
-        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, (int64_t)state_.B * D, "out", dev_)));
-        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        float *p = ptr<float>(out, at::kFloat, (int64_t)state_.B * D, "out", dev_);
+        const uint8_t *m = mask_ptr(only, "only");
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_vector_obs(&cfg_, &world_, &state_, &vo, m, p, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
-                 "tde_vector_obs");
+        check_rc(tde_vector_obs(&cfg_, &world_, &state_, &vo, m, p, cur_stream(dev_)), "tde_vector_obs");
     }
 
     // tde_plan_action: float32 [B, 2] ego actions of the envs in `only` (all without it); diag: optional int32 [B, 4] = tde_plan_diag rows
@@ -334,26 +340,17 @@ class EnvHandle {
     {
         TORCH_CHECK(!accel.empty() && !steer.empty() && accel.size() * steer.size() <= (size_t)TDE_PLAN_MAX_CAND,
                     "plan_action: accel x steer must hold 1 .. TDE_PLAN_MAX_CAND candidates");
-        tde_planner pl;
-        std::memset(&pl, 0, sizeof(pl));
+        tde_planner pl = planner_of(horizon, v_target, margin, w_progress, w_speed, w_steer);
         for (size_t i = 0; i < accel.size(); ++i) pl.accel[i] = (float)accel[i];
         for (size_t i = 0; i < steer.size(); ++i) pl.steer[i] = (float)steer[i];
         pl.n_a = (int32_t)accel.size();
         pl.n_s = (int32_t)steer.size();
-        pl.horizon = (int32_t)horizon;
-        pl.v_target = (float)v_target;
-        pl.margin = (float)margin;
-        pl.w_progress = (float)w_progress;
-        pl.w_speed = (float)w_speed;
-        pl.w_steer = (float)w_steer;
-        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, (int64_t)state_.B * 2, "out", dev_)));
-        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
-        static_assert(sizeof(tde_plan_diag) == 4 * sizeof(int32_t), "tde_plan_diag rows are four 32-bit words");
-        tde_plan_diag *d = diag ? static_cast<tde_plan_diag *>(const_cast<void *>(dev_ptr(*diag, at::kInt, (int64_t)state_.B * 4, "diag", dev_))) : nullptr;
+        float *p = ptr<float>(out, at::kFloat, (int64_t)state_.B * 2, "out", dev_);
+        const uint8_t *m = mask_ptr(only, "only");
+        tde_plan_diag *d = diag_ptr(diag);
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_plan_action(&cfg_, &world_, &state_, &pl, m, p, d, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
-                 "tde_plan_action");
+        check_rc(tde_plan_action(&cfg_, &world_, &state_, &pl, m, p, d, cur_stream(dev_)), "tde_plan_action");
     }
 
     // tde_score_plans: cost float32 [B, N] and fail_step int32 [B, N] of the N sequences of seq (float32 [B, N, K, 2], contiguous); action
@@ -385,25 +382,18 @@ class EnvHandle {
         TORCH_CHECK(seq.dim() == 4 && seq.size(0) == state_.B && seq.size(3) == 2, "score_plans: seq must be [B, N, K, 2]");
         TORCH_CHECK(seq.is_contiguous(), "score_plans: seq must be contiguous (no copy of it is made)");
         const int64_t N = seq.size(1), K = seq.size(2);
-        tde_planner pl;
-        std::memset(&pl, 0, sizeof(pl));
-        pl.horizon = (int32_t)horizon;
-        pl.v_target = (float)v_target;
-        pl.margin = (float)margin;
-        pl.w_progress = (float)w_progress;
-        pl.w_speed = (float)w_speed;
-        pl.w_steer = (float)w_steer;
+        const tde_planner pl = planner_of(horizon, v_target, margin, w_progress, w_speed, w_steer);
         tde_plan_set ps;
-        ps.seq = static_cast<const float *>(dev_ptr(seq, at::kFloat, (int64_t)state_.B * N * K * 2, "seq", dev_));
+        ps.seq = ptr<const float>(seq, at::kFloat, (int64_t)state_.B * N * K * 2, "seq", dev_);
         ps.N = (int32_t)N;
         ps.K = (int32_t)K;
         ps.knot_len = (int32_t)knot_len;
         ps.tail = (int32_t)tail;
-        float *pc = static_cast<float *>(const_cast<void *>(dev_ptr(cost, at::kFloat, (int64_t)state_.B * N, "cost", dev_)));
-        int32_t *pf = static_cast<int32_t *>(const_cast<void *>(dev_ptr(fail_step, at::kInt, (int64_t)state_.B * N, "fail_step", dev_)));
-        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
-        float *pa = action ? static_cast<float *>(const_cast<void *>(dev_ptr(*action, at::kFloat, (int64_t)state_.B * 2, "action", dev_))) : nullptr;
-        tde_plan_diag *d = diag ? static_cast<tde_plan_diag *>(const_cast<void *>(dev_ptr(*diag, at::kInt, (int64_t)state_.B * 4, "diag", dev_))) : nullptr;
+        float *pc = ptr<float>(cost, at::kFloat, (int64_t)state_.B * N, "cost", dev_);
+        int32_t *pf = ptr<int32_t>(fail_step, at::kInt, (int64_t)state_.B * N, "fail_step", dev_);
+        const uint8_t *m = mask_ptr(only, "only");
+        float *pa = opt<float>(action, at::kFloat, (int64_t)state_.B * 2, "action");
+        tde_plan_diag *d = diag_ptr(diag);
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
         if (forecast) {
@@ -412,21 +402,16 @@ class EnvHandle {
             TORCH_CHECK(fc.dim() == 4 && fc.size(0) == state_.B && fc.size(2) == state_.A && fc.size(3) == 4,
                         "score_plans: forecast must be [B, T, A, 4]");
             TORCH_CHECK(fc.is_contiguous(), "score_plans: forecast must be contiguous (no copy of it is made)");
-            const float *pfc = static_cast<const float *>(dev_ptr(fc, at::kFloat, fc.numel(), "forecast", dev_));
-            check_rc(tde_score_plans_forecast(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d, pfc, (int32_t)fc.size(1),
-                                              c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
+            const float *pfc = ptr<const float>(fc, at::kFloat, fc.numel(), "forecast", dev_);
+            check_rc(tde_score_plans_forecast(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d, pfc, (int32_t)fc.size(1), cur_stream(dev_)),
                      "tde_score_plans_forecast");
             return;
         }
         if (scene) {
-            check_rc(tde_score_plans_scene(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d,
-                                           c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
-                     "tde_score_plans_scene");
+            check_rc(tde_score_plans_scene(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d, cur_stream(dev_)), "tde_score_plans_scene");
             return;
         }
-        check_rc(tde_score_plans(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d,
-                                 c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
-                 "tde_score_plans");
+        check_rc(tde_score_plans(&cfg_, &world_, &state_, &pl, &ps, m, pc, pf, pa, d, cur_stream(dev_)), "tde_score_plans");
     }
 
     // tde_forecast_agents: out float32 [B, T, A, 4] = (x, y, psi, v) of every slot at each of the next T steps (rows of envs outside `only` untouched)
@@ -434,13 +419,11 @@ class EnvHandle {
     {
         TORCH_CHECK(out.dim() == 4 && out.size(0) == state_.B && out.size(2) == state_.A && out.size(3) == 4,
                     "forecast_agents: out must be [B, T, A, 4]");
-        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, out.numel(), "out", dev_)));
-        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        float *p = ptr<float>(out, at::kFloat, out.numel(), "out", dev_);
+        const uint8_t *m = mask_ptr(only, "only");
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_forecast_agents(&cfg_, &world_, &state_, (int32_t)out.size(1), m, p,
-                                     c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
-                 "tde_forecast_agents");
+        check_rc(tde_forecast_agents(&cfg_, &world_, &state_, (int32_t)out.size(1), m, p, cur_stream(dev_)), "tde_forecast_agents");
     }
 
     // tde_forecast_scene: out float32 [B, T, A, 4] = (x, y, psi, v) of every slot, the ego included, at each of the next T steps under
@@ -450,38 +433,36 @@ class EnvHandle {
         TORCH_CHECK(out.dim() == 4 && out.size(0) == state_.B && out.size(2) == state_.A && out.size(3) == 4,
                     "forecast_scene: out must be [B, T, A, 4]");
         const int64_t T = out.size(1);
-        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, out.numel(), "out", dev_)));
+        float *p = ptr<float>(out, at::kFloat, out.numel(), "out", dev_);
         const float *pa = nullptr;
         if (ego_actions) {
             const at::Tensor &ea = *ego_actions;
             TORCH_CHECK(ea.dim() == 3 && ea.size(0) == state_.B && ea.size(1) == T && ea.size(2) == 2, "forecast_scene: ego_actions must be [B, T, 2]");
             TORCH_CHECK(ea.is_contiguous(), "forecast_scene: ego_actions must be contiguous (no copy of it is made)");
-            pa = static_cast<const float *>(dev_ptr(ea, at::kFloat, (int64_t)state_.B * T * 2, "ego_actions", dev_));
+            pa = ptr<const float>(ea, at::kFloat, (int64_t)state_.B * T * 2, "ego_actions", dev_);
         }
-        const uint8_t *m = only ? static_cast<const uint8_t *>(dev_ptr(*only, at::kByte, state_.B, "only", dev_)) : nullptr;
+        const uint8_t *m = mask_ptr(only, "only");
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_forecast_scene(&cfg_, &world_, &state_, (int32_t)T, pa, m, p,
-                                    c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
-                 "tde_forecast_scene");
+        check_rc(tde_forecast_scene(&cfg_, &world_, &state_, (int32_t)T, pa, m, p, cur_stream(dev_)), "tde_forecast_scene");
     }
 
     // tde_ego_infractions: float32 [B, 4] = the ego's (offroad, collision, overlap count, 0) magnitudes of the state as it is (gym_env.py:427-428)
     void ego_infractions(const at::Tensor &out, int64_t flags)
     {
-        float *p = static_cast<float *>(const_cast<void *>(dev_ptr(out, at::kFloat, (int64_t)state_.B * 4, "out", dev_)));
+        float *p = ptr<float>(out, at::kFloat, (int64_t)state_.B * 4, "out", dev_);
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_ego_infractions(&cfg_, &world_, &state_, p, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_ego_infractions");
+        check_rc(tde_ego_infractions(&cfg_, &world_, &state_, p, cur_stream(dev_)), "tde_ego_infractions");
     }
 
     // tde_env_post_step: magnitudes (optional) of the state a step without TDE_F_AUTORESET left + the re-spawn of the envs it finished
     void post_step(const std::optional<at::Tensor> &mag, int64_t flags)
     {
-        float *p = mag ? static_cast<float *>(const_cast<void *>(dev_ptr(*mag, at::kFloat, (int64_t)state_.B * 4, "magnitudes", dev_))) : nullptr;
+        float *p = opt<float>(mag, at::kFloat, (int64_t)state_.B * 4, "magnitudes");
         cfg_.flags = static_cast<uint32_t>(flags);
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_env_post_step(&cfg_, &world_, &state_, p, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()), "tde_env_post_step");
+        check_rc(tde_env_post_step(&cfg_, &world_, &state_, p, cur_stream(dev_)), "tde_env_post_step");
     }
 
     // tde_near_field_spawn: near-field traffic in the free slots of the masked envs (all without a mask)
@@ -489,10 +470,9 @@ class EnvHandle {
     {
         cfg_.flags = static_cast<uint32_t>(flags);
         TORCH_CHECK(nf.dev == dev_, "near_field is on ", nf.dev, ", expected ", dev_);
-        const uint8_t *m = mask ? static_cast<const uint8_t *>(dev_ptr(*mask, at::kByte, state_.B, "mask", dev_)) : nullptr;
+        const uint8_t *m = mask_ptr(mask, "mask");
         const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
-        check_rc(tde_near_field_spawn(&cfg_, &world_, &state_, &nf.nf, m, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index()).stream()),
-                 "tde_near_field_spawn");
+        check_rc(tde_near_field_spawn(&cfg_, &world_, &state_, &nf.nf, m, cur_stream(dev_)), "tde_near_field_spawn");
     }
 
     int64_t flags() const { return cfg_.flags; }
@@ -500,6 +480,33 @@ class EnvHandle {
     int64_t agents_per_env() const { return state_.A; }
 
   private:
+    // an optional tensor's checked pointer, NULL without it
+    template <typename T> T *opt(const std::optional<at::Tensor> &t, at::ScalarType dt, int64_t numel, const char *name) const
+    {
+        return t ? ptr<T>(*t, dt, numel, name, dev_) : nullptr;
+    }
+    // ... of a uint8 [B] mask over the envs (`only`, `mask`, `fresh`)
+    const uint8_t *mask_ptr(const std::optional<at::Tensor> &m, const char *name) const { return opt<const uint8_t>(m, at::kByte, state_.B, name); }
+    // ... of the planner family's int32 [B, 4] diag output, as tde_plan_diag rows
+    tde_plan_diag *diag_ptr(const std::optional<at::Tensor> &diag) const
+    {
+        static_assert(sizeof(tde_plan_diag) == 4 * sizeof(int32_t), "tde_plan_diag rows are four 32-bit words");
+        return opt<tde_plan_diag>(diag, at::kInt, (int64_t)state_.B * 4, "diag");
+    }
+    // a tde_planner of the six scalars, its lattice empty (tde_plan_action's caller fills it; the plan-set judges do not read it)
+    static tde_planner planner_of(int64_t horizon, double v_target, double margin, double w_progress, double w_speed, double w_steer)
+    {
+        tde_planner pl;
+        std::memset(&pl, 0, sizeof(pl));
+        pl.horizon = (int32_t)horizon;
+        pl.v_target = (float)v_target;
+        pl.margin = (float)margin;
+        pl.w_progress = (float)w_progress;
+        pl.w_speed = (float)w_speed;
+        pl.w_steer = (float)w_steer;
+        return pl;
+    }
+
     tde_config cfg_;
     tde_world world_;
     std::shared_ptr<World> wkeep_;         // (owns the world's tensors)
@@ -509,11 +516,6 @@ class EnvHandle {
 };
 
 // ---- operator level: the SimulatorInterface methods GymEnv calls (include/tde_hip.h, first block), torch tensors in / out ----
-template <typename T> T *ptr(const at::Tensor &t, at::ScalarType dt, int64_t numel, const char *name, const at::Device &dev)
-{
-    return static_cast<T *>(const_cast<void *>(dev_ptr(t, dt, numel, name, dev)));
-}
-void *cur_stream(const at::Device &dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
 
 // tde_kinematics_step: KinematicBicycle.step for n agents, in place (ref gym_env.py:117)
 void kinematics_step(const at::Tensor &x, const at::Tensor &y, const at::Tensor &psi, const at::Tensor &v, const at::Tensor &lr,

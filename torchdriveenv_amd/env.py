@@ -862,8 +862,7 @@ class BatchedWaypointEnv:
             if self._plan_diag is None:
                 self._plan_diag = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.torch_device)
             d = self._plan_diag
-        if only is not None:
-            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
+        only = self._as_only(only)
         pl = self.planner
         if self.plan_react is not None:
             la = self._plan_lattice()
@@ -873,7 +872,7 @@ class BatchedWaypointEnv:
         if pl.predict in ("route", "queue"):
             T = int(pl.horizon) + (int(self.plan_refine.tail) if self.plan_refine is not None else 0)
             if self._plan_fc is None:
-                self._plan_fc = torch.zeros((self.num_envs, T, self.A, 4), dtype=torch.float32, device=self.torch_device)
+                self._plan_fc = self._forecast_args(T, only, None)[0]
             fc = self._forecast(self._plan_fc, only) if pl.predict == "route" else self._forecast_scene(self._plan_fc, None, only)
         if self.plan_refine is not None:
             if self._plan_diag is None:
@@ -885,8 +884,7 @@ class BatchedWaypointEnv:
             self._score_plans(la["seq"], int(pl.horizon), 0, only, la["cost"], la["fail"], out, d, fc)
             return (out, d) if diag else out
         if self._h is not None:
-            self._h.plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings], int(pl.horizon),
-                                float(pl.v_target), float(pl.margin), float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, d,
+            self._h.plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings], *self._plan_scalars(), only, d,
                                 int(self.tde_cfg.flags))
         else:
             if self._plan_struct is None:
@@ -897,39 +895,46 @@ class BatchedWaypointEnv:
     def _plan_lattice(self):
         """the planner's lattice as one-knot sequences [B, nc, 1, 2] with their cost / fail_step buffers (made once)"""
         if self._plan_lat is None:
-            pl = self.planner
-            B, nc, dev = self.num_envs, pl.n_candidates, self.torch_device
-            acc, ste = pl.tables()
-            lat = np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(np.float32)      # [nc, 2]: candidate i = ia * n_s + is
-            self._plan_lat = {"seq": torch.from_numpy(lat).to(dev)[None, :, None, :].expand(B, nc, 1, 2).contiguous(),
+            B, nc, dev = self.num_envs, self.planner.n_candidates, self.torch_device
+            self._plan_lat = {"seq": self._lattice(1)[1],
                               "cost": torch.zeros((B, nc), dtype=torch.float32, device=dev),
                               "fail": torch.zeros((B, nc), dtype=torch.int32, device=dev)}
         return self._plan_lat
 
+    def _lattice(self, K):
+        """the planner's lattice -> (float32 [nc, 2] on the host, candidate i = ia * n_s + is; the same as sequences of K equal knots,
+        float32 [B, nc, K, 2] on the device, contiguous)"""
+        acc, ste = self.planner.tables()
+        lat = np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(np.float32)
+        seq = torch.from_numpy(lat).to(self.torch_device)[None, :, None, :].expand(self.num_envs, len(lat), K, 2).contiguous()
+        return lat, seq
+
+    def _as_only(self, only):
+        """an `only` mask as the uint8 [B] device tensor the entry points read (None stays None)"""
+        return None if only is None else torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
+
+    def _plan_scalars(self):
+        """self.planner's (horizon, v_target, margin, w_progress, w_speed, w_steer) as the extension takes them"""
+        pl = self.planner
+        return int(pl.horizon), float(pl.v_target), float(pl.margin), float(pl.w_progress), float(pl.w_speed), float(pl.w_steer)
+
     def _score_plans(self, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast=None, react=False):
         """tde_score_plans (forecast: tde_score_plans_forecast; react: tde_score_plans_scene) through the env's binding (arguments
         already checked)"""
-        pl = self.planner
-        if react:
-            if self._h is not None:
-                self._h.score_plans_scene(seq, knot_len, tail, cost, fail_step, int(pl.horizon), float(pl.v_target), float(pl.margin),
-                                          float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, action, diag,
-                                          int(self.tde_cfg.flags))
-            else:
-                if self._plan_struct is None:
-                    self._plan_struct = ops.planner_struct(pl)
-                ops.score_plans_scene(self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step,
-                                      action, diag)
-            return
         if self._h is not None:
-            self._h.score_plans(seq, knot_len, tail, cost, fail_step, int(pl.horizon), float(pl.v_target), float(pl.margin),
-                                float(pl.w_progress), float(pl.w_speed), float(pl.w_steer), only, action, diag, int(self.tde_cfg.flags),
-                                forecast)
+            args = (seq, knot_len, tail, cost, fail_step, *self._plan_scalars(), only, action, diag, int(self.tde_cfg.flags))
+            if react:
+                self._h.score_plans_scene(*args)
+            else:
+                self._h.score_plans(*args, forecast)
         else:
             if self._plan_struct is None:
-                self._plan_struct = ops.planner_struct(pl)
-            ops.score_plans(self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step, action, diag,
-                            forecast)
+                self._plan_struct = ops.planner_struct(self.planner)
+            args = (self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step, action, diag)
+            if react:
+                ops.score_plans_scene(*args)
+            else:
+                ops.score_plans(*args, forecast)
 
     def _forecast(self, out, only):
         """tde_forecast_agents into `out` (float32 [B, T, A, 4]) through the env's binding (arguments already checked) -> out"""
@@ -947,6 +952,19 @@ class BatchedWaypointEnv:
             ops.forecast_scene(self.tde_cfg, self.dworld, self.state, out.shape[1], ego_actions, only, out)
         return out
 
+    def _forecast_args(self, T, only, out):
+        """what forecast_agents() and forecast_scene() share: T (None: the planner's horizon) an integer in range, `out` checked, or
+        allocated - zeroed when `only` leaves rows unwritten -, `only` as the entry points read it -> (out, only)"""
+        T = int(self.planner.horizon) if T is None else T
+        if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
+            raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
+        shape = (self.num_envs, int(T), self.A, 4)
+        if out is None:
+            out = (torch.empty if only is None else torch.zeros)(shape, dtype=torch.float32, device=self.torch_device)
+        elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+        return out, self._as_only(only)
+
     def forecast_scene(self, T=None, ego_actions=None, only=None, out=None):
         """where the environment's own rules put EVERY agent, the ego included, at each of the next T steps when the ego takes
         `ego_actions` (tde_forecast_scene) -> float32 [B, T, A, 4] on the device: row [e, h - 1, j] = (x, y, psi, v) of slot j at
@@ -957,20 +975,11 @@ class BatchedWaypointEnv:
         (acceleration, steering), taken as given - no clamp, no scaling; None: the ego coasts; only: uint8 [B], the other envs' rows
         are left as they are (zeros in a fresh buffer); out: a float32 [B, T, A, 4] device tensor to write into.  The state is not
         written.  score_plans(forecast=) takes the result (it ignores row 0)."""
-        T = int(self.planner.horizon) if T is None else T
-        if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
-            raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
-        shape = (self.num_envs, int(T), self.A, 4)
+        out, only = self._forecast_args(T, only, out)
         if ego_actions is not None:
-            ops.check_ego_actions(ego_actions, self.num_envs, int(T))
+            ops.check_ego_actions(ego_actions, self.num_envs, out.shape[1])
             if ego_actions.device != self.torch_device:
                 raise ValueError(f"ego_actions is on {ego_actions.device}, expected {self.torch_device}")
-        if out is None:
-            out = (torch.empty if only is None else torch.zeros)(shape, dtype=torch.float32, device=self.torch_device)
-        elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
-        if only is not None:
-            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
         return self._forecast_scene(out, ego_actions, only)
 
     def forecast_agents(self, T=None, only=None, out=None):
@@ -981,17 +990,7 @@ class BatchedWaypointEnv:
         (None: the planner's horizon); only: uint8 [B], the other envs' rows are left as they are (zeros in a fresh buffer); out: a
         float32 [B, T, A, 4] device tensor to write into (16 * B * T * A bytes the caller keeps).  score_plans(forecast=) takes the
         result."""
-        T = int(self.planner.horizon) if T is None else T
-        if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
-            raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
-        shape = (self.num_envs, int(T), self.A, 4)
-        if out is None:
-            out = (torch.empty if only is None else torch.zeros)(shape, dtype=torch.float32, device=self.torch_device)
-        elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
-        if only is not None:
-            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
-        return self._forecast(out, only)
+        return self._forecast(*self._forecast_args(T, only, out))
 
     def score_plans(self, seq, knot_len=None, tail=0, only=None, forecast=None, react=False):
         """how each of N action sequences per ego fares on the state as it is (tde_score_plans with self.planner's horizon, margin,
@@ -1012,8 +1011,7 @@ class BatchedWaypointEnv:
             raise ValueError(f"score_plans: react=True needs num_envs * N * A <= {_abi.PLAN_SCENE_MAX_LANES}")
         if forecast is not None:
             ops.check_forecast(forecast, self.num_envs, self.A, int(self.planner.horizon) + tail)
-        if only is not None:
-            only = torch.as_tensor(only, device=self.torch_device).to(torch.uint8)
+        only = self._as_only(only)
         cost = torch.zeros((self.num_envs, N), dtype=torch.float32, device=self.torch_device)
         fail_step = torch.zeros((self.num_envs, N), dtype=torch.int32, device=self.torch_device)
         self._score_plans(seq, knot_len, tail, only, cost, fail_step, None, None, forecast, react=bool(react))
@@ -1025,9 +1023,8 @@ class BatchedWaypointEnv:
         B, nc, K, R = self.num_envs, pl.n_candidates, int(pr.knots), int(pr.rounds)
         dev = self.torch_device
         if self._refine is None:
-            acc, ste = pl.tables()
-            lat = np.stack([np.repeat(acc, len(ste)), np.tile(ste, len(acc))], -1).astype(np.float32)      # [nc, 2]: candidate i = ia * n_s + is
-            rf = {"seq0": torch.from_numpy(lat).to(dev)[None, :, None, :].expand(B, nc, K, 2).contiguous(),
+            lat, seq0 = self._lattice(K)
+            rf = {"seq0": seq0,
                   "cost0": torch.zeros((B, nc), dtype=torch.float32, device=dev), "fail0": torch.zeros((B, nc), dtype=torch.int32, device=dev),
                   "lo": torch.tensor([-_abi.PLAN_BOX_ACCEL, -_abi.PLAN_BOX_STEER], dtype=torch.float32, device=dev),
                   "hi": torch.tensor([_abi.PLAN_BOX_ACCEL, _abi.PLAN_BOX_STEER], dtype=torch.float32, device=dev)}

@@ -326,12 +326,9 @@ def check_forecast(forecast, B, A, need):
     return T
 
 
-def forecast_agents(cfg, dworld, state, T, only=None, out=None):
-    """tde_forecast_agents: (x, y, psi, v) of every slot at each of the next T steps when nobody is in its cone -> float32 [B, T, A,
-    4] on the device (zeros for the ego and absent slots).  only: uint8 [B], the other envs' rows of `out` are left as they are;
-    out: a float32 [B, T, A, 4] device tensor to write into.  Asynchronous."""
-    L = _lib.load()
-    dev = torch.device(state.device)
+def _forecast_out(state, T, only, out, dev):
+    """the forecast family's T (an integer in range) and `out`, float32 [B, T, A, 4]: checked, or allocated - zeroed when `only`
+    leaves rows unwritten -> (T, out, out's address)"""
     if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
         raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
     T = int(T)
@@ -339,7 +336,16 @@ def forecast_agents(cfg, dworld, state, T, only=None, out=None):
         out = (torch.empty if only is None else torch.zeros)((state.B, T, state.A, 4), dtype=torch.float32, device=dev)
     elif tuple(out.shape) != (state.B, T, state.A, 4):
         raise ValueError(f"out must be [B={state.B}, T={T}, A={state.A}, 4], got {tuple(out.shape)}")
-    po = _chk(out, torch.float32, state.B * T * state.A * 4, "out", dev)
+    return T, out, _chk(out, torch.float32, state.B * T * state.A * 4, "out", dev)
+
+
+def forecast_agents(cfg, dworld, state, T, only=None, out=None):
+    """tde_forecast_agents: (x, y, psi, v) of every slot at each of the next T steps when nobody is in its cone -> float32 [B, T, A,
+    4] on the device (zeros for the ego and absent slots).  only: uint8 [B], the other envs' rows of `out` are left as they are;
+    out: a float32 [B, T, A, 4] device tensor to write into.  Asynchronous."""
+    L = _lib.load()
+    dev = torch.device(state.device)
+    T, out, po = _forecast_out(state, T, only, out, dev)
     pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
     _lib.check(_call(dev, L.tde_forecast_agents, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), T, pm, po,
                      _lib.current_stream(dev)), "tde_forecast_agents")
@@ -364,16 +370,9 @@ def forecast_scene(cfg, dworld, state, T, ego_actions=None, only=None, out=None)
     float32 [B, T, A, 4] device tensor to write into.  Asynchronous."""
     L = _lib.load()
     dev = torch.device(state.device)
-    if int(T) != T or not 1 <= int(T) <= _abi.FORECAST_MAX_T:
-        raise ValueError(f"T must be an integer in [1, {_abi.FORECAST_MAX_T}]")
-    T = int(T)
+    T, out, po = _forecast_out(state, T, only, out, dev)
     if ego_actions is not None:
         check_ego_actions(ego_actions, state.B, T)
-    if out is None:
-        out = (torch.empty if only is None else torch.zeros)((state.B, T, state.A, 4), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (state.B, T, state.A, 4):
-        raise ValueError(f"out must be [B={state.B}, T={T}, A={state.A}, 4], got {tuple(out.shape)}")
-    po = _chk(out, torch.float32, state.B * T * state.A * 4, "out", dev)
     pa = _chk(ego_actions, torch.float32, state.B * T * 2, "ego_actions", dev, optional=True)
     pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
     _lib.check(_call(dev, L.tde_forecast_scene, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), T, pa, pm, po,
@@ -391,9 +390,26 @@ def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=No
     action and its tde_plan_diag row.  forecast: float32 [B, T >= horizon + tail, A, 4] device tensor, contiguous - the other agents'
     (x, y, psi, v) per step (tde_score_plans_forecast; tde_forecast_agents' layout); None: tde_score_plans' constant velocity.
     Asynchronous."""
+    return _score_plans(cfg, dworld, state, planner, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast)
+
+
+def score_plans_scene(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, action=None, diag=None):
+    """tde_score_plans_scene: score_plans with every sequence judged in a scene of its own, in which the other agents run the
+    controller - leader sweep included - against the ego that follows THAT sequence (no forecast is materialised) -> (cost float32
+    [B, N], fail_step int32 [B, N]) on the device.  Arguments and outputs are score_plans' (there is no forecast=).  With
+    planner.margin == 0 fail_step is the step at which env_step would end the episode by an infraction under those actions.
+    B * N * A is bounded by PLAN_SCENE_MAX_LANES.  Asynchronous."""
+    return _score_plans(cfg, dworld, state, planner, seq, knot_len, tail, only, cost, fail_step, action, diag, scene=True)
+
+
+def _score_plans(cfg, dworld, state, planner, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast=None, scene=False):
+    """score_plans (forecast: tde_score_plans_forecast) and score_plans_scene (scene=True): one set of checks and buffers, the entry
+    point chosen last"""
     L = _lib.load()
     ps = planner if isinstance(planner, _abi.TdePlanner) else planner_struct(planner)
     N, K, knot_len, tail = check_plan_set(seq, state.B, ps.horizon, knot_len, tail)
+    if scene and state.B * N * state.A > _abi.PLAN_SCENE_MAX_LANES:
+        raise ValueError(f"B * N * A = {state.B * N * state.A} exceeds {_abi.PLAN_SCENE_MAX_LANES} (the launch grid of tde_score_plans_scene)")
     fT = check_forecast(forecast, state.B, state.A, ps.horizon + tail) if forecast is not None else 0
     dev = torch.device(state.device)
     if cost is None:
@@ -406,40 +422,11 @@ def score_plans(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=No
     pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
     pa = _chk(action, torch.float32, state.B * 2, "action", dev, optional=True)
     pd = _chk(diag, torch.int32, state.B * 4, "diag", dev, optional=True)
+    name, more = "tde_score_plans_scene" if scene else "tde_score_plans", ()
     if forecast is not None:
-        pfc = _chk(forecast, torch.float32, state.B * fT * state.A * 4, "forecast", dev)
-        _lib.check(_call(dev, L.tde_score_plans_forecast, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps),
-                         C.byref(st), pm, pc, pf, pa, pd, pfc, fT, _lib.current_stream(dev)), "tde_score_plans_forecast")
-        return cost, fail_step
-    _lib.check(_call(dev, L.tde_score_plans, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps), C.byref(st), pm, pc,
-                     pf, pa, pd, _lib.current_stream(dev)), "tde_score_plans")
-    return cost, fail_step
-
-
-def score_plans_scene(cfg, dworld, state, planner, seq, knot_len=None, tail=0, only=None, cost=None, fail_step=None, action=None, diag=None):
-    """tde_score_plans_scene: score_plans with every sequence judged in a scene of its own, in which the other agents run the
-    controller - leader sweep included - against the ego that follows THAT sequence (no forecast is materialised) -> (cost float32
-    [B, N], fail_step int32 [B, N]) on the device.  Arguments and outputs are score_plans' (there is no forecast=).  With
-    planner.margin == 0 fail_step is the step at which env_step would end the episode by an infraction under those actions.
-    B * N * A is bounded by PLAN_SCENE_MAX_LANES.  Asynchronous."""
-    L = _lib.load()
-    ps = planner if isinstance(planner, _abi.TdePlanner) else planner_struct(planner)
-    N, K, knot_len, tail = check_plan_set(seq, state.B, ps.horizon, knot_len, tail)
-    if state.B * N * state.A > _abi.PLAN_SCENE_MAX_LANES:
-        raise ValueError(f"B * N * A = {state.B * N * state.A} exceeds {_abi.PLAN_SCENE_MAX_LANES} (the launch grid of tde_score_plans_scene)")
-    dev = torch.device(state.device)
-    if cost is None:
-        cost = torch.empty((state.B, N), dtype=torch.float32, device=dev)
-    if fail_step is None:
-        fail_step = torch.empty((state.B, N), dtype=torch.int32, device=dev)
-    st = _abi.TdePlanSet(_chk(seq, torch.float32, state.B * N * K * 2, "seq", dev), N, K, knot_len, tail)
-    pc = _chk(cost, torch.float32, state.B * N, "cost", dev)
-    pf = _chk(fail_step, torch.int32, state.B * N, "fail_step", dev)
-    pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
-    pa = _chk(action, torch.float32, state.B * 2, "action", dev, optional=True)
-    pd = _chk(diag, torch.int32, state.B * 4, "diag", dev, optional=True)
-    _lib.check(_call(dev, L.tde_score_plans_scene, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps), C.byref(st), pm,
-                     pc, pf, pa, pd, _lib.current_stream(dev)), "tde_score_plans_scene")
+        name, more = "tde_score_plans_forecast", (_chk(forecast, torch.float32, state.B * fT * state.A * 4, "forecast", dev), fT)
+    _lib.check(_call(dev, getattr(L, name), C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ps), C.byref(st), pm, pc,
+                     pf, pa, pd, *more, _lib.current_stream(dev)), name)
     return cost, fail_step
 
 
