@@ -515,6 +515,37 @@ typedef struct tde_plan_set {
     int32_t tail;               /* brake-tail steps after the horizon */
 } tde_plan_set;
 
+/* Evaluation over chosen scenarios (tde_env_reset_to, tde_eval_advance: include/tde_hip.h; no ABI bump: new entry points and new
+ * structs only, every existing layout as it was).  What the reference's EvalNTimestepsCallback reports per finished episode
+ * (examples/rl_training.py:51-108) as one record, 48 bytes, read and written as three 16-byte words (arrays of it are 16-byte
+ * aligned):
+ *   word 0   ret, psi_sum               word 1   speed_sum, length, reached               word 2   scn, bits, padding */
+typedef struct tde_episode_record {
+    double ret;                 /* sum of (double)state.reward[e] over the episode's steps, in step order */
+    double psi_sum;             /* sum of state.info[e][0] (psi_smoothness) over the episode's steps, in step order */
+    double speed_sum;           /* sum of state.info[e][1] (speed_smoothness), likewise; the callback's per-episode means are
+                                   psi_sum / length and speed_sum / length */
+    int32_t length;             /* state.steps[e] at the finishing step (0 in a running record) */
+    int32_t reached;            /* state.info_reached[e] at the finishing step (reached_waypoint_num) */
+    int32_t scn;                /* state.scn[e]: the scenario the episode ran */
+    uint8_t bits;               /* state.done_bits[e] of the finishing step, tde_rollout.done's layout: bit0 terminated, bit1
+                                   truncated, bit2 offroad, bit3 collided, bit4 red-light violation */
+    uint8_t _pad0[3];           /* zero */
+    int32_t _pad1[2];           /* zero */
+} tde_episode_record;
+
+/* The evaluation schedule and its results (tde_eval_advance).  A HOST struct of DEVICE pointers.  Env e runs the episodes
+ * plan[0][e], plan[1][e], ... one after the other; round[e] counts the ones it has finished. */
+typedef struct tde_eval {
+    const int32_t *plan;        /* in  [R][B] scenario id of the r-th episode of env e; < 0 (or >= n_scn): no further episode */
+    int32_t *round;             /* in/out [B] index of the running episode */
+    uint8_t *active;            /* in/out [B] 1 while env e is still evaluating */
+    tde_episode_record *acc;    /* in/out [B] the running episode (ret, psi_sum, speed_sum; the other fields zero) */
+    tde_episode_record *results;/* out [R][B] the finished episodes: episode r of env e at r * B + e */
+    int32_t R;                  /* episodes per env, >= 1 */
+    int32_t _pad0;
+} tde_eval;
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@
  * The reference has no FFI of its own (it is pure Python over torchdrivesim); INTEGRATION.md shows the ctypes stub a
  * maintainer would add and how GymEnv/WaypointSuiteEnv would call it.
  *
- * Struct arguments (tde_config, tde_world, tde_state, tde_rollout: include/tde_abi.h) are HOST structs whose pointer
+ * Struct arguments (tde_config, tde_world, tde_state, tde_rollout, tde_eval: include/tde_abi.h) are HOST structs whose pointer
  * members are device pointers; they are copied by value into the kernel arguments at launch.
  */
 #ifndef TDE_HIP_H
@@ -428,6 +428,43 @@ TDE_API int tde_forecast_scene(const tde_config *cfg, const tde_world *world, co
 TDE_API int tde_score_plans_scene(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_planner *plan,
                                   const tde_plan_set *set, const uint8_t *only, float *cost, int32_t *fail_step, float *action,
                                   tde_plan_diag *diag, void *stream);
+
+/* ---- evaluation over chosen scenarios --------------------------------------------------------------------------------- */
+
+/* tde_env_reset with the scenario given: env e with scn[e] >= 0 (DEVICE int32 [B]) starts scenario scn[e]; an env with scn[e] < 0,
+ * and every env when scn is NULL, draws it as tde_env_reset does (scn = (philox(seed, env, episode, 0).x * n_scn) >> 32).  The draw
+ * is the only use of that random word, so everything else is tde_env_reset's, line for line: the Philox counters and words (blocks
+ * 0 and 1 of (seed, env_base + e, episode, tag 0x7DE)), the ego's start (ego_spawn: point on the first waypoint segment, speed,
+ * heading noise, TDE_F_EGO_ONLY_ATTRS attributes), the slots' spawn records, steps = 0, target_idx = 1, reached = 0, episode + 1,
+ * ep_return zeroed, collided and offroad cleared; like tde_env_reset it writes none of the lookup caches (their entries carry the
+ * key they were formed for and are rebuilt by the step that meets another).  `mask` (u8 [B], NULL = all) selects the envs as there.
+ * What the reference does with WaypointSuiteEnv.reset when the suite index is chosen instead of sampled (gym_env.py:319-323; how
+ * examples/rl_training.py:136-160 runs validation_cases.yml).  An id >= world.n_scn cannot be rejected on the host - the array
+ * lives on the device - : such an env is left UNWRITTEN, counters included.  Rejected: what tde_env_reset rejects (NULL cfg / world
+ * / state, A not a power of two in [1, 128], world.A != state.A, the npc_max_steer / npc_max_accel ranges under TDE_F_NPC).  An
+ * empty batch returns 0 before any launch.  No allocation, no synchronisation (graph-capturable). */
+TDE_API int tde_env_reset_to(const tde_config *cfg, const tde_world *world, const tde_state *state, const uint8_t *mask,
+                             const int32_t *scn /* DEVICE [B], or NULL */, void *stream);
+
+/* One step of an evaluation over chosen scenarios, after a tde_env_step launched WITHOUT TDE_F_AUTORESET: ONE launch, one wavefront
+ * per env (tde_env_post_step is the model).  eval = tde_eval (tde_abi.h), R = eval.R.  For every env e with active[e] != 0:
+ *   1. fold the step into acc[e]: ret = ret + (double)state.reward[e], psi_sum = psi_sum + state.info[e][0], speed_sum = speed_sum
+ *      + state.info[e][1] (float64 additions, in step order);
+ *   2. when !(state.terminated[e] | state.truncated[e]): done with e;
+ *   3. else results[round[e]][e] = acc[e] with length = state.steps[e], reached = state.info_reached[e], scn = state.scn[e], bits =
+ *      state.done_bits[e] (tde_episode_record); acc[e] = zeros; round[e] = round[e] + 1;
+ *   4. when round[e] < R and plan[round[e]][e] lies in [0, world.n_scn): the env is re-spawned to that scenario by
+ *      tde_env_reset_to's rule and, when state.obs is set, the compact observation of the new episode is written (as
+ *      tde_env_post_step does); state.terminated / truncated / reward / done_bits keep the step's values;
+ *   5. else active[e] = 0 and the state stays as the step left it.
+ * Envs with active[e] == 0 are not touched.  A round[e] outside [0, R) when an episode ends - a caller's error the host cannot see -
+ * records nothing and sets active[e] = 0.  An episode ends here with terminated | truncated; the reference's callback ends one with
+ * `infraction or is_success` (examples/rl_training.py:51-53): the two coincide under terminated_at_infraction = 1, the default.
+ * No atomics: every env owns its column of plan and results.  Rejected: NULL cfg / world / state / eval or a NULL array in eval, R
+ * < 1, a state without reward, terminated, truncated, done_bits, info, info_reached, steps or scn, TDE_F_AUTORESET in cfg->flags
+ * (the step would already have re-spawned the env), and what tde_env_reset rejects.  An empty batch returns 0 before any launch.
+ * No allocation, no synchronisation (graph-capturable); every store is an ordinary vector store. */
+TDE_API int tde_eval_advance(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_eval *eval, void *stream);
 
 /* ---- host side: static tables ------------------------------------------------------------------------------------ */
 

@@ -169,6 +169,22 @@ FORECAST_MAX_T = PLAN_MAX_H + PLAN_MAX_TAIL      # TDE_FORECAST_MAX_T: steps of 
 PLAN_SCENE_MAX_LANES = 2**31 - 256                # TDE_PLAN_SCENE_MAX_LANES (tde_hip.h): B * N * A of tde_score_plans_scene
 PLAN_BOX_ACCEL, PLAN_BOX_STEER = 1.0, 0.3
 
+class TdeEpisodeRecord(C.Structure):
+    """tde_episode_record (tde_abi.h): one finished episode of an evaluation, 48 bytes"""
+    _fields_ = [("ret", C.c_double), ("psi_sum", C.c_double), ("speed_sum", C.c_double), ("length", C.c_int32), ("reached", C.c_int32),
+                ("scn", C.c_int32), ("bits", C.c_uint8), ("_pad0", C.c_uint8 * 3), ("_pad1", C.c_int32 * 2)]
+
+
+EPISODE_RECORD_DTYPE = np.dtype([("ret", "f8"), ("psi_sum", "f8"), ("speed_sum", "f8"), ("length", "i4"), ("reached", "i4"), ("scn", "i4"),
+                                 ("bits", "u1"), ("_pad0", "u1", (3,)), ("_pad1", "i4", (2,))])
+assert EPISODE_RECORD_DTYPE.itemsize == C.sizeof(TdeEpisodeRecord) == 48
+
+
+class TdeEval(C.Structure):
+    """tde_eval (tde_abi.h): the schedule and the results of tde_eval_advance; device addresses"""
+    _fields_ = [("plan", _p), ("round", _p), ("active", _p), ("acc", _p), ("results", _p), ("R", C.c_int32), ("_pad0", C.c_int32)]
+
+
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7
 RENDER_LEFT_HANDED, RENDER_PLAIN_EGO = 1 << 0, 1 << 1

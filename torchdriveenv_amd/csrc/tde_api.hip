@@ -133,6 +133,43 @@ int tde_env_reset(const tde_config *cfg, const tde_world *world, const tde_state
     return launch_status("tde_env_reset");
 }
 
+int tde_env_reset_to(const tde_config *cfg, const tde_world *world, const tde_state *st, const uint8_t *mask, const int32_t *scn,
+                     void *stream)
+{
+    int rc = check_env_args("tde_env_reset_to", cfg, world, st);         // (tde_env_reset's rejections, stated there)
+    if (rc) return rc;
+    if (st->B <= 0) return 0;
+    const unsigned nb = blocks_for((int64_t)st->B * st->A);
+    TDE_DISPATCH_A128(st->A, tde::env_reset_to_kernel<kA><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, mask, scn));
+    return launch_status("tde_env_reset_to");
+}
+
+// the arrays of the state tde_eval_advance folds and records
+static int check_eval_reads(const char *fn, const tde_state *st)
+{
+    if (!st->reward || !st->terminated || !st->truncated || !st->done_bits || !st->info || !st->info_reached || !st->steps || !st->scn) {
+        snprintf(g_err, sizeof(g_err), "%s: the state lacks reward, terminated, truncated, done_bits, info, info_reached, steps or scn", fn);
+        return (int)hipErrorInvalidValue;
+    }
+    return 0;
+}
+
+int tde_eval_advance(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_eval *ev, void *stream)
+{
+    const char *fn = "tde_eval_advance";
+    if (!ev) { snprintf(g_err, sizeof(g_err), "%s: NULL argument", fn); return (int)hipErrorInvalidValue; }
+    int rc = check_env_args(fn, cfg, world, st);
+    if (rc) return rc;
+    if (!ev->plan || !ev->round || !ev->active || !ev->acc || !ev->results) return bad("tde_eval_advance: a NULL array in eval");
+    if (ev->R < 1) return bad("tde_eval_advance: eval.R must be >= 1");
+    if (cfg->flags & TDE_F_AUTORESET) return bad("tde_eval_advance: TDE_F_AUTORESET is set (the step has already re-spawned the finished envs)");
+    if ((rc = check_eval_reads(fn, st))) return rc;
+    if (st->B <= 0) return 0;
+    const unsigned nb = (unsigned)((st->B + (tde::kBlock / tde::kWave) - 1) / (tde::kBlock / tde::kWave));
+    TDE_DISPATCH_A128(st->A, tde::env_eval_advance_kernel<kA><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *ev));
+    return launch_status("tde_eval_advance");
+}
+
 // `load_slots`: the agent slots stepping on the device at the same time - the batch's own, or the whole batch's when this is one
 // of the sub-batches tde_env_step_render runs side by side (the choice of kernel form is a matter of load)
 // The (world, configuration) pairs whose first-step gap cache this process has filled: tde_env_step / tde_env_rollout fill it on

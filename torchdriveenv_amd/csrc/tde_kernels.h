@@ -406,9 +406,12 @@ TDE_DEV void ego_spawn(const tde_config &cfg, const Cold &w, int scn, const uint
 
 // (DRAWN: the env's Philox blocks 0 and 1 for this episode were drawn by the caller - the one-step three-role kernel draws them
 //  ahead of the barrier behind which it learns whether the env finished, off the launch's tail)
+// (forced_scn >= 0: the episode runs that scenario instead of the drawn one - word r0.x has no other use, so every other random word
+//  of the episode is the one the draw would have met; passed by the kernels of tde_eval_kernels.h alone, -1 everywhere else)
 template <int A, bool SPREAD = true, bool DRAWN = false>
 TDE_DEV void reset_lane(const tde_config &cfg, const Cold &w, int e, int a, Agent &ag, EnvRegs &er,
-                        uint4 d0 = make_uint4(0, 0, 0, 0), uint4 d1 = make_uint4(0, 0, 0, 0), const float4 *pre_ego = nullptr)
+                        uint4 d0 = make_uint4(0, 0, 0, 0), uint4 d1 = make_uint4(0, 0, 0, 0), const float4 *pre_ego = nullptr,
+                        int forced_scn = -1)
 {
     uint32_t ep = (uint32_t)er.episode;
     const uint32_t ge = w.env_base + (uint32_t)e;       // global env index keys the stream
@@ -429,6 +432,7 @@ TDE_DEV void reset_lane(const tde_config &cfg, const Cold &w, int e, int a, Agen
         r0 = philox(seed, ge, ep, 0u, 0x7DEu);
     }
     int scn = (int)(((uint64_t)r0.x * (uint64_t)w.n_scn) >> 32);
+    if (forced_scn >= 0) scn = forced_scn;
     er.scn = scn;
     er.steps = 0;
     er.target_idx = 1;
@@ -4108,4 +4112,5 @@ void render_views_kernel(RenderArgs ra, int B)
 }  // namespace tde
 
 #include "tde_magnitudes_kernels.h"
+#include "tde_eval_kernels.h"
 #endif  // TDE_KERNELS_H

@@ -465,6 +465,37 @@ class EnvHandle {
         check_rc(tde_env_post_step(&cfg_, &world_, &state_, p, cur_stream(dev_)), "tde_env_post_step");
     }
 
+    // tde_env_reset_to: tde_env_reset with the scenario of env e given by scn[e] >= 0 (int32 [B]; without it every env draws)
+    void reset_to(const std::optional<at::Tensor> &scn, const std::optional<at::Tensor> &mask, int64_t flags)
+    {
+        cfg_.flags = static_cast<uint32_t>(flags);
+        const uint8_t *m = mask_ptr(mask, "mask");
+        const int32_t *s = opt<const int32_t>(scn, at::kInt, state_.B, "scn");
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_env_reset_to(&cfg_, &world_, &state_, m, s, cur_stream(dev_)), "tde_env_reset_to");
+    }
+
+    // tde_eval_advance: plan int32 [R, B], round int32 [B], active uint8 [B], acc uint8 [B, 48], results uint8 [R, B, 48]
+    // (tde_episode_record rows as raw bytes)
+    void eval_advance(const at::Tensor &plan, const at::Tensor &round, const at::Tensor &active, const at::Tensor &acc,
+                      const at::Tensor &results, int64_t flags)
+    {
+        static_assert(sizeof(tde_episode_record) == 48, "tde_episode_record rows are 48 bytes");
+        TORCH_CHECK(plan.dim() == 2 && plan.size(0) >= 1 && plan.size(1) == state_.B, "plan must be [R >= 1, B]");
+        const int64_t R = plan.size(0), B = state_.B;
+        cfg_.flags = static_cast<uint32_t>(flags);
+        tde_eval ev;
+        std::memset(&ev, 0, sizeof(ev));
+        ev.plan = ptr<const int32_t>(plan, at::kInt, R * B, "plan", dev_);
+        ev.round = ptr<int32_t>(round, at::kInt, B, "round", dev_);
+        ev.active = ptr<uint8_t>(active, at::kByte, B, "active", dev_);
+        ev.acc = ptr<tde_episode_record>(acc, at::kByte, B * 48, "acc", dev_);
+        ev.results = ptr<tde_episode_record>(results, at::kByte, R * B * 48, "results", dev_);
+        ev.R = static_cast<int32_t>(R);
+        const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev_);
+        check_rc(tde_eval_advance(&cfg_, &world_, &state_, &ev, cur_stream(dev_)), "tde_eval_advance");
+    }
+
     // tde_near_field_spawn: near-field traffic in the free slots of the masked envs (all without a mask)
     void near_field_spawn(const NearField &nf, const std::optional<at::Tensor> &mask, int64_t flags)
     {
@@ -635,6 +666,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         .def("ego_infractions", &EnvHandle::ego_infractions, py::arg("out"), py::arg("flags"))
         .def("post_step", &EnvHandle::post_step, py::arg("magnitudes"), py::arg("flags"))
         .def("near_field_spawn", &EnvHandle::near_field_spawn, py::arg("nf"), py::arg("mask"), py::arg("flags"))
+        .def("reset_to", &EnvHandle::reset_to, py::arg("scn"), py::arg("mask"), py::arg("flags"))
+        .def("eval_advance", &EnvHandle::eval_advance, py::arg("plan"), py::arg("round"), py::arg("active"), py::arg("acc"),
+             py::arg("results"), py::arg("flags"))
         .def("vector_obs", &EnvHandle::vector_obs, py::arg("out"), py::arg("ray_dir"), py::arg("k_nbr"), py::arg("n_rays"),
              py::arg("nbr_radius"), py::arg("ray_range"), py::arg("ray_step"), py::arg("only"), py::arg("flags"))
         .def("plan_action", &EnvHandle::plan_action, py::arg("out"), py::arg("accel"), py::arg("steer"), py::arg("horizon"),

@@ -449,6 +449,63 @@ def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=
     return world, table
 
 
+def eval_plan(n_scn, B, cases=None, repeats=1):
+    """the static schedule of BatchedWaypointEnv.evaluate -> (plan int32 [R, B] numpy, jobs int32 [J]): jobs = `cases` (default:
+    every scenario) repeated `repeats` times; job j is episode j // B of env j % B; -1 where an env has no further episode"""
+    cases = np.arange(int(n_scn)) if cases is None else np.asarray(cases)
+    if cases.ndim != 1 or len(cases) == 0 or cases.dtype.kind not in "iu":
+        raise ValueError("cases must be a non-empty sequence of scenario indices")
+    if int(cases.min()) < 0 or int(cases.max()) >= int(n_scn):
+        raise ValueError(f"cases must be in [0, {int(n_scn)})")
+    if int(repeats) != repeats or int(repeats) < 1:
+        raise ValueError("repeats must be an integer >= 1")
+    jobs = np.tile(cases.astype(np.int32), int(repeats))
+    R = -(-len(jobs) // int(B))
+    plan = np.full(R * int(B), -1, np.int32)
+    plan[:len(jobs)] = jobs
+    return plan.reshape(R, int(B)), jobs
+
+
+@dataclasses.dataclass
+class EvalResult:
+    """the finished episodes of BatchedWaypointEnv.evaluate, one entry per job in job order (host tensors)"""
+    episode_return: torch.Tensor    # float64 [J]: sum of the episode's rewards
+    length: torch.Tensor            # int32 [J]: its number of steps
+    reached: torch.Tensor           # int32 [J]: reached_waypoint_num at its last step
+    scenario: torch.Tensor          # int32 [J]: the scenario it ran
+    bits: torch.Tensor              # uint8 [J]: the done bits of its last step (1 terminated, 2 truncated, 4 offroad, 8 collided, 16 red light)
+    psi_smoothness: torch.Tensor    # float64 [J]: mean of info["psi_smoothness"] over its steps (psi_sum / length)
+    speed_smoothness: torch.Tensor  # float64 [J]: mean of info["speed_smoothness"] over its steps
+
+    @classmethod
+    def from_records(cls, rec, jobs=None):
+        """from tde_episode_record rows (_abi.EPISODE_RECORD_DTYPE) in job order; `jobs`: the scenario of every job, checked"""
+        rec = np.ascontiguousarray(rec)
+        if jobs is not None and not np.array_equal(rec["scn"], np.asarray(jobs)):
+            raise RuntimeError("evaluate(): a job was not recorded under its scenario")
+        n = rec["length"].astype(np.float64)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a))      # noqa: E731
+        return cls(t(rec["ret"]), t(rec["length"]), t(rec["reached"]), t(rec["scn"]), t(rec["bits"]), t(rec["psi_sum"] / n),
+                   t(rec["speed_sum"] / n))
+
+    def __len__(self):
+        return int(self.length.numel())
+
+    def metrics(self):
+        """the nine values the reference's callback logs, with its arithmetic (ref examples/rl_training.py:96-108): means over
+        the episodes; the rates count the episodes whose last step had the bit set (offroad 4, collision 8, red light 16, success =
+        truncated 2); the smoothness values are means of the per-episode means"""
+        n = len(self)
+        if n == 0:
+            raise ValueError("metrics() of an empty result")
+        bit = lambda k: int(((self.bits >> k) & 1).sum()) / n        # noqa: E731
+        mean = lambda t: sum(t.tolist()) / n                         # noqa: E731  (Python floats summed in episode order, as there)
+        return {"mean_episode_reward": mean(self.episode_return), "mean_episode_length": mean(self.length),
+                "offroad_rate": bit(2), "collision_rate": bit(3), "traffic_light_violation_rate": bit(4), "success_percentage": bit(1),
+                "reached_waypoint_num": mean(self.reached), "psi_smoothness": mean(self.psi_smoothness),
+                "speed_smoothness": mean(self.speed_smoothness)}
+
+
 class _LazyInfo(dict):
     """dict of per-env info tensors (ref gym_env.py:419-437) whose values are built when first read.  The entries are VIEWS of the
     env's own output buffers (like reward / terminated / truncated): valid until the next step() overwrites them - clone what
@@ -676,13 +733,21 @@ class BatchedWaypointEnv:
         """re-spawn all envs (or those in `mask`, uint8/bool [B]).  `seed` is ignored like in the reference
         (ref gym_env.py:107-109); seeding is EnvConfig.seed.  With a mask only the re-spawned envs' observations
         change: their newest frame is re-rendered in place and their older frames are blanked; the other envs keep
-        their frame stack exactly as the last step left it."""
+        their frame stack exactly as the last step left it.
+        options={"scenario": ids}: the scenario each re-spawned env starts in (tde_env_reset_to) - an int (every env), a sequence
+        or an integer tensor [B]; -1 = drawn as without the option; ids outside [-1, n_scn) raise ValueError.  Everything else of
+        the episode (start point, speed, heading noise, the slots' spawn) is what the same reset would give had it drawn that
+        scenario; observations, near-field traffic and the frame stack are handled as without the option.  Other keys of `options`
+        are ignored, like the reference ignores them all (ref gym_env.py:107-109)."""
         m = None
         if mask is not None:
             # 0 / 1 bytes: the rasteriser reads bits 0-1 of a `fresh` byte (tde_render.fresh), so a mask like done_bits with only
             # infraction bits set must not re-spawn an env and leave its older stack frames un-blanked
             m = (torch.as_tensor(mask, device=self.torch_device) != 0).to(torch.uint8).contiguous()
-        if m is not None and self.obs_mode == "birdview" and self._obs is not None and self.dnf is None:
+        scn = None
+        if options is not None and options.get("scenario") is not None:
+            scn = ops.check_scenario_ids(options["scenario"], self.num_envs, self.world.n_scn).to(self.torch_device)
+        if scn is None and m is not None and self.obs_mode == "birdview" and self._obs is not None and self.dnf is None:
             # the SB3-style auto-reset: the re-spawn and the re-spawned views' first observation in ONE C-ABI call
             if self._stack is not None:
                 self._obs = self._stack.reset_rerender(self.tde_cfg, self.dworld, self.state, m, self._fov)
@@ -692,7 +757,12 @@ class BatchedWaypointEnv:
                 ops.env_reset_render(self.tde_cfg, self.dworld, self.state, m, self._obs, self._res, self._res, self._fov, 1,
                                      flags=self._rflags)
             return self._obs
-        if self._h is not None:
+        if scn is not None:
+            if self._h is not None:
+                self._h.reset_to(scn, m, int(self.tde_cfg.flags))
+            else:
+                ops.env_reset_to(self.tde_cfg, self.dworld, self.state, scn, m)
+        elif self._h is not None:
             self._h.reset(m, int(self.tde_cfg.flags))
         else:
             ops.env_reset(self.tde_cfg, self.dworld, self.state, m)
@@ -1052,6 +1122,60 @@ class BatchedWaypointEnv:
                 cv[:, k, :, k, :] = torch.minimum(torch.maximum(w[:, k, None, :] + rf["delta"][r][None], rf["lo"]), rf["hi"])
             seqs = rf["cand"]
             self._score_plans(seqs, knot_len, tail, only, rf["cost"], rf["fail"], out, diag, forecast)
+
+    def evaluate(self, policy, cases=None, repeats=1):
+        """run `policy` once (or `repeats` times) on each of the scenarios `cases` (default: every scenario of the world) and
+        collect whole-episode results on the device -> EvalResult: what the reference's EvalNTimestepsCallback does with its
+        eval env over validation_cases.yml (ref examples/rl_training.py:39-108), with the cases chosen instead of drawn.
+        policy: a callable observation -> float32 [B, 2] actions on the device (it sees the observation of every env, idle ones
+        included), or "planner" (plan_actions()).  The job list is `cases` repeated `repeats` times; job j runs on env j % B as that
+        env's (j // B)-th episode, so for a deterministic policy the results do not depend on timing.  Per step: the step without
+        in-kernel re-spawn, tde_eval_advance (fold the step into the running records, record finished episodes, re-spawn their envs
+        to the next planned scenario), the near-field spawner and the observation rows of the envs just re-spawned.  The host looks
+        at the `active` flags every 8 steps; at most ceil(jobs / B) * max_steps steps are made.  An episode ends with terminated |
+        truncated (the callback's `infraction or is_success` under terminated_at_infraction=True).
+        The env is left mid-evaluation (finished envs are not re-spawned at the end): reset() it before training on it again, or
+        evaluate on a second env as the reference does."""
+        if self.state["info"] is None:
+            raise ValueError("evaluate() needs with_info=True (the per-step psi / speed smoothness and the done bits)")
+        if not (callable(policy) or (isinstance(policy, str) and policy == "planner")):
+            raise ValueError("policy must be a callable obs -> actions [B, 2] or 'planner'")
+        B, S, dev = self.num_envs, self.world.n_scn, self.torch_device
+        plan, jobs = eval_plan(S, B, cases, repeats)
+        ev = ops.EvalBuffers(plan, dev)
+        ev.active.copy_((ev.plan[0] >= 0).to(torch.uint8))
+        obs = self.reset(options={"scenario": ev.plan[0].clamp(min=-1)})
+        st = self.state
+        full = int(self.tde_cfg.flags)
+        respawned = torch.empty(B, dtype=torch.uint8, device=dev)
+        self.tde_cfg.flags = full & ~_abi.F_AUTORESET
+        try:
+            flags = int(self.tde_cfg.flags)
+            for t in range(ev.R * int(self.tde_cfg.max_steps)):
+                if t % 8 == 0 and not bool(ev.active.any()):
+                    break
+                a = self.plan_actions() if isinstance(policy, str) else policy(obs)
+                obs = self.step(a)[0]
+                if self._h is not None:
+                    self._h.eval_advance(ev.plan, ev.round, ev.active, ev.acc, ev.results, flags)
+                else:
+                    ops.eval_advance(self.tde_cfg, self.dworld, st, ev)
+                if self.dnf is not None or self.obs_mode != "state":
+                    # the envs the advance re-spawned: finished at this step and still evaluating
+                    torch.bitwise_or(st["terminated"], st["truncated"], out=respawned).bitwise_and_(ev.active)
+                    self._spawn_near_field(respawned)
+                    if self.obs_mode == "vector":
+                        obs = self._vector_obs(respawned)
+                    elif self.obs_mode == "birdview":
+                        if self._stack is not None:
+                            obs = self._obs = self._stack.rerender(self.tde_cfg, self.dworld, st, respawned, self._fov)
+                        else:
+                            self._render1(self._obs, only=respawned)
+        finally:
+            self.tde_cfg.flags = full
+        if bool(ev.active.any()):
+            raise RuntimeError("evaluate(): envs still active after ceil(jobs / B) * max_steps steps")
+        return EvalResult.from_records(ev.records().reshape(-1)[:len(jobs)], jobs)
 
     def _render1(self, out, only=None):
         """single-frame raster of every (or the masked) view into `out`"""
@@ -1500,7 +1624,8 @@ class WaypointSuiteEnv(_GymEnvBase):
         return int(self._env.state["reached"][0])
 
     def reset(self, seed=None, options=None):                       # ref gym_env.py:319-349
-        obs = self._env.reset()
+        """options={"scenario": i}: start in scenario i of the suite instead of a drawn one (BatchedWaypointEnv.reset)"""
+        obs = self._env.reset(options=options)
         if self._video is not None:
             self._video.start()                                      # (the reference builds a new recording wrapper per reset)
             self._video_views = None                                 # (the env's map may have changed)

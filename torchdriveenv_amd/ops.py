@@ -136,6 +136,79 @@ def env_reset(cfg, dworld, state, mask=None):
                                _lib.current_stream(state.device)), "tde_env_reset")
 
 
+def check_scenario_ids(ids, B, n_scn):
+    """the checks of reset(options={"scenario": ids}) that need no GPU: an int, a sequence of B ints or an integer tensor [B], every
+    id in [-1, n_scn) (-1: draw the scenario) -> int32 [B] host tensor"""
+    if isinstance(ids, bool) or (isinstance(ids, float) and int(ids) != ids):
+        raise ValueError("scenario ids must be integers")
+    if torch.is_tensor(ids):
+        if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise ValueError(f"scenario ids must be an integer tensor, got {ids.dtype}")
+        t = ids.detach().cpu().to(torch.int64).reshape(-1)
+    else:
+        try:
+            a = np.asarray(ids)
+        except Exception as ex:
+            raise ValueError(f"scenario ids must be an int, a sequence of ints or an integer tensor: {ex}") from ex
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"scenario ids must be integers, got dtype {a.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(a, np.int64).reshape(-1))
+    if (ids.dim() if torch.is_tensor(ids) else np.ndim(ids)) == 0:
+        t = t.expand(int(B)).contiguous()                           # one id: every env
+    if t.numel() != int(B):
+        raise ValueError(f"scenario ids must be one int or {int(B)} of them, got {t.numel()}")
+    if t.numel() and (int(t.min()) < -1 or int(t.max()) >= int(n_scn)):
+        raise ValueError(f"scenario ids must be in [-1, {int(n_scn)}) (-1: draw), got {int(t.min())} .. {int(t.max())}")
+    return t.to(torch.int32)
+
+
+def env_reset_to(cfg, dworld, state, scn=None, mask=None):
+    """tde_env_reset_to: tde_env_reset with the scenario of env e given by scn[e] >= 0 (int32 [B] on the device; < 0, or scn None:
+    drawn as env_reset draws it).  An id >= n_scn leaves its env unwritten (the kernel cannot raise).  Asynchronous."""
+    L = _lib.load()
+    dev = torch.device(state.device)
+    pm = _chk(mask, torch.uint8, state.B, "mask", dev, optional=True)
+    ps = _chk(scn, torch.int32, state.B, "scn", dev, optional=True)
+    _lib.check(_call(dev, L.tde_env_reset_to, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), pm, ps,
+                     _lib.current_stream(dev)), "tde_env_reset_to")
+
+
+class EvalBuffers:
+    """the device arrays of a tde_eval for B envs x R episodes: plan int32 [R, B], round int32 [B], active uint8 [B], acc / results as
+    raw bytes (uint8 [B, 48] / [R, B, 48]: tde_episode_record rows, _abi.EPISODE_RECORD_DTYPE on the host)"""
+
+    def __init__(self, plan, device):
+        plan = torch.as_tensor(plan, dtype=torch.int32)
+        if plan.dim() != 2 or plan.shape[0] < 1:
+            raise ValueError(f"plan must be int32 [R >= 1, B], got {tuple(plan.shape)}")
+        self.R, self.B = int(plan.shape[0]), int(plan.shape[1])
+        self.plan = plan.to(device).contiguous()
+        self.round = torch.zeros(self.B, dtype=torch.int32, device=device)
+        self.active = torch.zeros(self.B, dtype=torch.uint8, device=device)
+        self.acc = torch.zeros((self.B, 48), dtype=torch.uint8, device=device)
+        self.results = torch.zeros((self.R, self.B, 48), dtype=torch.uint8, device=device)
+        self.struct = _abi.TdeEval(self.plan.data_ptr(), self.round.data_ptr(), self.active.data_ptr(), self.acc.data_ptr(),
+                                   self.results.data_ptr(), self.R, 0)
+
+    def records(self):
+        """the results on the host: a numpy record array [R, B] of _abi.EPISODE_RECORD_DTYPE (synchronises)"""
+        return self.results.cpu().numpy().view(_abi.EPISODE_RECORD_DTYPE).reshape(self.R, self.B)
+
+
+def eval_advance(cfg, dworld, state, ev):
+    """tde_eval_advance after an env_step made WITHOUT TDE_F_AUTORESET: fold the step into the running episode records of `ev`
+    (EvalBuffers), record the episodes it finished and re-spawn their envs to the next planned scenario.  One launch, asynchronous."""
+    L = _lib.load()
+    dev = torch.device(state.device)
+    if ev.B != state.B:
+        raise ValueError(f"the evaluation buffers are for {ev.B} envs, the state has {state.B}")
+    for n in ("plan", "round", "active", "acc", "results"):
+        if getattr(ev, n).device != dev:
+            raise ValueError(f"eval.{n} is on {getattr(ev, n).device}, expected {dev}")
+    _lib.check(_call(dev, L.tde_eval_advance, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(ev.struct),
+                     _lib.current_stream(dev)), "tde_eval_advance")
+
+
 def _no_near_field(dworld, what):
     if getattr(dworld, "near_field", None) is not None:
         raise NotImplementedError(f"{what} re-spawns finished envs inside one launch, where the near-field spawner cannot run: "
