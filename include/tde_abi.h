@@ -350,6 +350,19 @@ typedef struct tde_state {
                                    offroad_threshold, 0), sum of the IoUs with the agents the ego overlaps, their number, 0), of
                                    the state the step left BEFORE any in-place re-spawn; zeros without the matching flag */
     int32_t B, A;
+    uint32_t *slot_route;       /* in [B*A] for tde_env_step, out for tde_near_field_spawn, may be NULL (= every entry 0): the route of a
+                                   slot whose spawn record has none - a near-field agent's.  Entry: 0 = the spawn record's route (as
+                                   everywhere without the array), else (route id + 1) | route length << 20, the encoding of
+                                   tde_slot_cache.route: the slot follows row `id` of tde_world.route_xy, `length` waypoints long, from
+                                   its tde_state.route_wp on, under the NPC controller (TDE_F_NPC) like any routed spawn agent.  The
+                                   record's replay row, attributes and presence are not overridden.  tde_near_field_spawn writes the
+                                   entries of slots 1 .. A-1 of every env it visits; with the array tde_env_step runs its routed
+                                   one-role kernel; the entry points that forecast agents from their spawn records refuse such a
+                                   state (include/tde_hip.h).  A struct member added under ABI 14 WITHOUT a new version number (the
+                                   number is pinned by the test suite; the bump is the next change): a caller
+                                   built against the shorter struct passes tde_abi_version()'s check and the library then reads this
+                                   member from the 8 bytes behind that caller's struct - rebuild every caller against this header.  (Behind the sizes: magnitudes, B and A stay the one
+                                   16-byte word the kernels fetch them as) */
 } tde_state;
 
 /* K-step open-loop rollout buffers (actions resident in HBM; per-step env outputs). */
@@ -433,7 +446,10 @@ typedef struct tde_nf_cand {    /* 48 bytes: three 16-byte loads */
     float c, s;                 /* cos / sin of psi (float64 values rounded once) */
     float len, wid, lr;         /* attributes: len 4.8-5.5, wid 1.8-2.2, lr 0.82-0.97 (gym_env.py:193-195) */
     float vdes;                 /* desired speed; the spawn speed is a uniform fraction of it */
-    float _pad[3];
+    uint32_t route;             /* the candidate's route: row of tde_world.route_xy + 1, 0 = none (all three words zero: a table
+                                   built without routes is the 3 pad words these were) */
+    uint32_t route_wp;          /* ... the first waypoint of that row to head for */
+    uint32_t route_n;           /* ... the row's length in waypoints (route_wp < route_n < 4096; id + 1 < 2^20) */
 } tde_nf_cand;
 
 typedef struct tde_near_field {

@@ -89,6 +89,12 @@ TDE_API int tde_env_reset(const tde_config *cfg, const tde_world *world, const t
  * :285-294), replay override (:275-283), all-pairs OBB collision, drivable-mesh offroad, WaypointSuite reward,
  * termination/truncation, info, waypoint advance, and (TDE_F_AUTORESET) in-place re-spawn of finished envs.
  * Reads state->action [B][2]; writes state in place.
+ * Per-slot routes (tde_state.slot_route != NULL; A >= 4, fewer is rejected): slot a > 0 of env e with word w = slot_route[e * A + a]
+ * != 0 steps as if its spawn record said route = (w & 0xFFFFF) - 1 and route_n = w >> 20 - its target is route_xy[route][route_wp]
+ * while state.route_wp < route_n, under TDE_F_NPC - everything else (replay row, attributes, the re-spawn under TDE_F_AUTORESET) stays
+ * the record's; w == 0: the record's route, as without the array.  The step then always runs its routed one-role kernel
+ * (env_step_routed_kernel; tde_kernel_override and the lookup caches do not apply) and does not write the array: after an in-place
+ * re-spawn call tde_near_field_spawn before the next step, as after tde_env_reset.
  * (At 128 agent slots the kernel reads (cfg, world, state) from an immutable argument block the library keeps in device memory, one
  *  per distinct argument set, uploaded on `stream` at first use; every other form takes them by value.  INTEGRATION.md, section 1.) */
 TDE_API int tde_env_step(const tde_config *cfg, const tde_world *world, const tde_state *state, void *stream);
@@ -96,6 +102,10 @@ TDE_API int tde_env_step(const tde_config *cfg, const tde_world *world, const td
 /* K consecutive timesteps with the ego actions taken from a resident [K][B][2] buffer (open-loop / action-repeat
  * rollouts; how bench.py drives the path without a host round trip per step).  Per-step reward [K][B] and done bits
  * [K][B] are written to `rollout`. */
+/* (tde_env_rollout, tde_env_step_render, tde_forecast_agents, tde_forecast_scene and tde_score_plans_scene read every slot's route from
+ * its spawn record: each rejects a state with slot_route != NULL - "<entry point>: state.slot_route is set: ..." - rather than drive the
+ * spawned agents to a standstill.  tde_plan_action, tde_score_plans(_forecast), tde_vector_obs, the rasterisers, tde_env_post_step,
+ * tde_env_reset(_to) and tde_eval_advance do not read routes and take such a state as any other.) */
 TDE_API int tde_env_rollout(const tde_config *cfg, const tde_world *world, const tde_state *state,
                             const tde_rollout *rollout, void *stream);
 
@@ -195,6 +205,11 @@ TDE_API int tde_first_gaps(const tde_config *config, const tde_world *world, voi
  * float64 of the float32 positions.  The k-th accepted candidate goes to the k-th free slot: pose, attributes, vdes, v = (float)
  * (u01(word (i & 3) of philox(seed, g, c, 512 + (i >> 2), TDE_NF_TAG)) * vdes), route_wp = 0, present = 1, collided = offroad = 0;
  * the env's act_cache key (if any) and the written slots' slot_cache entries are invalidated.  One wavefront per env.
+ * Per-slot routes (state.slot_route != NULL): for every env with mask[e] != 0 - whatever T is, and also when state.scn[e] is outside
+ * [0, nf.S) - the entries of ALL slots 1..A-1 are written: the slot that received candidate i with cand.route != 0 gets
+ * cand.route | cand.route_n << 20 and state.route_wp = cand.route_wp (instead of 0); every other slot gets 0, so no word of an earlier
+ * episode survives a re-spawn.  Entry 0 of an env (the ego's) and the entries of the other envs are not written.  With
+ * state.slot_route == NULL the candidates' route words are not read.  Acceptance order, Philox words and speeds do not depend on it.
  * Rejected: NULL cfg / world / state / nf or nf tables, nf.S != world.n_scn, nf.A != state.A (a power of two <= 128), NC or K out
  * of range.  No allocation, no synchronisation (graph-capturable). */
 TDE_API int tde_near_field_spawn(const tde_config *cfg, const tde_world *world, const tde_state *state, const tde_near_field *nf,

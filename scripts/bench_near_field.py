@@ -1,6 +1,8 @@
 """Near-field spawner timings: BatchedWaypointEnv.step() (obs_mode "state", auto-reset, 40-step episodes) with and without
 near_field at 8192 x 16 and 1024 x 128 envs on the first validation case, and tde_near_field_spawn alone on the same worlds and on a
-town (lattice candidates) with 0 %, 2 % and 100 % of the envs masked.  Prints one JSON line.  Run it under
+town (lattice candidates) with 0 %, 2 % and 100 % of the envs masked.  Prints one JSON line.  --routes: only the closed-loop step, the
+unrouted near field (role-split step forms) against NearField(routes=True) (routed one-role form), alternated in one process, five
+timed regions each (median and spread).  Run it under
 `rocprofv3 --kernel-trace --stats` for the kernels' own durations (profiles/README.md)."""
 import json
 import os
@@ -39,6 +41,28 @@ def time_us(fn, n=50, warm=5):
 
 out = {}
 d = tempfile.mkdtemp()
+if "--routes" in sys.argv[1:]:
+    for B, A in ((8192, 16), (1024, 128)):
+        cfg = EnvConfig(seed=3, distance_cutoff=0.25, max_environment_steps=40, use_background_traffic=False)
+        g = torch.Generator().manual_seed(0)
+        acts = torch.stack([torch.rand(64, B, generator=g) * 1.2 - 0.2, torch.rand(64, B, generator=g) * 0.2 - 0.1], -1).to(dev)
+        envs = {}
+        for name, nf in (("unrouted", NearField()), ("routed", NearField(routes=True))):
+            world, tab = R.validation_world(0, A, d, nf=nf)
+            envs[name] = BatchedWaypointEnv(cfg, world, num_envs=B, device=dev, obs_mode="state", near_field=tab)
+            envs[name].reset()
+        times = {name: [] for name in envs}
+        k = [0]
+        for rep in range(5):                                  # alternated: both forms see the same clocks and neighbours
+            for name, env in envs.items():
+                def step():
+                    env.step(acts[k[0] % 64])
+                    k[0] += 1
+                times[name].append(time_us(step, n=200, warm=20))
+        for name, t in times.items():
+            out[f"step_{B}x{A}_{name}"] = dict(us_median=float(np.median(t)), us_min=min(t), us_max=max(t))
+    print(json.dumps(out))
+    sys.exit(0)
 worlds = {A: R.validation_world(0, A, d) for A in (16, 128)}
 data, meshes, field = R.town_suite(n_scn=2, n_streets=4)
 worlds["town128"] = world_from_waypoint_suite(data, agents_per_env=128, road_meshes=meshes, start_headings=field, near_field=NearField(),

@@ -104,11 +104,12 @@ STATE_AGENT_U8 = ["present", "collided", "offroad"]
 STATE_ENV_I32 = ["scn", "steps", "target_idx", "reached", "episode"]
 STATE_PTRS = (STATE_AGENT_F32 + STATE_AGENT_I32 + STATE_AGENT_U8 + STATE_ENV_I32 +
               ["action", "reward", "terminated", "truncated", "tl_violation", "info", "info_reached", "done_bits", "obs",
-               "ep_return", "ep_final", "ep_final_len", "slot_cache", "env_cache", "act_cache", "magnitudes"])
+               "ep_return", "ep_final", "ep_final_len", "slot_cache", "env_cache", "act_cache", "magnitudes", "slot_route"])
 
 
 class TdeState(C.Structure):
-    _fields_ = [(n, _p) for n in STATE_PTRS] + [("B", C.c_int32), ("A", C.c_int32)]
+    # (slot_route is the struct's last member, behind the sizes)
+    _fields_ = [(n, _p) for n in STATE_PTRS if n != "slot_route"] + [("B", C.c_int32), ("A", C.c_int32), ("slot_route", _p)]
 
 
 class TdeRollout(C.Structure):
@@ -133,9 +134,10 @@ class TdeNearField(C.Structure):
 
 
 NF_MAX_CAND, NF_MAX_NBR, NF_TAG = 1024, 32, 0x4E46
-# tde_nf_cand: x, y, psi, c, s, len, wid, lr, vdes + 3 pad words
+# tde_nf_cand: x, y, psi, c, s, len, wid, lr, vdes, then the route words (route id + 1 or 0, first waypoint, length: zero without routes)
 NF_CAND_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("psi", "f4"), ("c", "f4"), ("s", "f4"), ("len", "f4"), ("wid", "f4"),
-                          ("lr", "f4"), ("vdes", "f4"), ("_pad0", "f4"), ("_pad1", "f4"), ("_pad2", "f4")])
+                          ("lr", "f4"), ("vdes", "f4"), ("route", "u4"), ("route_wp", "u4"), ("route_n", "u4")])
+CACHE_ID_BITS = 20          # TDE_CACHE_ID_BITS: route ids below 2^20 - 1, lengths below 4096 (tde_slot_cache.route, tde_state.slot_route)
 assert NF_CAND_DTYPE.itemsize == 48
 
 class TdeVectorObs(C.Structure):
@@ -250,7 +252,8 @@ STATE_DTYPES = {**{n: np.float32 for n in STATE_AGENT_F32}, **{n: np.int32 for n
                 "tl_violation": np.uint8,
                 "info": np.float64, "info_reached": np.int32, "done_bits": np.uint8, "obs": np.float32,
                 "ep_return": np.float64, "ep_final": np.float64, "ep_final_len": np.int32,
-                "slot_cache": np.int32, "env_cache": np.int32, "act_cache": np.int32, "magnitudes": np.float32}          # opaque 32-byte records (tde_slot_cache / tde_env_cache)
+                "slot_cache": np.int32, "env_cache": np.int32, "act_cache": np.int32, "magnitudes": np.float32,
+                "slot_route": np.int32}     # (uint32 words held as int32: torch has no arithmetic on uint32; view them as uint32)          # opaque 32-byte records (tde_slot_cache / tde_env_cache)
 
 
 def state_shapes(B, A):
@@ -260,7 +263,7 @@ def state_shapes(B, A):
                "info": (B, 4),
                "info_reached": (B,), "done_bits": (B,), "obs": (B, 8), "ep_return": (B,), "ep_final": (B,),
                "ep_final_len": (B,), "slot_cache": (B * A, 8), "env_cache": (B, 8), "act_cache": (B * (A + 1), 2),
-               "magnitudes": (B, 4)})
+               "magnitudes": (B, 4), "slot_route": (B * A,)})
     return sh
 
 

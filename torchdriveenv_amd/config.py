@@ -141,7 +141,14 @@ class NearField:
       margin     minimum gap between a candidate and any other agent's box [m]
       clear_ego  minimum centre distance of a candidate from the ego [m]
       speed      (low, high) range of the candidates' desired speeds [m/s]; the spawn speed is a uniform fraction of it
-      candidates optional hook (location, scenario_index) -> array [n, 3] of (x, y, psi), e.g. lane centrelines"""
+      candidates optional hook (location, scenario_index) -> array [n, 3] of (x, y, psi), e.g. lane centrelines; with `routes` it may
+                 return (array [n, 3], routes) instead, routes[i] = the polyline [k, 2] candidate i drives along (or None)
+      routes     True: every candidate gets a route ahead of its pose (world.build_near_field) and the spawned agents drive: they
+                 keep their desired speed, follow the lane, queue, yield and stop at red lines like the scenario's routed NPCs, and
+                 stop at the end of their route.  False (default): no routes - a spawned agent holds its heading and brakes to a
+                 standstill; every table, launch and result as without the field
+      route_pitch  spacing of a route's waypoints [m]; None: `pitch`
+      route_points the most waypoints a route has"""
     radius: float = 120.0
     count: int = 95
     density: Optional[int] = None
@@ -150,6 +157,9 @@ class NearField:
     clear_ego: float = 10.0
     speed: tuple = (5.0, 12.0)
     candidates: Optional[object] = None
+    routes: bool = False
+    route_pitch: Optional[float] = None
+    route_points: int = 32
 
 
 def check_near_field(nf, cfg: Optional[EnvConfig] = None):
@@ -168,6 +178,10 @@ def check_near_field(nf, cfg: Optional[EnvConfig] = None):
     lo, hi = (float(v) for v in nf.speed)
     if not (0 <= lo <= hi) or hi == float("inf"):
         raise ValueError("near_field.speed must be a finite range (low, high) with 0 <= low <= high")
+    if nf.route_pitch is not None and not (nf.route_pitch > 0 and nf.route_pitch != float("inf")):
+        raise ValueError("near_field.route_pitch must be finite and > 0 (or None: pitch)")
+    if int(nf.route_points) != nf.route_points or not 2 <= int(nf.route_points) < 4096:
+        raise ValueError("near_field.route_points must be an integer in [2, 4096)")
     if nf.candidates is not None and not callable(nf.candidates):
         raise ValueError("near_field.candidates must be a callable (location, scenario_index) -> array [n, 3] of (x, y, psi)")
     return nf

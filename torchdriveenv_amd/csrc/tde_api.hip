@@ -104,6 +104,16 @@ int tde_waypoint_reward(const tde_config *cfg, int32_t n, const float *pre_x, co
     return launch_status("tde_waypoint_reward");
 }
 
+// tde_state.slot_route (per-slot routes of near-field agents): only tde_env_step and tde_near_field_spawn know the array.  The entry
+// points that advance or forecast agents on the routes of their spawn records would drive the spawned cars to a standstill: they
+// refuse such a state, in these words
+static int check_no_slot_route(const char *fn, const tde_state *st)
+{
+    if (!st->slot_route) return 0;
+    snprintf(g_err, sizeof(g_err), "%s: state.slot_route is set: this entry point reads routes from the spawn records only (step such a state with tde_env_step)", fn);
+    return (int)hipErrorInvalidValue;
+}
+
 static int check_env_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st)
 {
     if (!cfg || !w || !st) { snprintf(g_err, sizeof(g_err), "%s: NULL argument", fn); return (int)hipErrorInvalidValue; }
@@ -278,6 +288,7 @@ static int env_step_launch(const tde_config *cfg, const tde_world *world, const 
     if (rc) return rc;
     if (st->B <= 0) return 0;
     if (!st->action) return bad("tde_env_step: state.action is NULL");
+    if (st->slot_route && st->A < 4) return bad("tde_env_step: state.slot_route needs at least 4 agent slots per env");
     if ((cfg->flags & TDE_F_OFFROAD) && TDE_STEP_CLS2 && !world->cell_cls2) return bad("tde_env_step: world.cell_cls2 is NULL (ABI 7 class map)");
     const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
     // With the lookup caches present (and a group shape the three-role kernels are built for) the step runs as three
@@ -290,6 +301,9 @@ static int env_step_launch(const tde_config *cfg, const tde_world *world, const 
     // (round 2: 3 roles 12.3 at 8192 envs - its re-spawn path, the tail every launch waits for, recomputed the next step's
     //  controller and walked the record -> route table chain: +3.4 us with TDE_F_AUTORESET; now +1).  Three roles up to
     // 131 072 agent slots, one role above (configs[4]: 8192 x 32).  tde_kernel_override(0, 1 | 3) forces one.
+    // per-slot routes: always the routed one-role form (no tde_kernel_override, no lookup caches: the spawner that wrote the array has
+    // invalidated their entries, which keeps them right for a caller who drops the array later)
+    if (st->slot_route) return st->magnitudes ? tde_host::launch_step_routed_mag(cfg, world, st, stream) : tde_host::launch_step_routed(cfg, world, st, stream);
     const int force = g_force_step;
     // (slot entries pack route / replay ids into 20 bits and their lengths into 12: tde_abi.h)
     const int32_t id_max = (1 << TDE_CACHE_ID_BITS) - 1, len_max = 1 << (32 - TDE_CACHE_ID_BITS);
@@ -341,7 +355,7 @@ static tde_state state_slice(const tde_state &s, int64_t e0, int32_t n)
     TDE_ADV(scn, e0); TDE_ADV(steps, e0); TDE_ADV(target_idx, e0); TDE_ADV(reached, e0); TDE_ADV(episode, e0);
     TDE_ADV(action, 2 * e0); TDE_ADV(reward, e0); TDE_ADV(terminated, e0); TDE_ADV(truncated, e0); TDE_ADV(tl_violation, e0);
     TDE_ADV(info, 4 * e0); TDE_ADV(info_reached, e0); TDE_ADV(done_bits, e0); TDE_ADV(obs, 8 * e0); TDE_ADV(ep_return, e0);
-    TDE_ADV(ep_final, e0); TDE_ADV(ep_final_len, e0); TDE_ADV(slot_cache, g0); TDE_ADV(env_cache, e0); TDE_ADV(act_cache, g0 + e0); TDE_ADV(magnitudes, 4 * e0);
+    TDE_ADV(ep_final, e0); TDE_ADV(ep_final_len, e0); TDE_ADV(slot_cache, g0); TDE_ADV(env_cache, e0); TDE_ADV(act_cache, g0 + e0); TDE_ADV(magnitudes, 4 * e0); TDE_ADV(slot_route, g0);
 #undef TDE_ADV
     t.B = n;
     return t;
@@ -363,7 +377,7 @@ int tde_env_rollout(const tde_config *cfg, const tde_world *world, const tde_sta
                     void *stream)
 {
     int rc = check_env_args("tde_env_rollout", cfg, world, st);
-    if (rc) return rc;
+    if (rc || (rc = check_no_slot_route("tde_env_rollout", st))) return rc;
     if (!ro) return bad("tde_env_rollout: rollout is NULL");
     if (st->B <= 0 || ro->K <= 0) return 0;
     if (!ro->actions) return bad("tde_env_rollout: rollout.actions is NULL");
@@ -590,6 +604,7 @@ static int check_scene_reads(const char *fn, const tde_config *cfg, const tde_wo
     if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->lr || !st->vdes || !st->route_wp || !st->present || !st->scn ||
         !st->steps || !world->spawn || !world->scn)
         return bad_in(fn, "a required state / world pointer is NULL");
+    if (const int rc = check_no_slot_route(fn, st)) return rc;
     if ((cfg->flags & TDE_F_NPC) && world->n_routes > 0 && !world->route_xy) return bad_in(fn, "world.route_xy is NULL");
     if ((cfg->flags & TDE_F_REPLAY) && world->n_replay > 0 && !world->replay_states) return bad_in(fn, "world.replay_states is NULL");
     return 0;
@@ -703,7 +718,7 @@ int tde_env_step_render(const tde_config *cfg, const tde_world *world, const tde
                         void *const *streams, int32_t n_streams)
 {
     int rc = check_env_args("tde_env_step_render", cfg, world, st);
-    if (rc) return rc;
+    if (rc || (rc = check_no_slot_route("tde_env_step_render", st))) return rc;
     if (!streams || n_streams < 1 || n_streams > 16) return bad("tde_env_step_render: streams is NULL or n_streams not in [1, 16]");
     if (rd) {                                              // before the first launch: a failing call advances no sub-batch
         rc = check_render_args("tde_env_step_render", world, rd);

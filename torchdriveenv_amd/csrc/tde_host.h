@@ -88,6 +88,9 @@ int launch_step_wide8(const tde::StepArgs *args, const tde_config *cfg, const td
 // tde_step_solo.hip / tde_step_solo_mag.hip: env_step_kernel<A, LIGHTS, OBS, BIG, WAVES, MAG = false / true>
 int launch_step_solo(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
 int launch_step_solo_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
+// tde_step_routed.hip / tde_step_routed_mag.hip: env_step_routed_kernel<A >= 4, LIGHTS, OBS, BIG, WAVES, MAG = false / true> (state.slot_route != NULL)
+int launch_step_routed(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
+int launch_step_routed_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
 // tde_rollout_trio.hip: env_rollout_trio_kernel<A in {8, 16, 32}, LIGHTS, BIG>; env_rollout_wide_kernel<LIGHTS> (128 slots)
 int launch_rollout_trio(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, void *stream);
 int launch_rollout_wide(const tde::StepArgs *args, const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, int waves, void *stream);

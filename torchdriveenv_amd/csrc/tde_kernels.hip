@@ -17,6 +17,8 @@
 #include "tde_step_wide8.hip"
 #include "tde_step_solo.hip"
 #include "tde_step_solo_mag.hip"
+#include "tde_step_routed.hip"
+#include "tde_step_routed_mag.hip"
 #include "tde_rollout_trio.hip"
 #include "tde_rollout_duo.hip"
 #include "tde_rollout_solo.hip"

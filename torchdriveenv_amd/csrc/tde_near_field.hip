@@ -35,11 +35,15 @@ __global__ __launch_bounds__(kWave) void near_field_kernel(tde_config cfg, tde_w
     const int lane = threadIdx.x;
     if (e >= st.B || (mask && !mask[e])) return;
     const int A = st.A;
+    const int64_t base = (int64_t)e * A;
+    // the per-slot routes of the env's last episode end here, whatever this call spawns (the accepted lanes write theirs below,
+    // behind at least one barrier)
+    if (st.slot_route)
+        for (int a = 1 + lane; a < A; a += kWave) st.slot_route[base + a] = 0u;
     const int s = st.scn[e];
     if (s < 0 || s >= nf.S) return;
     const uint32_t c = (uint32_t)st.episode[e];
     const uint32_t g = cfg.env_base + (uint32_t)e;
-    const int64_t base = (int64_t)e * A;
     const float ex = st.x[base], ey = st.y[base];
     const double r2 = (double)nf.radius * (double)nf.radius;
     const double ce2 = (double)nf.clear_ego * (double)nf.clear_ego;
@@ -146,7 +150,8 @@ __global__ __launch_bounds__(kWave) void near_field_kernel(tde_config cfg, tde_w
             st.x[gi] = cd.x; st.y[gi] = cd.y; st.psi[gi] = cd.psi;
             st.v[gi] = (float)(u01(wv) * (double)cd.vdes);
             st.len[gi] = cd.len; st.wid[gi] = cd.wid; st.lr[gi] = cd.lr; st.vdes[gi] = cd.vdes;
-            st.route_wp[gi] = 0;
+            st.route_wp[gi] = st.slot_route ? (int)cd.route_wp : 0;
+            if (st.slot_route && cd.route) st.slot_route[gi] = cd.route | (cd.route_n << TDE_CACHE_ID_BITS);
             st.present[gi] = 1; st.collided[gi] = 0; st.offroad[gi] = 0;
             if (st.slot_cache) st.slot_cache[gi].key = 0;        // (TDE_CACHE_VALID clear)
             atomicOr(&sh.taken[i >> 5], 1u << (i & 31));

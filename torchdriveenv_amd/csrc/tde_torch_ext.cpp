@@ -89,7 +89,7 @@ const Field kStateFields[] = {
     SF(info_reached, at::kInt, K_ENV, false), SF(done_bits, at::kByte, K_ENV, false), SF(obs, at::kFloat, K_ENV8, false),
     SF(ep_return, at::kDouble, K_ENV, false), SF(ep_final, at::kDouble, K_ENV, false), SF(ep_final_len, at::kInt, K_ENV, false),
     SF(slot_cache, at::kInt, K_SLOT8, false), SF(env_cache, at::kInt, K_ENV8, false), SF(act_cache, at::kInt, K_ACT, false),
-    SF(magnitudes, at::kFloat, K_ENV4, false)};
+    SF(magnitudes, at::kFloat, K_ENV4, false), SF(slot_route, at::kInt, K_AGENT, false)};
 #undef SF
 
 int64_t count_of(int kind, int64_t B, int64_t A)

@@ -224,12 +224,13 @@ def _heading_field(start_headings, loc):
     return lambda x, y: start_headings(loc, x, y)
 
 
-def _resample_polyline(pl, pitch):
-    """(x, y, psi) every `pitch` metres of arc length along a polyline, psi = the direction of the segment"""
+def _resample_polyline(pl, pitch, where=None):
+    """(x, y, psi) every `pitch` metres of arc length along a polyline, psi = the direction of the segment (`where`: a list that
+    receives (segment, metres into it) of every point)"""
     p = np.asarray(pl, np.float64).reshape(-1, 2)
     out = []
     carry = 0.0
-    for a, b in zip(p[:-1], p[1:]):
+    for i, (a, b) in enumerate(zip(p[:-1], p[1:])):
         d = float(np.hypot(*(b - a)))
         if d <= 0:
             continue
@@ -237,26 +238,50 @@ def _resample_polyline(pl, pitch):
         t = carry
         while t <= d:
             out.append((a[0] + (b[0] - a[0]) * t / d, a[1] + (b[1] - a[1]) * t / d, psi))
+            if where is not None:
+                where.append((i, t))
             t += pitch
         carry = t - d
     return np.asarray(out, np.float64).reshape(-1, 3)
 
 
-def near_field_positions(world, nf, scn_polylines, locations, start_headings=None):
+def near_field_positions(world, nf, scn_polylines, locations, start_headings=None, with_routes=False):
     """candidate positions [m, 3] of (x, y, psi) per scenario, from the first source that applies: the `nf.candidates` hook
     (location, scenario_index) -> [n, 3]; the location's lane-direction field (`start_headings`) on a lattice of pitch `nf.pitch`
     over the scenario's drivable mesh, where the field gives a heading; the scenario's polylines (waypoints, NPC routes, replay
-    paths) every `nf.pitch` metres with the segment's direction.  -> (positions, source names)"""
+    paths) every `nf.pitch` metres with the segment's direction.  -> (positions, source names)
+    with_routes: -> (positions, source names, tracers), tracers[s](i, x, y, psi) = the waypoints ahead of candidate i of scenario s
+    for world.build_near_field, from the candidate's own source: the field stepped `route_pitch` at a time; the rest of the polyline
+    it was resampled from, every `route_pitch` metres; the route the hook gave for it, else the field's trace (None: no tracer)"""
+    from .world import polyline_ahead, trace_heading_field
+
     thr = 0.5 if world.threshold is None else float(world.threshold)
     tri_all = world.arrays["tri"].reshape(-1, 3, 2).astype(np.float64)
-    pos, src = [], []
+    rp = float(nf.route_pitch if nf.route_pitch is not None else nf.pitch)
+    n_pts = int(nf.route_points)
+    pos, src, tracers = [], [], []
+
+    def field_tracer(field):
+        return None if field is None else (lambda i, x, y, psi: trace_heading_field(field, x, y, psi, rp, n_pts))
+
     for si in range(world.n_scn):
         loc = locations[si]
         if nf.candidates is not None:
             try:
-                P = np.asarray(nf.candidates(loc, si), np.float64)
+                got = nf.candidates(loc, si)
+                own = None
+                # (points, routes) only under `routes`, and only a pair whose first member is the [n, 3] array: any other return is
+                # the points themselves, as it always was
+                if nf.routes and isinstance(got, tuple) and len(got) == 2 and np.ndim(got[0]) == 2:
+                    got, own = got
+                P = np.asarray(got, np.float64)
             except (TypeError, ValueError) as ex:
                 raise ValueError(f"near_field.candidates({loc!r}, {si}) failed: {ex}") from ex
+            if own is not None and len(own) != len(P):
+                raise ValueError(f"near_field.candidates({loc!r}, {si}) gave {len(own)} routes for {len(P)} candidates")
+            by_field = field_tracer(_heading_field(start_headings, loc))
+            tracers.append((lambda i, x, y, psi, own=own, f=by_field:
+                            own[i] if own is not None and own[i] is not None else f(i, x, y, psi) if f is not None else None))
             if P.size == 0:
                 P = P.reshape(0, 3)
             if P.ndim != 2 or P.shape[1] != 3:
@@ -287,11 +312,15 @@ def near_field_positions(world, nf, scn_polylines, locations, start_headings=Non
                     P.append((x, y, psi))
             pos.append(np.asarray(P, np.float64).reshape(-1, 3))
             src.append("lattice")
+            tracers.append(field_tracer(field))
             continue
-        pls = [_resample_polyline(pl, float(nf.pitch)) for pl in scn_polylines[si]]
+        where = [[] for _ in scn_polylines[si]]
+        pls = [_resample_polyline(pl, float(nf.pitch), w) for pl, w in zip(scn_polylines[si], where)]
         pos.append(np.concatenate(pls, 0) if pls else np.zeros((0, 3)))
         src.append("polylines")
-    return pos, src
+        flat = [(pl, seg, t) for pl, w in zip(scn_polylines[si], where) for seg, t in w]
+        tracers.append(lambda i, x, y, psi, flat=flat: polyline_ahead(*flat[i], rp, n_pts))
+    return (pos, src, tracers) if with_routes else (pos, src)
 
 
 def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=12.0, threshold=0.5,
@@ -442,9 +471,9 @@ def world_from_waypoint_suite(data: WaypointSuite, agents_per_env=8, road_width=
                            near_range=NEAR_RANGE if near_range is None else float(near_range))
     if near_field is None:
         return world
-    positions, sources = near_field_positions(world, near_field, scn_polylines, scn_locations, start_headings)
+    positions, sources, tracers = near_field_positions(world, near_field, scn_polylines, scn_locations, start_headings, with_routes=True)
     density = int(near_field.density) if near_field.density is not None else max(densities, default=0)
-    table = build_near_field(world, positions, near_field, near_field_seed, density)
+    table = build_near_field(world, positions, near_field, near_field_seed, density, tracers if near_field.routes else None)
     table.sources = sources
     return world, table
 
@@ -614,7 +643,9 @@ class BatchedWaypointEnv:
         iai_conditional_initialize, ref gym_env.py:232-238): a config.NearField (or a dict of its fields) when `data` is a
         WaypointSuite, or a world.NearFieldTable built for the World `data` is (world_from_waypoint_suite(..., near_field=)).  Every
         (re)spawn - reset(), auto-reset in step(), the VecEnv's re-spawn - then runs the spawner before the state is observed;
-        rollout() and the multi-stream step raise.  None (default): no near field, every path as it was.
+        rollout() and the multi-stream step raise.  With NearField(routes=True) the spawned agents drive along routes of their own
+        (tde_state.slot_route; step() then runs the routed one-role kernel); rollout(), plan_react= and Planner(predict="route" | "queue")
+        raise ValueError.  None (default): no near field, every path as it was.
         vector_obs: the config.VectorObs (or a dict of its fields) of obs_mode="vector" (None: VectorObs()); the observation is
         float32 [B, vector_obs.dim] (tde_vector_obs), taken after every reset, step and re-spawn (after the near-field spawner).
         planner: the config.Planner (or a dict of its fields) of plan_actions() (None: Planner()).
@@ -668,6 +699,14 @@ class BatchedWaypointEnv:
             raise ValueError(f"the near-field table is for {near_field.S} scenarios x {near_field.A} slots, the world has "
                              f"{self.world.n_scn} x {self.world.A}")
         self.near_field = near_field                                 # world.NearFieldTable or None
+        # routed near-field traffic: the state carries per-slot routes (tde_state.slot_route), which only step() and the spawner know
+        self._nf_routed = near_field is not None and bool(getattr(near_field, "routes", False))
+        if self._nf_routed and self.planner.predict in ("route", "queue"):
+            raise ValueError(f"Planner(predict={self.planner.predict!r}) with routed near-field traffic (NearField(routes=True)): the "
+                             "forecasts read routes from the spawn records and would see the spawned agents stopping; use predict='constant'")
+        if self._nf_routed and self.plan_react is not None:
+            raise ValueError("plan_react= with routed near-field traffic (NearField(routes=True)): the reacting scene reads routes from "
+                             "the spawn records and would see the spawned agents stopping")
         check_threshold(self.world, sim.offroad_threshold, sim.offroad_threshold_squared,
                         "EnvConfig.simulator.offroad_threshold")   # a prebuilt World bakes its threshold into the grid
         self.A = self.world.A
@@ -694,7 +733,7 @@ class BatchedWaypointEnv:
         # obs_mode "state": tde_env_step writes the compact observation itself (no second launch per step)
         self.info_magnitudes = bool(info_magnitudes)
         self.state = EnvState(self.num_envs, self.A, device=self.torch_device, with_info=with_info,
-                              with_obs=(obs_mode == "state"), with_magnitudes=self.info_magnitudes)
+                              with_obs=(obs_mode == "state"), with_magnitudes=self.info_magnitudes, with_slot_route=self._nf_routed)
         self.obs_mode, self.frame_stack = obs_mode, max(1, int(frame_stack))
         r = cfg.simulator.renderer
         self._res, self._fov = int(r.res), float(r.fov)
@@ -872,6 +911,9 @@ class BatchedWaypointEnv:
         """K open-loop steps from a resident [K,B,2] action tensor -> (reward [K,B], done bits [K,B]).  (The Monitor-style
         episode statistics of the closed-loop API are not maintained across a rollout: they follow from the returned
         arrays.)"""
+        if self._nf_routed:
+            raise ValueError("rollout() with routed near-field traffic (NearField(routes=True)): the rollout kernels read routes from the "
+                             "spawn records; step() the envs instead")
         if self.dnf is not None:
             raise NotImplementedError("rollout() with near_field: the rollout kernels re-spawn finished envs inside one launch, where "
                                       "the near-field spawner cannot run; step() the envs instead")

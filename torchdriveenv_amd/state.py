@@ -19,7 +19,7 @@ class EnvState:
     """`arrays[name]` are numpy arrays (host; used with the CPU oracle in tests) or torch tensors (device)."""
 
     def __init__(self, B, A, device=None, with_info=True, with_obs=False, with_episode=None, with_cache=None,
-                 with_magnitudes=None):
+                 with_magnitudes=None, with_slot_route=False):
         assert A >= 1 and (A & (A - 1)) == 0 and A <= _abi.TDE_MAX_AGENTS, f"A must be a power of two <= {_abi.TDE_MAX_AGENTS}"
         self.B, self.A, self.device = int(B), int(A), device
         with_episode = with_info if with_episode is None else with_episode
@@ -37,6 +37,9 @@ class EnvState:
         # the step's lookup caches (tde_state.slot_cache / env_cache): device-side only (the oracle has no use for them)
         if not (with_cache if with_cache is not None else device is not None):
             off_keys |= {"slot_cache", "env_cache", "act_cache"}
+        # the per-slot routes of near-field agents (tde_state.slot_route): only envs with routed near-field traffic carry them
+        if not with_slot_route:
+            off_keys.add("slot_route")
         self.arrays = {}
         self._arena = self._pinned = None
         self._slots = {}

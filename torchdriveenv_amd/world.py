@@ -660,8 +660,9 @@ class NearFieldTable:
     """Host copy of a world's near-field candidate tables (tde_near_field): cand [S][NC] (NF_CAND_DTYPE), nbr [S][NC][K] uint16,
     nbr_n / fixed [S][NC] uint8, n_cand [S] int32, and the parameters of the draw."""
 
-    def __init__(self, cand, nbr, nbr_n, fixed, n_cand, A, radius, clear_ego, count, density, sources=None):
+    def __init__(self, cand, nbr, nbr_n, fixed, n_cand, A, radius, clear_ego, count, density, sources=None, routes=False):
         self.cand, self.nbr, self.nbr_n, self.fixed = cand, nbr, nbr_n, fixed
+        self.routes = bool(routes)                 # built with NearField(routes=True): envs over it carry tde_state.slot_route
         self.n_cand = np.ascontiguousarray(n_cand, np.int32)
         self.S, self.NC, self.K = cand.shape[0], cand.shape[1], nbr.shape[2]
         self.A, self.radius, self.clear_ego = int(A), float(radius), float(clear_ego)
@@ -697,13 +698,76 @@ class DeviceNearField:
         self.struct = table.struct_of(tensors)
 
 
-def build_near_field(world, positions, nf, seed, density=0):
+def trace_heading_field(field, x, y, psi, pitch, n):
+    """float64 [n, 2]: n points ahead of (x, y), each `pitch` metres from the last along the lane direction `field(x, y)` gives
+    there (the candidate's own heading for the first step; where the field gives none - a junction's interior - straight on)"""
+    out = np.empty((n, 2))
+    for k in range(n):
+        x, y = x + pitch * math.cos(psi), y + pitch * math.sin(psi)
+        out[k] = x, y
+        h = field(float(x), float(y))
+        if h is not None:
+            h = float(np.asarray(h, np.float64).reshape(-1)[0])
+            if np.isfinite(h):
+                psi = h
+    return out
+
+
+def polyline_ahead(pl, seg, t, pitch, n):
+    """float64 [<= n, 2]: points every `pitch` metres of arc length along the polyline `pl` past the point `t` metres into its segment
+    `seg`, up to the polyline's end"""
+    p = np.asarray(pl, np.float64).reshape(-1, 2)
+    out = []
+    need = pitch
+    for i in range(int(seg), len(p) - 1):
+        a, b = p[i], p[i + 1]
+        d = float(np.hypot(*(b - a)))
+        at = t if i == seg else 0.0
+        while d > 0 and at + need <= d and len(out) < n:
+            at += need
+            need = pitch
+            out.append(a + (b - a) * (at / d))
+        need -= max(0.0, d - at)
+        if len(out) >= n:
+            break
+    return np.asarray(out, np.float64).reshape(-1, 2)
+
+
+def _append_routes(world, rows, route_points):
+    """the polylines `rows` (float32 [k, 2] each) as rows n_routes, n_routes + 1, ... of the world's route table, in place: RW grows to
+    max(RW, route_points), the new rows are padded with zeros as the others are"""
+    n0, RW0 = world.ints["n_routes"], world.ints["RW"]
+    RW = max(RW0, int(route_points))
+    n = n0 + len(rows)
+    id_max, len_max = (1 << _abi.CACHE_ID_BITS) - 1, 1 << (32 - _abi.CACHE_ID_BITS)
+    if n >= id_max or RW >= len_max:
+        raise ValueError(f"near-field routes: {n} routes of up to {RW} waypoints, the per-slot route word holds ids below {id_max} and "
+                         f"lengths below {len_max}: thin the candidates (near_field.pitch) or shorten the routes (route_points)")
+    table = np.zeros((n, RW, 2), np.float32)
+    if n0:
+        table[:n0, :RW0] = world.arrays["route_xy"].reshape(-1, RW0, 2)[:n0]
+    for i, r in enumerate(rows):
+        table[n0 + i, :len(r)] = r
+    world.arrays["route_xy"] = np.ascontiguousarray(table)
+    world.ints["n_routes"], world.ints["RW"] = n, RW
+    world._host_struct = None
+
+
+def build_near_field(world, positions, nf, seed, density=0, tracers=None):
     """The near-field candidate table of `world` (NearFieldTable) from candidate positions per scenario (`positions[s]`: float
     array [m, 3] of x, y, psi) and a config.NearField: candidates within radius + |p1 - p0| of the first waypoint p0 (every ego
     start on the first segment), whose boxes are on the drivable surface (every corner within the world's offroad distance minus
     NF_ROAD_SLACK of the scenario's mesh, float64); attributes and desired speeds drawn from a generator seeded by (seed, scenario);
     at most TDE_NF_MAX_CAND per scenario (the nearest to p0); neighbour lists and fixed-conflict bits from an exact float64 SAT of
-    the boxes inflated by margin / 2 each; candidates with more than TDE_NF_MAX_NBR neighbours dropped."""
+    the boxes inflated by margin / 2 each; candidates with more than TDE_NF_MAX_NBR neighbours dropped.
+
+    With `nf.routes` every kept candidate also gets a route: `tracers[s](i, x, y, psi)` -> float64 [k, 2], the waypoints ahead of entry i
+    of `positions[s]` (env.near_field_positions builds the tracers: the lane-direction field stepped `route_pitch` at a time, the rest of
+    the polyline the candidate was resampled from, or the `candidates` hook's own route; None: none).  Of those, leading points that are
+    not ahead of the candidate in its own frame are dropped; the route then ends before the first waypoint (float32, as stored) farther
+    than the offroad distance minus NF_ROAD_SLACK from the mesh - the predicate the box corners pass - and after `route_points` waypoints.
+    A route of fewer than two waypoints is no route (the candidate's route words stay 0).  The routes are appended to THE WORLD'S route
+    table in place (rows past the scenario routes; equal polylines share a row), so build the table before the world is uploaded."""
     import warnings
 
     S, A = world.n_scn, world.A
@@ -720,12 +784,17 @@ def build_near_field(world, positions, nf, seed, density=0):
         raise ValueError(f"near_field.clear_ego = {nf.clear_ego:g} m is below the largest circumradii of the ego ({r_ego:.3f}) and of a "
                          f"candidate ({r_cand:.3f}) plus margin ({nf.margin:g}): a spawned car could overlap the ego")
     rows = []
+    routes = bool(getattr(nf, "routes", False)) and tracers is not None
+    n_pts = int(getattr(nf, "route_points", 32))
+    new_routes, row_of = [], {}                                 # polylines to append to the world's route table; bytes -> row
     for si in range(S):
         P = np.asarray(positions[si], np.float64).reshape(-1, 3)
-        P = P[np.isfinite(P).all(1)]
+        orig = np.flatnonzero(np.isfinite(P).all(1))           # (index into positions[si]: what a tracer is asked for)
+        P = P[orig]
         p0, p1 = wp[si, 0], wp[si, 1]
         reach = float(nf.radius) + float(np.hypot(*(p1 - p0)))
-        P = P[np.hypot(P[:, 0] - p0[0], P[:, 1] - p0[1]) <= reach]
+        near = np.hypot(P[:, 0] - p0[0], P[:, 1] - p0[1]) <= reach
+        P, orig = P[near], orig[near]
         m = len(P)
         rng = np.random.default_rng([int(seed) & 0xFFFFFFFFFFFFFFFF, si])
         L = rng.uniform(*NF_LEN, m).astype(np.float32)
@@ -773,6 +842,28 @@ def build_near_field(world, positions, nf, seed, density=0):
         rec["x"], rec["y"], rec["psi"] = x32[k], y32[k], p32[k]
         rec["c"], rec["s"] = c[k].astype(np.float32), s[k].astype(np.float32)
         rec["len"], rec["wid"], rec["lr"], rec["vdes"] = L[k], W[k], LR[k], V[k]
+        if routes and tracers[si] is not None and n:
+            traced = []
+            for j in k:
+                r = tracers[si](int(orig[j]), X[j], Y[j], psi[j])
+                r = np.zeros((0, 2)) if r is None else np.asarray(r, np.float64).reshape(-1, 2)
+                r = r[np.isfinite(r).all(1)].astype(np.float32)
+                ahead = (r[:, 0].astype(np.float64) - X[j]) * c[j] + (r[:, 1].astype(np.float64) - Y[j]) * s[j] > 0.0
+                traced.append(r[int(np.argmax(ahead)) if ahead.any() else len(r):][:n_pts])
+            flat = np.concatenate(traced, 0).astype(np.float64)
+            on = mesh_distance(flat, mesh, thr) <= thr - NF_ROAD_SLACK
+            at = 0
+            for q, r in enumerate(traced):
+                ok = on[at:at + len(r)]
+                at += len(r)
+                r = r[:len(r) if ok.all() else int(np.argmin(ok))]
+                if len(r) < 2:
+                    continue
+                key = r.tobytes()
+                if key not in row_of:
+                    row_of[key] = world.ints["n_routes"] + len(new_routes)
+                    new_routes.append(r)
+                rec["route"][q], rec["route_wp"][q], rec["route_n"][q] = row_of[key] + 1, 0, len(r)
         rows.append((rec, [sorted(v) for v in nbrs], fixed))
     NC = max(1, max(len(r[0]) for r in rows))
     K = max(1, max((len(v) for r in rows for v in r[1]), default=1))
@@ -789,4 +880,7 @@ def build_near_field(world, positions, nf, seed, density=0):
         for i, v in enumerate(nb):
             nbr_n[si, i] = len(v)
             nbr[si, i, :len(v)] = v
-    return NearFieldTable(cand, nbr, nbr_n, fixed, n_cand, A, nf.radius, nf.clear_ego, nf.count, density)
+    if new_routes:
+        _append_routes(world, new_routes, n_pts)
+    return NearFieldTable(cand, nbr, nbr_n, fixed, n_cand, A, nf.radius, nf.clear_ego, nf.count, density,
+                          routes=bool(getattr(nf, "routes", False)))
