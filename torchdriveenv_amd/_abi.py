@@ -187,6 +187,16 @@ class TdeEval(C.Structure):
     _fields_ = [("plan", _p), ("round", _p), ("active", _p), ("acc", _p), ("results", _p), ("R", C.c_int32), ("_pad0", C.c_int32)]
 
 
+class TdeReplay(C.Structure):
+    """tde_replay (include/tde_replay.h): the ring of a replay buffer; device addresses"""
+    _fields_ = [("C", C.c_int32), ("B", C.c_int32), ("n_stack", C.c_int32), ("plane", C.c_int32), ("D", C.c_int32), ("frames", _p),
+                ("action", _p), ("reward", _p), ("done", _p), ("age", _p)]
+
+
+TDE_REPLAY_VERSION = 1
+REPLAY_CUT, REPLAY_TAG = 0x80, 0x5250
+REPLAY_MAX_STACK, REPLAY_MAX_PLANE = 8, 4096
+
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7
 RENDER_LEFT_HANDED, RENDER_PLAIN_EGO = 1 << 0, 1 << 1

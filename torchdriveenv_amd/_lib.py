@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("TDE_HIP_LIB") or os.path.join(_PKG, "libtde_hip.so") 
 SYMBOLS = ["tde_abi_version", "tde_last_error", "tde_kernel_override", "tde_kinematics_step", "tde_compute_collision",
            "tde_compute_offroad", "tde_kin_collide_step", "tde_waypoint_reward", "tde_env_reset", "tde_env_step",
            "tde_env_rollout", "tde_render_ego", "tde_render_scene", "tde_env_reset_render", "tde_env_step_render", "tde_state_obs", "tde_ego_infractions", "tde_env_post_step", "tde_first_gaps", "tde_near_field_spawn", "tde_vector_obs", "tde_plan_action", "tde_score_plans", "tde_forecast_agents", "tde_score_plans_forecast", "tde_forecast_scene", "tde_score_plans_scene", "tde_env_reset_to", "tde_eval_advance", "tde_grid_build", "tde_grid_free"]
+# every symbol include/tde_replay.h declares (an additive header with a version of its own: TDE_REPLAY_VERSION)
+REPLAY_SYMBOLS = ["tde_replay_version", "tde_replay_begin", "tde_replay_push", "tde_replay_sample", "tde_replay_pack"]
 
 _lib = None
 
@@ -73,6 +75,19 @@ def load():
     for s in SYMBOLS:
         if s not in ("tde_last_error", "tde_grid_free"):
             getattr(L, s).restype = C.c_int
+    missing = [s for s in REPLAY_SYMBOLS if not hasattr(L, s)]
+    if missing:
+        raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")
+    if L.tde_replay_version() != _abi.TDE_REPLAY_VERSION:
+        raise TdeError(f"replay version mismatch: library {L.tde_replay_version()} vs python {_abi.TDE_REPLAY_VERSION}")
+    rpp, u64 = C.POINTER(_abi.TdeReplay), C.c_uint64
+    L.tde_replay_version.argtypes = []
+    L.tde_replay_begin.argtypes = [rpp, i32, vp, i64, vp, vp]
+    L.tde_replay_push.argtypes = [rpp, i32, vp, vp, vp, vp, i64, vp]
+    L.tde_replay_sample.argtypes = [rpp, i32, i32, i32, vp, u64, u64] + [vp] * 6 + [vp]
+    L.tde_replay_pack.argtypes = [rpp, vp, i64, vp, i64, vp]
+    for s in REPLAY_SYMBOLS:
+        getattr(L, s).restype = C.c_int
     _lib = L
     return L
 

@@ -1266,6 +1266,12 @@ class BatchedWaypointEnv:
             else:
                 self.state.arrays[k].copy_(v)
 
+    def replay_buffer(self, capacity_steps, seed=None):
+        """a replay.ReplayBuffer of `capacity_steps` time slots bound to this env (index draws seeded by `seed`; None: the env's seed)"""
+        from .replay import ReplayBuffer
+
+        return ReplayBuffer(self, capacity_steps, seed=self.seed_value if seed is None else seed)
+
     # ---- SB3 VecEnv-shaped numpy API --------------------------------------------------------------------
     def as_vec_env(self, **kw):
         """the SB3 `VecEnv` over this batch (one shared adapter per env object)"""

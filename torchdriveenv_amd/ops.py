@@ -716,3 +716,77 @@ class FrameStack:
         self.layers.copy_(sd["layers"])
         self.obs.copy_(sd["obs"])
         self.phase = int(sd["phase"]) % self.n_stack
+
+
+# ---- replay buffer (include/tde_replay.h) ---------------------------------------------------------------------------------------
+def _replay_src(rp, src, src_offset, src_stride, dev):
+    """address and stride of the frame source of replay_begin / replay_push: a uint8 (planes mode) or float32 (rows mode) device
+    tensor holding one plane / row per env `src_stride` bytes apart, the first at byte `src_offset`"""
+    dt = torch.uint8 if rp.plane > 0 else torch.float32
+    p = _chk(src, dt, None, "src", dev)
+    row = rp.plane if rp.plane > 0 else 4 * rp.D
+    src_stride = row if src_stride is None else int(src_stride)
+    src_offset = int(src_offset)
+    if src_offset < 0 or src_stride < row or src_offset + (rp.B - 1) * src_stride + row > src.numel() * src.element_size():
+        raise ValueError(f"src holds {src.numel() * src.element_size()} bytes: too few for {rp.B} rows of {row} bytes, {src_stride} apart, from byte {src_offset}")
+    return p + src_offset, src_stride
+
+
+def replay_struct(C_, B, n_stack, plane, D, frames, action, reward, done, age):
+    """_abi.TdeReplay over the caller's ring tensors: frames uint8 [C, B, plane] (planes mode, D = 0) or float32 [C, B, D] (rows mode,
+    plane = 0), action float32 [C, B, 2], reward float32 [C, B], done / age uint8 [C, B], all on one HIP device"""
+    C_, B, n_stack, plane, D = int(C_), int(B), int(n_stack), int(plane), int(D)
+    if (plane > 0) == (D > 0):
+        raise ValueError("exactly one of plane (planes mode) and D (rows mode) must be > 0")
+    dev = frames.device if torch.is_tensor(frames) else None
+    n = C_ * B
+    pf = _chk(frames, torch.uint8 if plane > 0 else torch.float32, n * (plane if plane > 0 else D), "frames", dev)
+    return _abi.TdeReplay(C_, B, n_stack, plane, D, pf, _chk(action, torch.float32, 2 * n, "action", dev),
+                          _chk(reward, torch.float32, n, "reward", dev), _chk(done, torch.uint8, n, "done", dev),
+                          _chk(age, torch.uint8, n, "age", dev))
+
+
+def replay_begin(rp, dev, w, src, src_offset=0, src_stride=None, mask=None):
+    """tde_replay_begin on the current stream: the open slot `w` takes its frame (and age 0) for the envs of `mask` (uint8 [B]; None:
+    all) from `src` (_replay_src); with a mask the slot before `w` is cut for those envs"""
+    dev = torch.device(dev)
+    ps, stride = _replay_src(rp, src, src_offset, src_stride, dev)
+    pm = _chk(mask, torch.uint8, rp.B, "mask", dev, optional=True)
+    _lib.check(_call(dev, _lib.load().tde_replay_begin, C.byref(rp), int(w), ps, stride, pm, _lib.current_stream(dev)), "tde_replay_begin")
+
+
+def replay_push(rp, dev, w, action, reward, done_bits, src, src_offset=0, src_stride=None):
+    """tde_replay_push on the current stream: action float32 [B, 2], reward float32 [B] and done_bits uint8 [B] of the step just taken
+    go to slot `w`, the new frame (from `src`, _replay_src) and its age to slot (w + 1) % C"""
+    dev = torch.device(dev)
+    ps, stride = _replay_src(rp, src, src_offset, src_stride, dev)
+    pa, pr = _chk(action, torch.float32, 2 * rp.B, "action", dev), _chk(reward, torch.float32, rp.B, "reward", dev)
+    pd = _chk(done_bits, torch.uint8, rp.B, "done_bits", dev)
+    _lib.check(_call(dev, _lib.load().tde_replay_push, C.byref(rp), int(w), pa, pr, pd, ps, stride, _lib.current_stream(dev)), "tde_replay_push")
+
+
+def replay_sample(rp, dev, first, count, n, out, idx_in=None, seed=0, draw=0):
+    """tde_replay_sample on the current stream: `n` transitions into the tensors of `out` - "indices" int32 [n, 2], "observations" /
+    "next_observations" uint8 [n, 3 * n_stack, plane] (planes mode) or float32 [n, D] (rows mode), "actions" float32 [n, 2],
+    "rewards" float32 [n], "dones" uint8 [n] - drawn from (seed, draw) or, with idx_in (int32 [n, 2] (slot, env) pairs), as given"""
+    dev = torch.device(dev)
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    dt, per = (torch.uint8, 3 * rp.n_stack * rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    po, pn = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["next_observations"], dt, n * per, "next_observations", dev)
+    pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
+    pa, pr = _chk(out["actions"], torch.float32, 2 * n, "actions", dev), _chk(out["rewards"], torch.float32, n, "rewards", dev)
+    pd = _chk(out["dones"], torch.uint8, n, "dones", dev)
+    pin = _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)
+    _lib.check(_call(dev, _lib.load().tde_replay_sample, C.byref(rp), int(first), int(count), n, pin, int(seed) & (2**64 - 1),
+                     int(draw) & (2**64 - 1), pi, po, pn, pa, pr, pd, _lib.current_stream(dev)), "tde_replay_sample")
+    return out
+
+
+def replay_pack(rp, dev, rgb, planes):
+    """tde_replay_pack on the current stream: colour observations uint8 [B, 3, plane] back to layer planes uint8 [B, plane]"""
+    dev = torch.device(dev)
+    _lib.check(_call(dev, _lib.load().tde_replay_pack, C.byref(rp), _chk(rgb, torch.uint8, rp.B * 3 * rp.plane, "rgb", dev), 3 * rp.plane,
+                     _chk(planes, torch.uint8, rp.B * rp.plane, "planes", dev), rp.plane, _lib.current_stream(dev)), "tde_replay_pack")
+    return planes

@@ -1,0 +1,206 @@
+"""A device-resident replay buffer for the off-policy algorithms the reference trains by default (SAC, TD3: ref
+examples/rl_training.py:166-183) over BatchedWaypointEnv (include/tde_replay.h, csrc/tde_replay.hip).
+
+Birdview observations are kept as ONE layer plane (a byte per pixel) per env and step - 4096 bytes per transition at 64 x 64, against
+the 2 * 3 * frame_stack * 4096 of a store of stacked obs + next_obs - and both stacks are rebuilt through the palette when a batch is
+sampled.  Vector and state observations are kept as float32 rows.
+
+    buf = env.replay_buffer(capacity_steps=128)
+    obs = env.reset();            buf.begin()
+    obs, *_ = env.step(actions);  buf.push(actions)            # every step
+    env.reset(mask=m);            buf.begin(mask=m)            # a reset of the caller's own
+    batch = buf.sample(256)                                    # observations, actions, next_observations, dones, rewards
+"""
+from collections import namedtuple
+
+import torch
+
+from . import _abi, ops
+
+
+class ReplaySamples(namedtuple("ReplaySamples", ["observations", "actions", "next_observations", "dones", "rewards", "indices"])):
+    """SB3's ReplayBufferSamples fields, all device tensors: observations / next_observations as the env returns them (uint8
+    [n, 3 * frame_stack, H, W] or float32 [n, D]), actions float32 [n, 2], rewards float32 [n], dones uint8 [n] (tde_state.done_bits of
+    the step | REPLAY_CUT), indices int32 [n, 2] (slot, env)."""
+    __slots__ = ()
+
+    @property
+    def terminal(self):
+        """bool [n]: the transition has no next observation (terminated, truncated, or cut by a reset of the caller's)"""
+        return (self.dones & (3 | _abi.REPLAY_CUT)) != 0
+
+
+class ReplayBuffer:
+    """A ring of `capacity_steps` time slots, one entry per env and slot, bound to a BatchedWaypointEnv (auto_reset=True, with_info=True).
+
+    Call order: begin() after env.reset(), push(actions) after every env.step(actions), begin(mask=m) after env.reset(mask=m).  The
+    buffer reads the observation the env RETURNED (for a near_field env that is the one taken after its spawner ran), so it must be
+    called after the env call it records and before the next one.
+
+    What a sample is: `observations` is the observation the env showed at the drawn step, byte for byte; `next_observations` is the
+    one it showed at the next step - or ZEROS where the transition ended its episode (dones & 3) or was cut by the caller's reset
+    (dones & REPLAY_CUT): a finished env is re-spawned inside the step kernel, the terminal frame is never rendered, so such a
+    transition has no next observation and the learner masks its bootstrap with `dones` / `.terminal`.  (SB3's
+    handle_timeout_termination, which bootstraps from the terminal observation of a truncated episode, is therefore not offered.)
+
+    One of the capacity_steps slots is always open (it holds the newest frame, whose step has not been taken), so the buffer holds at
+    most capacity_steps - 1 transitions per env; sample() draws from those whose whole frame stack is still in the ring (it needs
+    more than frame_stack - 1 stored steps).  The tensors a sample returns are reused by the next sample of the same size."""
+
+    def __init__(self, env, capacity_steps, seed=0):
+        C_ = int(capacity_steps)
+        if not env.auto_reset:
+            raise ValueError("ReplayBuffer needs an env with auto_reset=True: it records the frame of the re-spawned episode as the successor of a finished one")
+        if env.state["done_bits"] is None:
+            raise ValueError("ReplayBuffer needs an env with with_info=True: it reads the step's done_bits")
+        self.env, self.B, self.C, self.seed = env, env.num_envs, C_, int(seed)
+        self.dev = env.torch_device
+        self.planes = env.obs_mode == "birdview"
+        self.n_stack = env.frame_stack if self.planes else 1
+        if C_ < self.n_stack + 1 or C_ < 2:
+            raise ValueError(f"capacity_steps must be >= frame_stack + 1 = {max(2, self.n_stack + 1)} (a stack and its successor), got {C_}")
+        if self.planes:
+            self.H = self.W = env._res
+            self.plane, self.D = self.H * self.W, 0
+            if self.plane % 16 != 0:
+                raise ValueError(f"H * W = {self.plane} must be a multiple of 16 (the planes move as 16-byte words)")
+            if self.plane > _abi.REPLAY_MAX_PLANE:
+                raise ValueError(f"H * W = {self.plane} exceeds {_abi.REPLAY_MAX_PLANE}")
+            self.frames = torch.full((C_, self.B, self.plane), _abi.LAYER_BLANK, dtype=torch.uint8, device=self.dev)
+            # an env without a frame stack renders colours only: its observation goes back to a layer plane through here
+            self._packed = torch.empty((self.B, self.plane), dtype=torch.uint8, device=self.dev) if self.n_stack == 1 else None
+        else:
+            self.plane, self.D = 0, int(env.observation_space.shape[0])
+            self.frames = torch.zeros((C_, self.B, self.D), dtype=torch.float32, device=self.dev)
+        self.action = torch.zeros((C_, self.B, 2), dtype=torch.float32, device=self.dev)
+        self.reward = torch.zeros((C_, self.B), dtype=torch.float32, device=self.dev)
+        self.done = torch.zeros((C_, self.B), dtype=torch.uint8, device=self.dev)
+        self.age = torch.zeros((C_, self.B), dtype=torch.uint8, device=self.dev)
+        self.struct = ops.replay_struct(C_, self.B, self.n_stack, self.plane, self.D, self.frames, self.action, self.reward, self.done, self.age)
+        self.first = self.w = self.count = self.draws = 0
+        self._begun = False
+        self._out = {}
+
+    # ---- bookkeeping --------------------------------------------------------------------------------------------------------
+    def __len__(self):
+        """stored transitions: valid slots x envs"""
+        return self.count * self.B
+
+    @property
+    def bytes_per_transition(self):
+        """bytes the ring holds per stored transition"""
+        return (self.plane if self.planes else 4 * self.D) + 8 + 4 + 1 + 1
+
+    def _source(self):
+        """(tensor, byte offset, byte stride) of the newest frame of every env's current observation"""
+        env = self.env
+        if not self.planes:
+            src = env._vobs if env.obs_mode == "vector" else env.state["obs"]
+            return src, 0, 4 * self.D
+        if self.n_stack == 1:
+            if env._obs is None:
+                raise ValueError("the env has no observation yet: call env.reset() first")
+            return ops.replay_pack(self.struct, self.dev, env._obs, self._packed), 0, self.plane
+        st = env._stack
+        if st is None:
+            raise ValueError("the env has no observation yet: call env.reset() first")
+        return st.layers, ((st.phase - 1) % self.n_stack) * self.plane, self.n_stack * self.plane
+
+    def begin(self, mask=None):
+        """after env.reset() (mask None) or env.reset(mask=m): the open slot takes the re-spawned envs' first frame with age 0; on a
+        buffer that already runs, the envs' last stored step is cut (REPLAY_CUT: its successor is not its next observation)"""
+        if mask is not None:
+            mask = (torch.as_tensor(mask, device=self.dev) != 0).to(torch.uint8).contiguous()
+            if mask.numel() != self.B:
+                raise ValueError(f"mask must have {self.B} elements")
+        elif self._begun:
+            mask = torch.ones(self.B, dtype=torch.uint8, device=self.dev)
+        src, off, stride = self._source()
+        ops.replay_begin(self.struct, self.dev, self.w, src, off, stride, mask)
+        self._begun = True
+
+    def push(self, actions):
+        """after env.step(actions): the step's action, reward and done bits complete the open slot; the observation it returned opens
+        the next one"""
+        if not self._begun:
+            raise ValueError("push() before begin(): call begin() after env.reset()")
+        a = actions
+        if not (torch.is_tensor(a) and a.dtype is torch.float32 and a.device == self.dev and a.dim() == 2 and a.shape[0] == self.B
+                and a.shape[1] == 2 and a.is_contiguous()):
+            a = torch.as_tensor(actions, dtype=torch.float32, device=self.dev).reshape(self.B, 2).contiguous()
+        st = self.env.state
+        src, off, stride = self._source()
+        ops.replay_push(self.struct, self.dev, self.w, a, st["reward"], st["done_bits"], src, off, stride)
+        self.w = (self.w + 1) % self.C
+        if self.w == self.first:
+            self.first = (self.first + 1) % self.C           # the ring is full: the oldest step's frame was just overwritten
+        else:
+            self.count += 1
+
+    def valid_pairs(self):
+        """int32 [m, 2] device tensor of every stored (slot, env) whose whole frame stack is still in the ring (what sample(idx=) may be
+        given): slot s, `off` slots behind `first`, of env e is one when min(age[s][e], n_stack - 1) <= off"""
+        off = torch.arange(self.count, device=self.dev)
+        slots = (self.first + off) % self.C
+        ok = torch.clamp(self.age[slots].to(torch.int64), max=self.n_stack - 1) <= off[:, None]
+        s, e = torch.nonzero(ok, as_tuple=True)
+        return torch.stack([slots[s], e], 1).to(torch.int32).contiguous()
+
+    def _buffers(self, n):
+        out = self._out.get(n)
+        if out is None:
+            if self.planes:
+                shape, dt = (n, 3 * self.n_stack, self.H, self.W), torch.uint8
+            else:
+                shape, dt = (n, self.D), torch.float32
+            out = self._out[n] = {"observations": torch.empty(shape, dtype=dt, device=self.dev),
+                                  "next_observations": torch.empty(shape, dtype=dt, device=self.dev),
+                                  "actions": torch.empty((n, 2), dtype=torch.float32, device=self.dev),
+                                  "rewards": torch.empty(n, dtype=torch.float32, device=self.dev),
+                                  "dones": torch.empty(n, dtype=torch.uint8, device=self.dev),
+                                  "indices": torch.empty((n, 2), dtype=torch.int32, device=self.dev)}
+        return out
+
+    def sample(self, n, idx=None, check=True):
+        """`n` transitions -> ReplaySamples, drawn on the device from (seed, the buffer's draw counter) - or, with idx (int [n, 2]
+        (slot, env) pairs; n may be None), those.  check (idx only): refuse pairs that are not valid_pairs() - one host
+        synchronisation; without it such a pair gathers zeros or blank older frames."""
+        if idx is not None:
+            idx = torch.as_tensor(idx, device=self.dev).to(torch.int32).reshape(-1, 2).contiguous()
+            if n is None:
+                n = idx.shape[0]
+            if idx.shape[0] != int(n):
+                raise ValueError(f"idx must hold {n} (slot, env) pairs")
+        if n is None or int(n) < 1:
+            raise ValueError("n must be >= 1")
+        n = int(n)
+        if self.count < 1:
+            raise ValueError("the buffer holds no transition yet")
+        if idx is None and self.count <= self.n_stack - 1:
+            raise ValueError(f"sample() draws steps whose whole frame stack is in the ring: it needs more than {self.n_stack - 1} stored steps, the buffer holds {self.count}")
+        if idx is not None and check:
+            s, e = idx[:, 0].long(), idx[:, 1].long()
+            ok = (s >= 0) & (s < self.C) & (e >= 0) & (e < self.B)
+            off = (s.clamp(0, self.C - 1) - self.first) % self.C
+            ok &= off < self.count
+            ok &= torch.clamp(self.age[s.clamp(0, self.C - 1), e.clamp(0, self.B - 1)].long(), max=self.n_stack - 1) <= off
+            if not bool(ok.all()):
+                raise ValueError("idx holds pairs that are not stored transitions with their whole frame stack in the ring (valid_pairs())")
+        out = ops.replay_sample(self.struct, self.dev, self.first, self.count, n, self._buffers(n), idx, self.seed, self.draws)
+        if idx is None:
+            self.draws += 1
+        return ReplaySamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"], out["indices"])
+
+    def state_dict(self):
+        return {"frames": self.frames.clone(), "action": self.action.clone(), "reward": self.reward.clone(), "done": self.done.clone(),
+                "age": self.age.clone(), "first": self.first, "w": self.w, "count": self.count, "draws": self.draws, "seed": self.seed,
+                "begun": self._begun}
+
+    def load_state_dict(self, sd):
+        for k in ("frames", "action", "reward", "done", "age"):
+            if tuple(sd[k].shape) != tuple(getattr(self, k).shape):
+                raise ValueError(f"{k} has shape {tuple(sd[k].shape)}, this buffer's is {tuple(getattr(self, k).shape)}")
+        for k in ("frames", "action", "reward", "done", "age"):
+            getattr(self, k).copy_(sd[k])
+        self.first, self.w, self.count, self.draws = int(sd["first"]), int(sd["w"]), int(sd["count"]), int(sd["draws"])
+        self.seed, self._begun = int(sd.get("seed", self.seed)), bool(sd.get("begun", True))
