@@ -196,6 +196,7 @@ class TdeReplay(C.Structure):
 TDE_REPLAY_VERSION = 1
 REPLAY_CUT, REPLAY_TAG = 0x80, 0x5250
 REPLAY_MAX_STACK, REPLAY_MAX_PLANE = 8, 4096
+TDE_ONPOLICY_VERSION = 1         # include/tde_onpolicy.h
 
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7

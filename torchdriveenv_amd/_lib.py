@@ -13,6 +13,8 @@ SYMBOLS = ["tde_abi_version", "tde_last_error", "tde_kernel_override", "tde_kine
            "tde_env_rollout", "tde_render_ego", "tde_render_scene", "tde_env_reset_render", "tde_env_step_render", "tde_state_obs", "tde_ego_infractions", "tde_env_post_step", "tde_first_gaps", "tde_near_field_spawn", "tde_vector_obs", "tde_plan_action", "tde_score_plans", "tde_forecast_agents", "tde_score_plans_forecast", "tde_forecast_scene", "tde_score_plans_scene", "tde_env_reset_to", "tde_eval_advance", "tde_grid_build", "tde_grid_free"]
 # every symbol include/tde_replay.h declares (an additive header with a version of its own: TDE_REPLAY_VERSION)
 REPLAY_SYMBOLS = ["tde_replay_version", "tde_replay_begin", "tde_replay_push", "tde_replay_sample", "tde_replay_pack"]
+# every symbol include/tde_onpolicy.h declares (additive over the replay header: TDE_ONPOLICY_VERSION)
+ONPOLICY_SYMBOLS = ["tde_onpolicy_version", "tde_gae", "tde_onpolicy_gather"]
 
 _lib = None
 
@@ -87,6 +89,16 @@ def load():
     L.tde_replay_sample.argtypes = [rpp, i32, i32, i32, vp, u64, u64] + [vp] * 6 + [vp]
     L.tde_replay_pack.argtypes = [rpp, vp, i64, vp, i64, vp]
     for s in REPLAY_SYMBOLS:
+        getattr(L, s).restype = C.c_int
+    missing = [s for s in ONPOLICY_SYMBOLS if not hasattr(L, s)]
+    if missing:
+        raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")
+    if L.tde_onpolicy_version() != _abi.TDE_ONPOLICY_VERSION:
+        raise TdeError(f"on-policy version mismatch: library {L.tde_onpolicy_version()} vs python {_abi.TDE_ONPOLICY_VERSION}")
+    L.tde_onpolicy_version.argtypes = []
+    L.tde_gae.argtypes = [rpp, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp]
+    L.tde_onpolicy_gather.argtypes = [rpp, i32, i32, i32, i32] + [vp] * 5 + [vp] * 6 + [vp]
+    for s in ONPOLICY_SYMBOLS:
         getattr(L, s).restype = C.c_int
     _lib = L
     return L

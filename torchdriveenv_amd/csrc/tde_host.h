@@ -10,6 +10,7 @@
 #include "../../include/tde_hip.h"
 
 namespace tde { struct StepArgs; }
+struct tde_replay;
 
 namespace tde_host {
 
@@ -123,6 +124,9 @@ int launch_forecast_scene(const tde_config *cfg, const tde_world *world, const t
 // tde_plan_scene.hip: score_plans_scene_kernel<A, LIGHTS> and plan_scene_winner_kernel (tde_score_plans_scene; arguments checked by the caller)
 int launch_score_plans_scene(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const tde_plan_set *ps,
                              const uint8_t *only, float *cost, int32_t *fail_step, float *action, tde_plan_diag *diag, void *stream);
+// tde_replay.hip: the check of a tde_replay struct that every replay entry point starts with, for the units that read the ring
+// (tde_onpolicy.hip); the message names `fn`
+int check_replay_struct(const char *fn, const tde_replay *rp);
 
 }  // namespace tde_host
 

@@ -278,6 +278,12 @@ unsigned env_blocks(int B) { return (unsigned)((B + tde::kReplayWaves - 1) / tde
 
 }  // namespace
 
+int tde_host::check_replay_struct(const char *fn, const tde_replay *rp)
+{
+    tde::ReplayArgs a;
+    return check_replay(fn, rp, a);
+}
+
 int tde_replay_version(void) { return TDE_REPLAY_VERSION; }
 
 int tde_replay_begin(const tde_replay *rp, int32_t w, const uint8_t *src, int64_t src_stride, const uint8_t *mask, void *stream)

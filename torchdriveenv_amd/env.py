@@ -1272,6 +1272,12 @@ class BatchedWaypointEnv:
 
         return ReplayBuffer(self, capacity_steps, seed=self.seed_value if seed is None else seed)
 
+    def rollout_buffer(self, n_steps, gamma=0.99, gae_lambda=0.95, seed=None):
+        """an onpolicy.RolloutBuffer of `n_steps` steps bound to this env (minibatch permutations seeded by `seed`; None: the env's seed)"""
+        from .onpolicy import RolloutBuffer
+
+        return RolloutBuffer(self, n_steps, gamma=gamma, gae_lambda=gae_lambda, seed=seed)
+
     # ---- SB3 VecEnv-shaped numpy API --------------------------------------------------------------------
     def as_vec_env(self, **kw):
         """the SB3 `VecEnv` over this batch (one shared adapter per env object)"""

@@ -790,3 +790,42 @@ def replay_pack(rp, dev, rgb, planes):
     _lib.check(_call(dev, _lib.load().tde_replay_pack, C.byref(rp), _chk(rgb, torch.uint8, rp.B * 3 * rp.plane, "rgb", dev), 3 * rp.plane,
                      _chk(planes, torch.uint8, rp.B * rp.plane, "planes", dev), rp.plane, _lib.current_stream(dev)), "tde_replay_pack")
     return planes
+
+
+# ---- on-policy view of the ring (include/tde_onpolicy.h) ------------------------------------------------------------------------------
+def gae(rp, dev, first, count, T, values, last_values, gamma, lam, advantages, returns):
+    """tde_gae on the current stream: generalised advantage estimation over the newest `T` stored steps of the ring `rp` - values /
+    advantages / returns float32 [T, B] (the last two written), last_values float32 [B]"""
+    dev = torch.device(dev)
+    T = int(T)
+    if T < 1:
+        raise ValueError("T must be >= 1")
+    n = T * rp.B
+    pv, pl = _chk(values, torch.float32, n, "values", dev), _chk(last_values, torch.float32, rp.B, "last_values", dev)
+    pa, pr = _chk(advantages, torch.float32, n, "advantages", dev), _chk(returns, torch.float32, n, "returns", dev)
+    _lib.check(_call(dev, _lib.load().tde_gae, C.byref(rp), int(first), int(count), T, pv, pl, float(gamma), float(lam), pa, pr,
+                     _lib.current_stream(dev)), "tde_gae")
+    return advantages, returns
+
+
+def onpolicy_gather(rp, dev, first, count, T, idx, values, log_probs, advantages, returns, out):
+    """tde_onpolicy_gather on the current stream: the samples idx (int32 [n], t * B + e over the newest `T` stored steps of the ring
+    `rp`) into the tensors of `out` - "observations" uint8 [n, 3 * n_stack, plane] (planes mode) or float32 [n, D] (rows mode),
+    "actions" float32 [n, 2], "old_values" / "old_log_prob" / "advantages" / "returns" float32 [n], read from the float32 [T, B]
+    values / log_probs / advantages / returns; an index outside [0, T * B) gathers zeros"""
+    dev = torch.device(dev)
+    T = int(T)
+    if T < 1:
+        raise ValueError("T must be >= 1")
+    pi = _chk(idx, torch.int32, None, "idx", dev)
+    n = idx.numel()
+    if n < 1:
+        raise ValueError("idx must hold at least one index")
+    src = [_chk(t, torch.float32, T * rp.B, nm, dev) for t, nm in ((values, "values"), (log_probs, "log_probs"), (advantages, "advantages"),
+                                                                  (returns, "returns"))]
+    dt, per = (torch.uint8, 3 * rp.n_stack * rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    po, pa = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["actions"], torch.float32, 2 * n, "actions", dev)
+    dst = [_chk(out[k], torch.float32, n, k, dev) for k in ("old_values", "old_log_prob", "advantages", "returns")]
+    _lib.check(_call(dev, _lib.load().tde_onpolicy_gather, C.byref(rp), int(first), int(count), T, n, pi, *src, po, pa, *dst,
+                     _lib.current_stream(dev)), "tde_onpolicy_gather")
+    return out
