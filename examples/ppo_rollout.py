@@ -22,7 +22,8 @@ def main():
     n_steps = int(sys.argv[2]) if len(sys.argv) > 2 else 32
     cfg = EnvConfig(seed=0, distance_cutoff=0.25, frame_stack=3)
     world = synthetic_world(n_scn=64, A=16, seed=0, n_maps=4)
-    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, frame_stack=3)
+    # terminal_obs=True: a truncated episode (the success case: max_environment_steps reached) can bootstrap from its terminal observation
+    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, frame_stack=3, terminal_obs=True)
     dev = env.torch_device
     gen = torch.Generator(device=dev).manual_seed(0)
     low, high = (torch.tensor(v, device=dev) for v in (env.action_space.low, env.action_space.high))
@@ -39,6 +40,9 @@ def main():
         actions, values, log_probs = policy(obs)
         obs, *_ = env.step(actions)
         buf.push(actions, values, log_probs)
+        envs, term_obs = buf.terminal_observations()   # the envs this step truncated, and what they showed before the re-spawn
+        if len(envs):
+            buf.bootstrap(envs, policy(term_obs)[1][:len(envs)])       # reward += gamma * V(terminal observation), as SB3 does
     buf.finish(policy(obs)[1])                         # the critic's value of the observation after the last step
     for epoch in range(2):
         n = batches = 0

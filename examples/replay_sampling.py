@@ -22,8 +22,9 @@ def main():
     capacity = int(sys.argv[3]) if len(sys.argv) > 3 else 64
     cfg = EnvConfig(seed=0, distance_cutoff=0.25, frame_stack=3)
     world = synthetic_world(n_scn=64, A=16, seed=0, n_maps=4)
-    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, frame_stack=3)
-    buf = env.replay_buffer(capacity_steps=capacity)
+    # terminal_obs=True: the env observes a finished episode before it re-spawns it, and the buffer pools that frame
+    env = BatchedWaypointEnv(cfg, world, num_envs=num_envs, frame_stack=3, terminal_obs=True)
+    buf = env.replay_buffer(capacity_steps=capacity)   # terminal_per_step=: pool rows per step (default num_envs // 8)
     env.reset()
     buf.begin()
     for _ in range(steps):
@@ -36,6 +37,8 @@ def main():
         t = getattr(batch, name)
         print(f"{name:18s} {str(t.dtype):14s} {tuple(t.shape)}")
     print(f"{len(buf)} transitions held ({buf.count} steps x {num_envs} envs), {int(batch.terminal.sum())} of the 256 drawn ended their episode")
+    # where .bootstrap is set, next_observations is what the learner bootstraps from - for a truncated episode, its terminal observation
+    print(f"{int(batch.bootstrap.sum())} of them bootstrap from next_observations ({int((batch.bootstrap & batch.terminal).sum())} truncated, from the terminal observation)")
     stacked = 2 * batch.observations[0].numel() * batch.observations.element_size()
     print(f"bytes held per transition: {buf.bytes_per_transition} (a store of stacked obs + next_obs: {stacked})")
 

@@ -198,6 +198,15 @@ REPLAY_CUT, REPLAY_TAG = 0x80, 0x5250
 REPLAY_MAX_STACK, REPLAY_MAX_PLANE = 8, 4096
 TDE_ONPOLICY_VERSION = 1         # include/tde_onpolicy.h
 
+
+class TdeTerminal(C.Structure):
+    """tde_terminal (include/tde_terminal.h): the pool of terminal frames beside a replay ring; device addresses"""
+    _fields_ = [("M", C.c_int32), ("pool", _p), ("ref", _p)]
+
+
+TDE_TERMINAL_VERSION = 1         # include/tde_terminal.h
+TERMINAL_HAS = 0x40              # in the done byte a terminal sample returns: next_observations is the terminal observation
+
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7
 RENDER_LEFT_HANDED, RENDER_PLAIN_EGO = 1 << 0, 1 << 1

@@ -15,6 +15,8 @@ SYMBOLS = ["tde_abi_version", "tde_last_error", "tde_kernel_override", "tde_kine
 REPLAY_SYMBOLS = ["tde_replay_version", "tde_replay_begin", "tde_replay_push", "tde_replay_sample", "tde_replay_pack"]
 # every symbol include/tde_onpolicy.h declares (additive over the replay header: TDE_ONPOLICY_VERSION)
 ONPOLICY_SYMBOLS = ["tde_onpolicy_version", "tde_gae", "tde_onpolicy_gather"]
+# every symbol include/tde_terminal.h declares (additive over the replay header: TDE_TERMINAL_VERSION)
+TERMINAL_SYMBOLS = ["tde_terminal_version", "tde_terminal_stash", "tde_terminal_push", "tde_terminal_sample"]
 
 _lib = None
 
@@ -99,6 +101,18 @@ def load():
     L.tde_gae.argtypes = [rpp, i32, i32, i32, vp, vp, f32, f32, vp, vp, vp]
     L.tde_onpolicy_gather.argtypes = [rpp, i32, i32, i32, i32] + [vp] * 5 + [vp] * 6 + [vp]
     for s in ONPOLICY_SYMBOLS:
+        getattr(L, s).restype = C.c_int
+    missing = [s for s in TERMINAL_SYMBOLS if not hasattr(L, s)]
+    if missing:
+        raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")
+    if L.tde_terminal_version() != _abi.TDE_TERMINAL_VERSION:
+        raise TdeError(f"terminal version mismatch: library {L.tde_terminal_version()} vs python {_abi.TDE_TERMINAL_VERSION}")
+    tmp = C.POINTER(_abi.TdeTerminal)
+    L.tde_terminal_version.argtypes = []
+    L.tde_terminal_stash.argtypes = [i32, i32, vp, vp, i64, vp, vp]
+    L.tde_terminal_push.argtypes = [rpp, tmp, i32, vp, vp, i64, vp]
+    L.tde_terminal_sample.argtypes = [rpp, tmp, i32, i32, i32, vp, u64, u64] + [vp] * 6 + [vp]
+    for s in TERMINAL_SYMBOLS:
         getattr(L, s).restype = C.c_int
     _lib = L
     return L

@@ -11,6 +11,7 @@
 
 namespace tde { struct StepArgs; }
 struct tde_replay;
+struct tde_terminal;
 
 namespace tde_host {
 
@@ -127,6 +128,9 @@ int launch_score_plans_scene(const tde_config *cfg, const tde_world *world, cons
 // tde_replay.hip: the check of a tde_replay struct that every replay entry point starts with, for the units that read the ring
 // (tde_onpolicy.hip); the message names `fn`
 int check_replay_struct(const char *fn, const tde_replay *rp);
+// tde_terminal.hip: the ring (check_replay_struct) and the terminal pool beside it - M in [1, B], pool and ref present and aligned -
+// that every entry point of tde_terminal.h that takes a pool starts with; the message names `fn`
+int check_terminal_struct(const char *fn, const tde_replay *rp, const tde_terminal *tm);
 
 }  // namespace tde_host
 

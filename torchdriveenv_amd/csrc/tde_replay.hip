@@ -114,6 +114,9 @@ __global__ __launch_bounds__(64 * kReplayWaves) void replay_pack_kernel(int B, i
 }
 
 // transition i of a sample (wave-uniform): the pair drawn or given, and whether it is a stored transition
+// (tde_terminal.hip restates replay_pick, replay_scalars and the planes gather - terminal_pick, terminal_scalars,
+//  terminal_gather_planes_kernel - because tde_terminal_sample must draw the pairs tde_replay_sample draws: a change to the draw, the
+//  validity rule or the blanking rule here is made there too; tests/test_gpu_terminal.py holds the two draws to each other)
 struct ReplayPick {
     int slot, env, off;                 // off: slots between `first` and `slot`
     bool ok;
@@ -349,6 +352,7 @@ int tde_replay_pack(const tde_replay *rp, const uint8_t *rgb, int64_t rgb_stride
     tde::ReplayArgs a;
     int rc = check_replay(fn, rp, a);
     if (rc) return rc;
+    // (the kernel takes B and plane of the struct and nothing else: ops.replay_pack_struct builds a struct for this call alone)
     if (rp->plane <= 0) return bad_in(fn, "planes mode only");
     if (!rgb || !planes) return bad_in(fn, "NULL argument");
     if (rgb_stride < 3 * (int64_t)rp->plane || planes_stride < rp->plane) return bad_in(fn, "a stride is smaller than what it strides over");

@@ -626,7 +626,7 @@ class BatchedWaypointEnv:
     def __init__(self, cfg: EnvConfig, data, num_envs, agents_per_env=16, device=None, obs_mode="birdview",
                  frame_stack=1, auto_reset=True, with_info=True, background=None, env_base=0, binding="ext",
                  info_magnitudes=True, road_meshes=None, near_range=None, traffic_lights=None, start_headings=None, light_radius=150.0,
-                 heading_samples=16, near_field=None, vector_obs=None, planner=None, plan_refine=None, plan_react=None):
+                 heading_samples=16, near_field=None, vector_obs=None, planner=None, plan_refine=None, plan_react=None, terminal_obs=False):
         """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp), "ctypes" = through
         the ctypes binding of the same C-ABI (ops.py); both call the very same entry points of libtde_hip.so.
         info_magnitudes (default): info["offroad"] / info["collision"] hold the MAGNITUDES the reference reports there (ref
@@ -653,8 +653,23 @@ class BatchedWaypointEnv:
         refines the winner knot by knot through tde_score_plans.  None (default): plan_actions() is tde_plan_action as it was.
         plan_react: a config.PlanReact (or a dict of its fields): plan_actions() then judges every lattice candidate in a scene that
         reacts to it (tde_score_plans_scene).  Not with plan_refine, and only with Planner(predict="constant").  None (default):
-        nothing changes."""
+        nothing changes.
+        terminal_obs: keep the observation each finished env showed BEFORE it was re-spawned (SB3's info["terminal_observation"], on
+        the device).  step() then runs the step without the in-kernel re-spawn, observes, copies the newest frame of the finished envs
+        into `terminal_frames` (tde_terminal_stash: uint8 [B, H * W] layer planes, or the float32 [B, D] rows of obs_mode "vector" /
+        "state"; the other envs' entries keep what they held) and re-spawns them with reset(mask=done).  Everything step() returns and
+        the whole state equal, bit for bit, those of the same env without the option; a step costs a few small launches more.  Needs
+        auto_reset=True and with_info=True; rollout() raises (it re-spawns inside one launch); not offered with near_field (the match
+        with the in-kernel re-spawn has not been established there).  replay_buffer() / rollout_buffer() of such an env store the
+        frames (include/tde_terminal.h).  False (default): nothing changes."""
         validate(cfg)
+        self.terminal_obs = bool(terminal_obs)
+        if self.terminal_obs and not (auto_reset and with_info):
+            raise ValueError("terminal_obs=True needs auto_reset=True and with_info=True: it keeps the frame of the envs the step "
+                             "finished (done_bits) before it re-spawns them")
+        if self.terminal_obs and near_field is not None:
+            raise ValueError("terminal_obs=True with near_field: the two-launch step (step, observe, re-spawn by reset(mask)) has not been "
+                             "shown to match the in-kernel re-spawn followed by the near-field spawner bit for bit, so it is not offered")
         self.planner = check_planner(planner if planner is not None else Planner())
         self.plan_refine = check_plan_refine(plan_refine, self.planner) if plan_refine is not None else None
         self.plan_react = check_plan_react(plan_react, self.planner, self.plan_refine) if plan_react is not None else None
@@ -759,6 +774,18 @@ class BatchedWaypointEnv:
             self._h = _ext.env_handle(self.tde_cfg, self.dworld, self.state)
             if self.dnf is not None:
                 self._hnf = _ext.near_field_of(self.dnf)
+        # terminal_obs: the newest frame each env showed when it last finished (tde_terminal_stash), and what step() needs around it
+        self.terminal_frames = self._term_mask = self._term_packed = self._term_pack_struct = None
+        if self.terminal_obs:
+            if obs_mode == "birdview":
+                if (self._res * self._res) % 16 != 0:
+                    raise ValueError(f"terminal_obs=True: H * W = {self._res * self._res} must be a multiple of 16 (the planes move as 16-byte words)")
+                self.terminal_frames = torch.full((self.num_envs, self._res * self._res), _abi.LAYER_BLANK, dtype=torch.uint8,
+                                                  device=self.torch_device)
+            else:
+                self.terminal_frames = torch.zeros((self.num_envs, self.observation_space.shape[0]), dtype=torch.float32,
+                                                   device=self.torch_device)
+            self._term_mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.torch_device)
         if self.dnf is None:
             # the world's first-step gap cache for this configuration, now - not inside the first step() (which may be under a stream capture)
             ops.first_gaps(self.tde_cfg, self.dworld)
@@ -782,7 +809,8 @@ class BatchedWaypointEnv:
         if mask is not None:
             # 0 / 1 bytes: the rasteriser reads bits 0-1 of a `fresh` byte (tde_render.fresh), so a mask like done_bits with only
             # infraction bits set must not re-spawn an env and leave its older stack frames un-blanked
-            m = (torch.as_tensor(mask, device=self.torch_device) != 0).to(torch.uint8).contiguous()
+            # (step() of a terminal_obs env hands over its own 0 / 1 mask: nothing to convert)
+            m = mask if mask is self._term_mask else (torch.as_tensor(mask, device=self.torch_device) != 0).to(torch.uint8).contiguous()
         scn = None
         if options is not None and options.get("scenario") is not None:
             scn = ops.check_scenario_ids(options["scenario"], self.num_envs, self.world.n_scn).to(self.torch_device)
@@ -847,6 +875,8 @@ class BatchedWaypointEnv:
         if not (torch.is_tensor(a) and a.dtype is torch.float32 and a.device == self.torch_device and a.dim() == 2
                 and a.shape[0] == self.num_envs and a.shape[1] == 2 and a.is_contiguous()):
             a = torch.as_tensor(actions, dtype=torch.float32, device=self.torch_device).reshape(self.num_envs, 2).contiguous()
+        if self.terminal_obs and self.auto_reset:                    # (the VecEnv adapter clears the flag and re-spawns the envs itself)
+            return self._step_terminal(a)
         if self._h is not None:
             self._h.step(a, int(self.tde_cfg.flags))
         else:
@@ -866,6 +896,41 @@ class BatchedWaypointEnv:
                 fresh = st["done_bits"] if st["done_bits"] is not None else (st["terminated"] | st["truncated"])
             obs = self.get_obs(fresh)
         # uint8 0/1 flags seen as bool without a copy; info entries are only computed when they are read
+        term, trunc = self._flag_views()
+        return obs, st["reward"], term, trunc, _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
+
+    def _terminal_source(self, obs):
+        """(tensor, byte offset, byte stride) of the newest frame of the observation `obs` the env just took: the layer plane of the
+        frame-stack ring, the plane tde_replay_pack makes of a colour observation without one, or the float32 row"""
+        if self.obs_mode != "birdview":
+            return obs, 0, 4 * obs.shape[1]
+        plane = self._res * self._res
+        if self._stack is not None:
+            st = self._stack
+            return st.layers, ((st.phase - 1) % self.frame_stack) * plane, self.frame_stack * plane
+        if self._term_packed is None:
+            self._term_packed = torch.empty((self.num_envs, plane), dtype=torch.uint8, device=self.torch_device)
+            self._term_pack_struct = ops.replay_pack_struct(self.num_envs, plane, self._term_packed)
+        return ops.replay_pack(self._term_pack_struct, self.torch_device, obs, self._term_packed), 0, plane
+
+    def _step_terminal(self, a):
+        """step() of a terminal_obs env: the step without the in-kernel re-spawn (the kernel form WaypointVecEnv.step_wait uses) ->
+        the observation, which for a finished env is its terminal one -> tde_terminal_stash of the finished envs' newest frame into
+        terminal_frames -> reset(mask=done): the masked re-spawn and re-render.  Same results as step() without the option."""
+        st = self.state
+        full = int(self.tde_cfg.flags)
+        self.tde_cfg.flags = full & ~_abi.F_AUTORESET
+        try:
+            if self._h is not None:
+                self._h.step(a, int(self.tde_cfg.flags))
+            else:
+                ops.env_step(self.tde_cfg, self.dworld, st, action=a)
+            obs = st["obs"] if self.obs_mode == "state" else self._vector_obs() if self.obs_mode == "vector" else self.get_obs()
+        finally:
+            self.tde_cfg.flags = full
+        src, off, stride = self._terminal_source(obs)
+        ops.terminal_stash(self.torch_device, st["done_bits"], src, off, stride, self.terminal_frames)
+        obs = self.reset(mask=torch.bitwise_or(st["terminated"], st["truncated"], out=self._term_mask))
         term, trunc = self._flag_views()
         return obs, st["reward"], term, trunc, _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
 
@@ -911,6 +976,9 @@ class BatchedWaypointEnv:
         """K open-loop steps from a resident [K,B,2] action tensor -> (reward [K,B], done bits [K,B]).  (The Monitor-style
         episode statistics of the closed-loop API are not maintained across a rollout: they follow from the returned
         arrays.)"""
+        if self.terminal_obs:
+            raise ValueError("rollout() on a terminal_obs env: the rollout kernels re-spawn finished envs inside one launch, where no "
+                             "terminal observation can be taken; step() the envs instead")
         if self._nf_routed:
             raise ValueError("rollout() with routed near-field traffic (NearField(routes=True)): the rollout kernels read routes from the "
                              "spawn records; step() the envs instead")
@@ -1253,6 +1321,8 @@ class BatchedWaypointEnv:
         sd = {k: v.clone() for k, v in self.state.arrays.items() if v is not None}
         if self._stack is not None:
             sd["_frame_stack"] = self._stack.state_dict()
+        if self.terminal_frames is not None:
+            sd["_terminal_frames"] = self.terminal_frames.clone()
         return sd
 
     def load_state_dict(self, sd):
@@ -1263,20 +1333,28 @@ class BatchedWaypointEnv:
                                                  flags=self._rflags, handle=self._h)
                 self._stack.load_state_dict(v)
                 self._obs = self._stack.obs
+            elif k == "_terminal_frames":
+                if self.terminal_frames is None:
+                    raise ValueError("the state holds terminal frames, this env was built without terminal_obs=True")
+                self.terminal_frames.copy_(v)
             else:
                 self.state.arrays[k].copy_(v)
 
-    def replay_buffer(self, capacity_steps, seed=None):
-        """a replay.ReplayBuffer of `capacity_steps` time slots bound to this env (index draws seeded by `seed`; None: the env's seed)"""
+    def replay_buffer(self, capacity_steps, seed=None, terminal_per_step=None):
+        """a replay.ReplayBuffer of `capacity_steps` time slots bound to this env (index draws seeded by `seed`; None: the env's seed).
+        On a terminal_obs env the buffer also keeps up to `terminal_per_step` terminal frames per step (None: max(1, num_envs // 8));
+        that pool costs capacity_steps * terminal_per_step * (H * W, or 4 * D) bytes beside the ring's capacity_steps * num_envs * ... -
+        an eighth more by default - plus 4 * capacity_steps * num_envs bytes of references.  Without the option it must be None."""
         from .replay import ReplayBuffer
 
-        return ReplayBuffer(self, capacity_steps, seed=self.seed_value if seed is None else seed)
+        return ReplayBuffer(self, capacity_steps, seed=self.seed_value if seed is None else seed, terminal_per_step=terminal_per_step)
 
-    def rollout_buffer(self, n_steps, gamma=0.99, gae_lambda=0.95, seed=None):
-        """an onpolicy.RolloutBuffer of `n_steps` steps bound to this env (minibatch permutations seeded by `seed`; None: the env's seed)"""
+    def rollout_buffer(self, n_steps, gamma=0.99, gae_lambda=0.95, seed=None, terminal_per_step=None):
+        """an onpolicy.RolloutBuffer of `n_steps` steps bound to this env (minibatch permutations seeded by `seed`; None: the env's seed;
+        terminal_per_step: as replay_buffer's, for the ring behind it)"""
         from .onpolicy import RolloutBuffer
 
-        return RolloutBuffer(self, n_steps, gamma=gamma, gae_lambda=gae_lambda, seed=seed)
+        return RolloutBuffer(self, n_steps, gamma=gamma, gae_lambda=gae_lambda, seed=seed, terminal_per_step=terminal_per_step)
 
     # ---- SB3 VecEnv-shaped numpy API --------------------------------------------------------------------
     def as_vec_env(self, **kw):

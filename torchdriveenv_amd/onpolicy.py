@@ -16,6 +16,10 @@ Beside it the buffer keeps the critic's values and the policy's log-probabilitie
         for batch in buf.get(4096):                          # observations, actions, old_values, old_log_prob, advantages, returns
             ...
     # the next push starts the next rollout
+
+On an env built with terminal_obs=True, after a push:
+    envs, term_obs = buf.terminal_observations()             # the envs the step truncated, and what they showed before the re-spawn
+    if len(envs): buf.bootstrap(envs, critic(term_obs))      # reward += gamma * V(terminal observation), as SB3 does
 """
 from collections import namedtuple
 
@@ -45,23 +49,27 @@ class RolloutBuffer:
     Advantages: SB3's RolloutBuffer.compute_returns_and_advantage, with "the next step starts an episode" read from the done bits of
     the step itself.  A terminated, truncated or caller-reset (REPLAY_CUT) step does not bootstrap: a finished env is re-spawned inside
     the step kernel, the terminal frame is never rendered, so there is no terminal observation whose value a truncated episode could
-    bootstrap from (SB3's timeout bootstrap is therefore not offered, as in ReplayBuffer).
+    bootstrap from (SB3's timeout bootstrap is therefore not offered, as in ReplayBuffer).  On an env with terminal_obs=True there is
+    one: terminal_observations() returns it for the envs the last pushed step truncated, and bootstrap() adds gamma * V of it to that
+    step's stored reward, as SB3's on_policy_algorithm.py does.  tde_gae is unchanged: the step still cuts the recurrence, and now
+    carries its bootstrap in the reward.
 
     The tensors a batch of get() holds are reused by the next batch of the same size: consume a batch before taking the next."""
 
-    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95, seed=None):
+    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95, seed=None, terminal_per_step=None):
         T = int(n_steps)
         if T < 1:
             raise ValueError(f"n_steps must be >= 1, got {n_steps}")
         n_stack = env.frame_stack if env.obs_mode == "birdview" else 1
         self.seed = int(getattr(env, "seed_value", 0) if seed is None else seed)
-        self.ring = ReplayBuffer(env, capacity_steps=T + n_stack, seed=self.seed)
+        self.ring = ReplayBuffer(env, capacity_steps=T + n_stack, seed=self.seed, terminal_per_step=terminal_per_step)
         self.env, self.B, self.n_steps, self.dev = env, env.num_envs, T, torch.device(env.torch_device)
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
         self.values, self.log_probs, self.advantages, self.returns = (torch.zeros((T, self.B), dtype=torch.float32, device=self.dev)
                                                                       for _ in range(4))
         self.pos, self.finished, self.calls = 0, False, 0
         self._out = {}
+        self._term_out = None                              # terminal_observations(): one output set of terminal_per_step rows
 
     # ---- filling ------------------------------------------------------------------------------------------------------------
     def __len__(self):
@@ -98,6 +106,42 @@ class RolloutBuffer:
         self.values[pos].copy_(values)
         self.log_probs[pos].copy_(log_probs)
         self.pos, self.finished = pos + 1, False
+
+    def terminal_observations(self):
+        """(envs int64 [k], observations [k, ...]): the envs whose last pushed step was truncated and not terminated (and whose frame
+        the ring's pool kept: the first terminal_per_step finished envs of a step), and the stacked terminal observation of each, as
+        tde_terminal_sample returns it for the pairs (last slot, env).  One host synchronisation (the nonzero that counts such envs).
+        The observations are the first k rows of one set of terminal_per_step rows the buffer owns: valid until the next call."""
+        r = self.ring
+        if r.tstruct is None:
+            raise ValueError("terminal_observations() needs an env built with terminal_obs=True")
+        if self.pos < 1 or self.finished:
+            raise ValueError("terminal_observations() follows a push(): the rollout holds no step")
+        slot = (r.w - 1) % r.C
+        envs = torch.nonzero(((r.done[slot] & 3) == 2) & (r.ref[slot] >= 0)).reshape(-1)
+        k = int(envs.numel())                              # (<= terminal_per_step: a slot's refs name distinct pool rows)
+        if self._term_out is None:
+            # one output set for every call, whatever k is: ReplayBuffer._buffers keeps a set per size, and k changes from step to step
+            self._term_out = r._alloc(r.M)
+        out = {key: v[:k] for key, v in self._term_out.items()}
+        if k == 0:
+            return envs, out["next_observations"]
+        idx = torch.stack([torch.full_like(envs, slot), envs], 1).to(torch.int32).contiguous()
+        ops.terminal_sample(r.struct, r.tstruct, self.dev, r.first, r.count, k, out, idx)
+        return envs, out["next_observations"]
+
+    def bootstrap(self, envs, values):
+        """reward[last pushed step, envs] += gamma * values (float32 [k]: the critic's value of terminal_observations()'s
+        observations), once per step.  An env named twice is added to twice."""
+        r = self.ring
+        if self.pos < 1 or self.finished:
+            raise ValueError("bootstrap() follows a push(): the rollout holds no step")
+        envs = torch.as_tensor(envs, device=self.dev).to(torch.int64).reshape(-1)
+        if not (torch.is_tensor(values) and values.dtype is torch.float32 and values.numel() == envs.numel()):
+            raise ValueError(f"values must be a float32 tensor of {envs.numel()} elements (one per env of `envs`)")
+        if values.device != self.dev:
+            raise ValueError(f"values is on {values.device}, expected {self.dev}")
+        r.reward[(r.w - 1) % r.C].index_add_(0, envs, values.reshape(-1) * self.gamma)
 
     def finish(self, last_values):
         """advantages and returns of the rollout (tde_gae); last_values float32 [B]: the critic's value of the observation the last

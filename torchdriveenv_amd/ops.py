@@ -784,6 +784,18 @@ def replay_sample(rp, dev, first, count, n, out, idx_in=None, seed=0, draw=0):
     return out
 
 
+def replay_pack_struct(B, plane, scratch):
+    """an _abi.TdeReplay for replay_pack alone, for a caller that has no ring (an env that keeps terminal frames at frame_stack=1).
+    tde_replay_pack reads B and plane of the struct and nothing else (csrc/tde_replay.hip: replay_pack_kernel takes those two), but it
+    starts, like every replay entry point, with the check of the whole struct: C = 2, n_stack = 1 and arrays that are present and
+    aligned satisfy it, so all five point at `scratch` (a uint8 device tensor of at least 16 bytes, 16-byte aligned), which nothing
+    reads or writes through them.  tests/test_gpu_terminal.py holds the frames packed this way to an env without auto-reset."""
+    p = _chk(scratch, torch.uint8, None, "scratch", scratch.device if torch.is_tensor(scratch) else None)
+    if scratch.numel() < 16 or p % 16 != 0:
+        raise ValueError("scratch must hold at least 16 bytes and be 16-byte aligned")
+    return _abi.TdeReplay(2, int(B), 1, int(plane), 0, p, p, p, p, p)
+
+
 def replay_pack(rp, dev, rgb, planes):
     """tde_replay_pack on the current stream: colour observations uint8 [B, 3, plane] back to layer planes uint8 [B, plane]"""
     dev = torch.device(dev)
@@ -828,4 +840,63 @@ def onpolicy_gather(rp, dev, first, count, T, idx, values, log_probs, advantages
     dst = [_chk(out[k], torch.float32, n, k, dev) for k in ("old_values", "old_log_prob", "advantages", "returns")]
     _lib.check(_call(dev, _lib.load().tde_onpolicy_gather, C.byref(rp), int(first), int(count), T, n, pi, *src, po, pa, *dst,
                      _lib.current_stream(dev)), "tde_onpolicy_gather")
+    return out
+
+
+# ---- terminal observations beside the ring (include/tde_terminal.h) ----------------------------------------------------------------------
+def terminal_struct(rp, M, pool, ref):
+    """_abi.TdeTerminal over the caller's pool tensors beside the ring `rp`: pool uint8 [C, M, plane] (planes mode) or float32 [C, M, D]
+    (rows mode), ref int32 [C, B], on the ring's HIP device"""
+    M = int(M)
+    if M < 1 or M > rp.B:
+        raise ValueError(f"M must be in [1, B = {rp.B}], got {M}")
+    dev = pool.device if torch.is_tensor(pool) else None
+    dt, per = (torch.uint8, rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    return _abi.TdeTerminal(M, _chk(pool, dt, rp.C * M * per, "pool", dev), _chk(ref, torch.int32, rp.C * rp.B, "ref", dev))
+
+
+def terminal_stash(dev, done_bits, src, src_offset, src_stride, dst):
+    """tde_terminal_stash on the current stream: dst[e] = the plane / row of env e in `src` (uint8 or float32 device tensor; rows
+    `src_stride` bytes apart, the first at byte `src_offset`) for the envs with done_bits[e] & 3; dst is [B, plane] uint8 or [B, D]
+    float32 and keeps the other envs' entries"""
+    dev = torch.device(dev)
+    B = int(dst.shape[0])
+    row = dst[0].numel() * dst.element_size()
+    pd = _chk(done_bits, torch.uint8, B, "done_bits", dev)
+    ps = _chk(src, dst.dtype, None, "src", dev)
+    pt = _chk(dst, dst.dtype, None, "dst", dev)
+    src_offset, src_stride = int(src_offset), int(src_stride)
+    if src_offset < 0 or src_stride < row or src_offset + (B - 1) * src_stride + row > src.numel() * src.element_size():
+        raise ValueError(f"src holds {src.numel() * src.element_size()} bytes: too few for {B} rows of {row} bytes, {src_stride} apart, from byte {src_offset}")
+    _lib.check(_call(dev, _lib.load().tde_terminal_stash, B, row, pd, ps + src_offset, src_stride, pt, _lib.current_stream(dev)),
+               "tde_terminal_stash")
+    return dst
+
+
+def terminal_push(rp, tm, dev, w, done_bits, term_src):
+    """tde_terminal_push on the current stream, beside replay_push for slot `w`: the terminal frames term_src ([B, plane] uint8 or
+    [B, D] float32) of the envs with done_bits[e] & 3 go to pool[w] in env order (the first M of them), ref[w] is written whole"""
+    dev = torch.device(dev)
+    dt, per = (torch.uint8, rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    pd = _chk(done_bits, torch.uint8, rp.B, "done_bits", dev)
+    ps = _chk(term_src, dt, rp.B * per, "term_src", dev)
+    _lib.check(_call(dev, _lib.load().tde_terminal_push, C.byref(rp), C.byref(tm), int(w), pd, ps, per * term_src.element_size(),
+                     _lib.current_stream(dev)), "tde_terminal_push")
+
+
+def terminal_sample(rp, tm, dev, first, count, n, out, idx_in=None, seed=0, draw=0):
+    """tde_terminal_sample on the current stream: replay_sample's arguments and outputs; where a transition ended its episode and its
+    terminal frame is in the pool, "next_observations" is the terminal observation and "dones" carries _abi.TERMINAL_HAS"""
+    dev = torch.device(dev)
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    dt, per = (torch.uint8, 3 * rp.n_stack * rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    po, pn = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["next_observations"], dt, n * per, "next_observations", dev)
+    pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
+    pa, pr = _chk(out["actions"], torch.float32, 2 * n, "actions", dev), _chk(out["rewards"], torch.float32, n, "rewards", dev)
+    pd = _chk(out["dones"], torch.uint8, n, "dones", dev)
+    pin = _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)
+    _lib.check(_call(dev, _lib.load().tde_terminal_sample, C.byref(rp), C.byref(tm), int(first), int(count), n, pin,
+                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), pi, po, pn, pa, pr, pd, _lib.current_stream(dev)), "tde_terminal_sample")
     return out

@@ -10,6 +10,10 @@ sampled.  Vector and state observations are kept as float32 rows.
     obs, *_ = env.step(actions);  buf.push(actions)            # every step
     env.reset(mask=m);            buf.begin(mask=m)            # a reset of the caller's own
     batch = buf.sample(256)                                    # observations, actions, next_observations, dones, rewards
+
+On an env built with terminal_obs=True the buffer also keeps the terminal frames (include/tde_terminal.h, csrc/tde_terminal.hip): a
+transition that ended its episode then returns the observation the env showed before it was re-spawned as `next_observations`, and
+`batch.bootstrap` says where the learner should use it.
 """
 from collections import namedtuple
 
@@ -29,6 +33,14 @@ class ReplaySamples(namedtuple("ReplaySamples", ["observations", "actions", "nex
         """bool [n]: the transition has no next observation (terminated, truncated, or cut by a reset of the caller's)"""
         return (self.dones & (3 | _abi.REPLAY_CUT)) != 0
 
+    @property
+    def bootstrap(self):
+        """bool [n]: the learner should bootstrap from next_observations - the transition did not end (not terminal), or it was
+        truncated, not terminated, and its terminal observation is there (dones & TERMINAL_HAS: a terminal_obs env; SB3's
+        handle_timeout_termination)"""
+        d = self.dones
+        return ((d & (3 | _abi.REPLAY_CUT)) == 0) | (((d & 3) == 2) & ((d & _abi.TERMINAL_HAS) != 0))
+
 
 class ReplayBuffer:
     """A ring of `capacity_steps` time slots, one entry per env and slot, bound to a BatchedWaypointEnv (auto_reset=True, with_info=True).
@@ -45,10 +57,24 @@ class ReplayBuffer:
 
     One of the capacity_steps slots is always open (it holds the newest frame, whose step has not been taken), so the buffer holds at
     most capacity_steps - 1 transitions per env; sample() draws from those whose whole frame stack is still in the ring (it needs
-    more than frame_stack - 1 stored steps).  The tensors a sample returns are reused by the next sample of the same size."""
+    more than frame_stack - 1 stored steps).  The tensors a sample returns are reused by the next sample of the same size.
 
-    def __init__(self, env, capacity_steps, seed=0):
+    On an env with terminal_obs=True: push() also files the frames of the envs the step finished (env.terminal_frames) in a pool of
+    `terminal_per_step` rows per slot (tde_terminal_push: in env order; when more envs finish at one step than the pool has rows, the
+    first terminal_per_step keep theirs and the others behave as above), and sample() (tde_terminal_sample) returns, for an ended
+    transition whose frame was kept, the terminal observation as next_observations - its newest frame from the pool, its older frames
+    those of `observations` moved down by one - with TERMINAL_HAS set in dones, also when the transition was cut as well.
+    `.terminal` keeps its meaning; `.bootstrap` is where the learner should use next_observations.  The pool costs capacity_steps *
+    terminal_per_step * (H * W or 4 * D) bytes (default terminal_per_step = max(1, num_envs // 8): an eighth of the ring) plus
+    4 * capacity_steps * num_envs bytes of references."""
+
+    def __init__(self, env, capacity_steps, seed=0, terminal_per_step=None):
         C_ = int(capacity_steps)
+        self.terminal_obs = bool(getattr(env, "terminal_obs", False))
+        if terminal_per_step is not None and not self.terminal_obs:
+            raise ValueError("terminal_per_step needs an env built with terminal_obs=True")
+        if terminal_per_step is not None and not 1 <= int(terminal_per_step) <= env.num_envs:
+            raise ValueError(f"terminal_per_step must be in [1, num_envs = {env.num_envs}], got {terminal_per_step}")
         if not env.auto_reset:
             raise ValueError("ReplayBuffer needs an env with auto_reset=True: it records the frame of the re-spawned episode as the successor of a finished one")
         if env.state["done_bits"] is None:
@@ -77,6 +103,13 @@ class ReplayBuffer:
         self.done = torch.zeros((C_, self.B), dtype=torch.uint8, device=self.dev)
         self.age = torch.zeros((C_, self.B), dtype=torch.uint8, device=self.dev)
         self.struct = ops.replay_struct(C_, self.B, self.n_stack, self.plane, self.D, self.frames, self.action, self.reward, self.done, self.age)
+        self.M, self.pool, self.ref, self.tstruct = 0, None, None, None
+        if self.terminal_obs:
+            self.M = int(terminal_per_step) if terminal_per_step is not None else max(1, self.B // 8)
+            self.pool = (torch.full((C_, self.M, self.plane), _abi.LAYER_BLANK, dtype=torch.uint8, device=self.dev) if self.planes else
+                         torch.zeros((C_, self.M, self.D), dtype=torch.float32, device=self.dev))
+            self.ref = torch.full((C_, self.B), -1, dtype=torch.int32, device=self.dev)
+            self.tstruct = ops.terminal_struct(self.struct, self.M, self.pool, self.ref)
         self.first = self.w = self.count = self.draws = 0
         self._begun = False
         self._out = {}
@@ -131,6 +164,8 @@ class ReplayBuffer:
         st = self.env.state
         src, off, stride = self._source()
         ops.replay_push(self.struct, self.dev, self.w, a, st["reward"], st["done_bits"], src, off, stride)
+        if self.tstruct is not None:
+            ops.terminal_push(self.struct, self.tstruct, self.dev, self.w, st["done_bits"], self.env.terminal_frames)
         self.w = (self.w + 1) % self.C
         if self.w == self.first:
             self.first = (self.first + 1) % self.C           # the ring is full: the oldest step's frame was just overwritten
@@ -146,19 +181,24 @@ class ReplayBuffer:
         s, e = torch.nonzero(ok, as_tuple=True)
         return torch.stack([slots[s], e], 1).to(torch.int32).contiguous()
 
+    def _alloc(self, n):
+        """a fresh set of the output tensors of a sample of `n` transitions"""
+        if self.planes:
+            shape, dt = (n, 3 * self.n_stack, self.H, self.W), torch.uint8
+        else:
+            shape, dt = (n, self.D), torch.float32
+        return {"observations": torch.empty(shape, dtype=dt, device=self.dev),
+                "next_observations": torch.empty(shape, dtype=dt, device=self.dev),
+                "actions": torch.empty((n, 2), dtype=torch.float32, device=self.dev),
+                "rewards": torch.empty(n, dtype=torch.float32, device=self.dev),
+                "dones": torch.empty(n, dtype=torch.uint8, device=self.dev),
+                "indices": torch.empty((n, 2), dtype=torch.int32, device=self.dev)}
+
     def _buffers(self, n):
+        """the output set of sample(n), kept per size (a learner draws a handful of fixed minibatch sizes)"""
         out = self._out.get(n)
         if out is None:
-            if self.planes:
-                shape, dt = (n, 3 * self.n_stack, self.H, self.W), torch.uint8
-            else:
-                shape, dt = (n, self.D), torch.float32
-            out = self._out[n] = {"observations": torch.empty(shape, dtype=dt, device=self.dev),
-                                  "next_observations": torch.empty(shape, dtype=dt, device=self.dev),
-                                  "actions": torch.empty((n, 2), dtype=torch.float32, device=self.dev),
-                                  "rewards": torch.empty(n, dtype=torch.float32, device=self.dev),
-                                  "dones": torch.empty(n, dtype=torch.uint8, device=self.dev),
-                                  "indices": torch.empty((n, 2), dtype=torch.int32, device=self.dev)}
+            out = self._out[n] = self._alloc(n)
         return out
 
     def sample(self, n, idx=None, check=True):
@@ -186,21 +226,31 @@ class ReplayBuffer:
             ok &= torch.clamp(self.age[s.clamp(0, self.C - 1), e.clamp(0, self.B - 1)].long(), max=self.n_stack - 1) <= off
             if not bool(ok.all()):
                 raise ValueError("idx holds pairs that are not stored transitions with their whole frame stack in the ring (valid_pairs())")
-        out = ops.replay_sample(self.struct, self.dev, self.first, self.count, n, self._buffers(n), idx, self.seed, self.draws)
+        if self.tstruct is not None:
+            out = ops.terminal_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, self._buffers(n), idx, self.seed,
+                                      self.draws)
+        else:
+            out = ops.replay_sample(self.struct, self.dev, self.first, self.count, n, self._buffers(n), idx, self.seed, self.draws)
         if idx is None:
             self.draws += 1
         return ReplaySamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"], out["indices"])
 
+    @property
+    def _tensors(self):
+        return ("frames", "action", "reward", "done", "age") + (("pool", "ref") if self.tstruct is not None else ())
+
     def state_dict(self):
-        return {"frames": self.frames.clone(), "action": self.action.clone(), "reward": self.reward.clone(), "done": self.done.clone(),
-                "age": self.age.clone(), "first": self.first, "w": self.w, "count": self.count, "draws": self.draws, "seed": self.seed,
-                "begun": self._begun}
+        return {**{k: getattr(self, k).clone() for k in self._tensors}, "first": self.first, "w": self.w, "count": self.count,
+                "draws": self.draws, "seed": self.seed, "begun": self._begun}
 
     def load_state_dict(self, sd):
-        for k in ("frames", "action", "reward", "done", "age"):
+        if ("pool" in sd) != (self.tstruct is not None):
+            raise ValueError("the state is of a buffer " + ("with" if "pool" in sd else "without") + " terminal frames, this buffer is "
+                             + ("with" if self.tstruct is not None else "without") + " (terminal_obs=True of the env)")
+        for k in self._tensors:
             if tuple(sd[k].shape) != tuple(getattr(self, k).shape):
                 raise ValueError(f"{k} has shape {tuple(sd[k].shape)}, this buffer's is {tuple(getattr(self, k).shape)}")
-        for k in ("frames", "action", "reward", "done", "age"):
+        for k in self._tensors:
             getattr(self, k).copy_(sd[k])
         self.first, self.w, self.count, self.draws = int(sd["first"]), int(sd["w"]), int(sd["count"]), int(sd["draws"])
         self.seed, self._begun = int(sd.get("seed", self.seed)), bool(sd.get("begun", True))
