@@ -15,6 +15,7 @@
 static thread_local char g_err[tde_host::kErrLen] = "";
 char *tde_host::err_buf() { return g_err; }
 using tde_host::bad;
+using tde_host::bad_in;
 using tde_host::cu_count;
 using tde_host::launch_status;
 
@@ -551,13 +552,7 @@ int tde_vector_obs(const tde_config *cfg, const tde_world *world, const tde_stat
 }
 
 // ---- the planner / forecast family (tde_plan_action, tde_score_plans*, tde_forecast_*): each host-side rule stated once, `fn` names
-// the entry point in the message; an entry point is the list of the pieces that apply to it plus its own one-off rules -----------------
-static int bad_in(const char *fn, const char *msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", fn, msg);
-    return (int)hipErrorInvalidValue;
-}
-
+// the entry point in the message (tde_host::bad_in); an entry point is the list of the pieces that apply to it plus its own one-off rules
 static int check_plan_set(const char *fn, const tde_plan_set *ps)
 {
     if (ps->N < 1 || ps->N > TDE_PLAN_MAX_SET) return bad_in(fn, "N must be in [1, TDE_PLAN_MAX_SET]");

@@ -31,6 +31,13 @@ inline int bad(const char *msg)
     return (int)hipErrorInvalidValue;
 }
 
+// the same for a rule that several entry points share: the message names the one that was called
+inline int bad_in(const char *fn, const char *msg)
+{
+    snprintf(err_buf(), kErrLen, "%s: %s", fn, msg);
+    return (int)hipErrorInvalidValue;
+}
+
 inline int launch_status(const char *what)
 {
     const hipError_t e = hipGetLastError();

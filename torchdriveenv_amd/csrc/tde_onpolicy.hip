@@ -6,20 +6,18 @@
 //     wavefront hides anything, the block in flight is all the latency hiding there is, and its registers (2 x 3 x kGaeBlock) cost
 //     no occupancy that anyone would use.  T / kGaeBlock memory round trips per lane instead of T.
 //   * tde_onpolicy_gather, planes mode: one workgroup per sample, one wavefront per frame of the stack; each reads its layer plane
-//     once (four 16-byte loads per lane at 64 x 64, in flight together) and expands it through raster_expand into its frame of `obs`,
-//     or writes zeros there - tde_replay_sample's construction of `obs`, without the wavefront and the bytes of `next_obs`.
+//     once (four 16-byte loads per lane at 64 x 64, in flight together) and expands it into its frame of `obs`, or writes zeros there:
+//     tde_replay_sample's construction of `obs` - tde_ring.h's frame rule and expansion - without the wavefront and the bytes of
+//     `next_obs`.
 //   * tde_onpolicy_gather, rows mode: one wavefront per sample copies its row.
 // All offsets into frames / obs and into the [T][B] arrays are int64_t.  The specification is restated in numpy by
 // tests/onpolicy_ref.py.
-#include "tde_raster.h"
-#include "tde_host.h"
+#include "tde_ring.h"
 #include "../../include/tde_onpolicy.h"
 
 namespace tde {
 
 constexpr int kGaeBlock = 16;           // steps whose loads are in flight together
-constexpr int kOnpolicyWaves = 4;       // samples per workgroup of the rows gather
-constexpr uint32_t kOnpolicyEnded = 3 | TDE_REPLAY_CUT;
 
 struct GaeArgs {
     const float *reward;                // [C][B] of the ring
@@ -41,8 +39,7 @@ TDE_DEV void gae_load(const GaeArgs &g, int e, int hi, GaeSteps &b)
 #pragma unroll
     for (int j = 0; j < kGaeBlock; ++j) {
         const int t = hi - j < 0 ? 0 : hi - j;
-        const int s = g.base + t >= g.C ? g.base + t - g.C : g.base + t;
-        const int64_t at = (int64_t)s * g.B + e;
+        const int64_t at = (int64_t)ring_slot(g.base, t, g.C) * g.B + e;
         b.r[j] = g.reward[at];
         b.d[j] = g.done[at];
         b.v[j] = g.values[(int64_t)t * g.B + e];
@@ -62,7 +59,7 @@ __global__ __launch_bounds__(64) void gae_kernel(GaeArgs g)
         for (int j = 0; j < kGaeBlock; ++j) {
             const int t = hi - j;
             if (t >= 0) {               // (wave-uniform; no break: the loop must unroll for cur to stay in registers)
-                const bool nnt = (cur.d[j] & kOnpolicyEnded) == 0;
+                const bool nnt = (cur.d[j] & kRingEnded) == 0;
                 const float delta = (cur.r[j] + (nnt ? g.gamma * nv : 0.0f)) - cur.v[j];
                 last = delta + (nnt ? g.gl * last : 0.0f);
                 g.adv[(int64_t)t * g.B + e] = last;
@@ -83,28 +80,23 @@ struct OnpolicyArgs {
     float *action, *old_values, *old_log_prob, *adv_out, *ret_out;
 };
 
-// sample i (wave-uniform): its step and env, its slot, and the slots between `first` and that slot
-struct OnpolicyPick {
-    int t, env, slot, off;
-    bool ok;
-};
-
-TDE_DEV OnpolicyPick onpolicy_pick(const OnpolicyArgs &g, int i)
+// sample i (wave-uniform): the pair of index t * B + e - step t is slot base + t, lead + t slots after `first`
+TDE_DEV RingPick onpolicy_pick(const OnpolicyArgs &g, int i)
 {
     const int B = g.rp.B, v = g.idx[i];
-    OnpolicyPick p;
+    RingPick p;
     p.ok = v >= 0 && v < g.T * B;       // (T * B <= INT32_MAX: checked by the host)
-    p.t = p.ok ? v / B : 0;
-    p.env = p.ok ? v - p.t * B : 0;
-    p.slot = g.base + p.t >= g.rp.C ? g.base + p.t - g.rp.C : g.base + p.t;
-    p.off = g.lead + p.t;
+    const int t = p.ok ? v / B : 0;
+    p.env = p.ok ? v - t * B : 0;
+    p.slot = ring_slot(g.base, t, g.rp.C);
+    p.off = g.lead + t;
     return p;
 }
 
 // the scalars of sample i, by one lane
-TDE_DEV void onpolicy_scalars(const OnpolicyArgs &g, int i, const OnpolicyPick &p)
+TDE_DEV void onpolicy_scalars(const OnpolicyArgs &g, int i, const RingPick &p)
 {
-    const int64_t at = (int64_t)p.slot * g.rp.B + p.env, row = (int64_t)p.t * g.rp.B + p.env;
+    const int64_t at = (int64_t)p.slot * g.rp.B + p.env, row = (int64_t)(p.off - g.lead) * g.rp.B + p.env;
     reinterpret_cast<float2 *>(g.action)[i] = p.ok ? reinterpret_cast<const float2 *>(g.rp.action)[at] : make_float2(0.0f, 0.0f);
     g.old_values[i] = p.ok ? g.values[row] : 0.0f;
     g.old_log_prob[i] = p.ok ? g.log_prob[row] : 0.0f;
@@ -118,39 +110,26 @@ __global__ __launch_bounds__(64 * TDE_REPLAY_MAX_STACK) void onpolicy_gather_pla
 {
     const int lane = (int)(threadIdx.x & 63u), k = (int)(threadIdx.x >> 6), i = (int)blockIdx.x;
     const int C = g.rp.C, B = g.rp.B, ns = g.rp.n_stack, plane = SIZE64 ? 4096 : g.rp.plane;
-    const OnpolicyPick p = onpolicy_pick(g, i);
+    const RingPick p = onpolicy_pick(g, i);
     if (k == 0 && lane == 0) onpolicy_scalars(g, i, p);
     // this wavefront's frame: k of obs (oldest first), slot s - d
     const int d = ns - 1 - k;
     bool show = false;
     int64_t src = 0;
     if (p.ok) {
-        // a frame is shown when it belongs to the episode (age) and has not been overwritten (it lies at or behind `first`)
-        show = d <= (int)g.rp.age[(int64_t)p.slot * B + p.env] && d <= p.off;
-        const int ss = p.slot - d < 0 ? p.slot - d + C : p.slot - d;          // (C >= ns + 1 > d)
-        src = ((int64_t)ss * B + p.env) * plane;
+        show = ring_shown(d, g.rp.age[(int64_t)p.slot * B + p.env], p.off);
+        src = ((int64_t)ring_slot(p.slot, -d, C) * B + p.env) * plane;       // (C >= ns + 1 > d)
     }
-    const uint4 *from = reinterpret_cast<const uint4 *>(g.rp.frames + src);
-    uint8_t *o = g.obs + ((int64_t)i * ns + k) * 3 * plane;
-    const uint32_t bl = TDE_LAYER_BLANK * 0x01010101u;
-    const uint4 blank = make_uint4(bl, bl, bl, bl);
-    if (SIZE64) {
-        uint4 ch[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ch[c] = show ? from[lane + 64 * c] : blank;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) raster_expand(ch[c], o, plane, lane + 64 * c);
-    } else {
-        for (int c = lane; c < plane / 16; c += 64) raster_expand(show ? from[c] : blank, o, plane, c);
-    }
+    const RingFrame o = {g.obs + ((int64_t)i * ns + k) * 3 * plane, true, show}, none = {nullptr, false, false};
+    ring_expand<SIZE64>(reinterpret_cast<const uint4 *>(g.rp.frames + src), plane, lane, o, none);
 }
 
-__global__ __launch_bounds__(64 * kOnpolicyWaves) void onpolicy_gather_rows_kernel(OnpolicyArgs g, int N)
+__global__ __launch_bounds__(64 * kRingWaves) void onpolicy_gather_rows_kernel(OnpolicyArgs g, int N)
 {
-    const int lane = (int)(threadIdx.x & 63u), i = (int)blockIdx.x * kOnpolicyWaves + (int)(threadIdx.x >> 6);
+    const int lane = (int)(threadIdx.x & 63u), i = (int)blockIdx.x * kRingWaves + (int)(threadIdx.x >> 6);
     if (i >= N) return;
     const int D = g.rp.D;
-    const OnpolicyPick p = onpolicy_pick(g, i);
+    const RingPick p = onpolicy_pick(g, i);
     if (lane == 0) onpolicy_scalars(g, i, p);
     const float *row = reinterpret_cast<const float *>(g.rp.frames) + ((int64_t)p.slot * g.rp.B + p.env) * D;
     float *o = reinterpret_cast<float *>(g.obs) + (int64_t)i * D;
@@ -159,15 +138,9 @@ __global__ __launch_bounds__(64 * kOnpolicyWaves) void onpolicy_gather_rows_kern
 
 }  // namespace tde
 
+using namespace tde_host;
+
 namespace {
-
-int bad_in(const char *fn, const char *msg)
-{
-    snprintf(tde_host::err_buf(), tde_host::kErrLen, "%s: %s", fn, msg);
-    return (int)hipErrorInvalidValue;
-}
-
-bool aligned(const void *p, int64_t n) { return ((uintptr_t)p % (uintptr_t)n) == 0; }
 
 // the ring (tde_replay.hip's own check of the struct) and the rollout inside it
 int check_rollout(const char *fn, const tde_replay *rp, int32_t first, int32_t count, int32_t T)
@@ -176,9 +149,7 @@ int check_rollout(const char *fn, const tde_replay *rp, int32_t first, int32_t c
     if (rc) return rc;
     if (T < 1) return bad_in(fn, "T must be >= 1");
     if (count < T) return bad_in(fn, "count must be >= T (the rollout is the newest T stored steps)");
-    if (count > rp->C - 1) return bad_in(fn, "count must be <= C - 1 (one slot is open)");
-    if (first < 0 || first >= rp->C) return bad_in(fn, "first must be in [0, C)");
-    return 0;
+    return check_stored(fn, rp, first, count);
 }
 
 }  // namespace
@@ -231,7 +202,7 @@ int tde_onpolicy_gather(const tde_replay *rp, int32_t first, int32_t count, int3
         if (rp->plane == 4096) tde::onpolicy_gather_planes_kernel<true><<<(unsigned)N, threads, 0, st>>>(g);
         else tde::onpolicy_gather_planes_kernel<false><<<(unsigned)N, threads, 0, st>>>(g);
     } else {
-        tde::onpolicy_gather_rows_kernel<<<(unsigned)((N + tde::kOnpolicyWaves - 1) / tde::kOnpolicyWaves), 64 * tde::kOnpolicyWaves, 0, st>>>(g, N);
+        tde::onpolicy_gather_rows_kernel<<<ring_blocks(N, tde::kRingWaves), 64 * tde::kRingWaves, 0, st>>>(g, N);
     }
     return tde_host::launch_status(fn);
 }

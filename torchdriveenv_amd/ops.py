@@ -719,17 +719,43 @@ class FrameStack:
 
 
 # ---- replay buffer (include/tde_replay.h) ---------------------------------------------------------------------------------------
+def _ring_frame(rp, stacked=False):
+    """dtype and elements of a frame of the ring `rp` - a layer plane (planes mode) or a row (rows mode) - or, stacked, of the
+    observation a gather builds from it"""
+    if rp.plane > 0:
+        return torch.uint8, (3 * rp.n_stack if stacked else 1) * rp.plane
+    return torch.float32, rp.D
+
+
+def _src_bounds(src, B, row, src_offset, src_stride):
+    """`src` must hold B rows of `row` bytes, `src_stride` bytes apart, the first at byte `src_offset`"""
+    if src_offset < 0 or src_stride < row or src_offset + (B - 1) * src_stride + row > src.numel() * src.element_size():
+        raise ValueError(f"src holds {src.numel() * src.element_size()} bytes: too few for {B} rows of {row} bytes, {src_stride} apart, from byte {src_offset}")
+
+
 def _replay_src(rp, src, src_offset, src_stride, dev):
     """address and stride of the frame source of replay_begin / replay_push: a uint8 (planes mode) or float32 (rows mode) device
     tensor holding one plane / row per env `src_stride` bytes apart, the first at byte `src_offset`"""
-    dt = torch.uint8 if rp.plane > 0 else torch.float32
+    dt, per = _ring_frame(rp)
     p = _chk(src, dt, None, "src", dev)
-    row = rp.plane if rp.plane > 0 else 4 * rp.D
+    row = per * src.element_size()
     src_stride = row if src_stride is None else int(src_stride)
     src_offset = int(src_offset)
-    if src_offset < 0 or src_stride < row or src_offset + (rp.B - 1) * src_stride + row > src.numel() * src.element_size():
-        raise ValueError(f"src holds {src.numel() * src.element_size()} bytes: too few for {rp.B} rows of {row} bytes, {src_stride} apart, from byte {src_offset}")
+    _src_bounds(src, rp.B, row, src_offset, src_stride)
     return p + src_offset, src_stride
+
+
+def _sample_args(rp, dev, n, out, idx_in):
+    """what replay_sample and terminal_sample pass after (first, count): n, idx_in, and behind seed and draw the six outputs"""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    dt, per = _ring_frame(rp, stacked=True)
+    po, pn = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["next_observations"], dt, n * per, "next_observations", dev)
+    pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
+    pa, pr = _chk(out["actions"], torch.float32, 2 * n, "actions", dev), _chk(out["rewards"], torch.float32, n, "rewards", dev)
+    pd = _chk(out["dones"], torch.uint8, n, "dones", dev)
+    return (n, _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)), (pi, po, pn, pa, pr, pd)
 
 
 def replay_struct(C_, B, n_stack, plane, D, frames, action, reward, done, age):
@@ -770,17 +796,9 @@ def replay_sample(rp, dev, first, count, n, out, idx_in=None, seed=0, draw=0):
     "next_observations" uint8 [n, 3 * n_stack, plane] (planes mode) or float32 [n, D] (rows mode), "actions" float32 [n, 2],
     "rewards" float32 [n], "dones" uint8 [n] - drawn from (seed, draw) or, with idx_in (int32 [n, 2] (slot, env) pairs), as given"""
     dev = torch.device(dev)
-    n = int(n)
-    if n < 1:
-        raise ValueError("n must be >= 1")
-    dt, per = (torch.uint8, 3 * rp.n_stack * rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
-    po, pn = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["next_observations"], dt, n * per, "next_observations", dev)
-    pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
-    pa, pr = _chk(out["actions"], torch.float32, 2 * n, "actions", dev), _chk(out["rewards"], torch.float32, n, "rewards", dev)
-    pd = _chk(out["dones"], torch.uint8, n, "dones", dev)
-    pin = _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)
-    _lib.check(_call(dev, _lib.load().tde_replay_sample, C.byref(rp), int(first), int(count), n, pin, int(seed) & (2**64 - 1),
-                     int(draw) & (2**64 - 1), pi, po, pn, pa, pr, pd, _lib.current_stream(dev)), "tde_replay_sample")
+    head, outs = _sample_args(rp, dev, n, out, idx_in)
+    _lib.check(_call(dev, _lib.load().tde_replay_sample, C.byref(rp), int(first), int(count), *head, int(seed) & (2**64 - 1),
+                     int(draw) & (2**64 - 1), *outs, _lib.current_stream(dev)), "tde_replay_sample")
     return out
 
 
@@ -835,7 +853,7 @@ def onpolicy_gather(rp, dev, first, count, T, idx, values, log_probs, advantages
         raise ValueError("idx must hold at least one index")
     src = [_chk(t, torch.float32, T * rp.B, nm, dev) for t, nm in ((values, "values"), (log_probs, "log_probs"), (advantages, "advantages"),
                                                                   (returns, "returns"))]
-    dt, per = (torch.uint8, 3 * rp.n_stack * rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    dt, per = _ring_frame(rp, stacked=True)
     po, pa = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["actions"], torch.float32, 2 * n, "actions", dev)
     dst = [_chk(out[k], torch.float32, n, k, dev) for k in ("old_values", "old_log_prob", "advantages", "returns")]
     _lib.check(_call(dev, _lib.load().tde_onpolicy_gather, C.byref(rp), int(first), int(count), T, n, pi, *src, po, pa, *dst,
@@ -851,7 +869,7 @@ def terminal_struct(rp, M, pool, ref):
     if M < 1 or M > rp.B:
         raise ValueError(f"M must be in [1, B = {rp.B}], got {M}")
     dev = pool.device if torch.is_tensor(pool) else None
-    dt, per = (torch.uint8, rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    dt, per = _ring_frame(rp)
     return _abi.TdeTerminal(M, _chk(pool, dt, rp.C * M * per, "pool", dev), _chk(ref, torch.int32, rp.C * rp.B, "ref", dev))
 
 
@@ -866,8 +884,7 @@ def terminal_stash(dev, done_bits, src, src_offset, src_stride, dst):
     ps = _chk(src, dst.dtype, None, "src", dev)
     pt = _chk(dst, dst.dtype, None, "dst", dev)
     src_offset, src_stride = int(src_offset), int(src_stride)
-    if src_offset < 0 or src_stride < row or src_offset + (B - 1) * src_stride + row > src.numel() * src.element_size():
-        raise ValueError(f"src holds {src.numel() * src.element_size()} bytes: too few for {B} rows of {row} bytes, {src_stride} apart, from byte {src_offset}")
+    _src_bounds(src, B, row, src_offset, src_stride)
     _lib.check(_call(dev, _lib.load().tde_terminal_stash, B, row, pd, ps + src_offset, src_stride, pt, _lib.current_stream(dev)),
                "tde_terminal_stash")
     return dst
@@ -877,7 +894,7 @@ def terminal_push(rp, tm, dev, w, done_bits, term_src):
     """tde_terminal_push on the current stream, beside replay_push for slot `w`: the terminal frames term_src ([B, plane] uint8 or
     [B, D] float32) of the envs with done_bits[e] & 3 go to pool[w] in env order (the first M of them), ref[w] is written whole"""
     dev = torch.device(dev)
-    dt, per = (torch.uint8, rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
+    dt, per = _ring_frame(rp)
     pd = _chk(done_bits, torch.uint8, rp.B, "done_bits", dev)
     ps = _chk(term_src, dt, rp.B * per, "term_src", dev)
     _lib.check(_call(dev, _lib.load().tde_terminal_push, C.byref(rp), C.byref(tm), int(w), pd, ps, per * term_src.element_size(),
@@ -888,15 +905,7 @@ def terminal_sample(rp, tm, dev, first, count, n, out, idx_in=None, seed=0, draw
     """tde_terminal_sample on the current stream: replay_sample's arguments and outputs; where a transition ended its episode and its
     terminal frame is in the pool, "next_observations" is the terminal observation and "dones" carries _abi.TERMINAL_HAS"""
     dev = torch.device(dev)
-    n = int(n)
-    if n < 1:
-        raise ValueError("n must be >= 1")
-    dt, per = (torch.uint8, 3 * rp.n_stack * rp.plane) if rp.plane > 0 else (torch.float32, rp.D)
-    po, pn = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["next_observations"], dt, n * per, "next_observations", dev)
-    pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
-    pa, pr = _chk(out["actions"], torch.float32, 2 * n, "actions", dev), _chk(out["rewards"], torch.float32, n, "rewards", dev)
-    pd = _chk(out["dones"], torch.uint8, n, "dones", dev)
-    pin = _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)
-    _lib.check(_call(dev, _lib.load().tde_terminal_sample, C.byref(rp), C.byref(tm), int(first), int(count), n, pin,
-                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), pi, po, pn, pa, pr, pd, _lib.current_stream(dev)), "tde_terminal_sample")
+    head, outs = _sample_args(rp, dev, n, out, idx_in)
+    _lib.check(_call(dev, _lib.load().tde_terminal_sample, C.byref(rp), C.byref(tm), int(first), int(count), *head,
+                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), *outs, _lib.current_stream(dev)), "tde_terminal_sample")
     return out
