@@ -39,6 +39,11 @@ def main():
     print(f"{len(buf)} transitions held ({buf.count} steps x {num_envs} envs), {int(batch.terminal.sum())} of the 256 drawn ended their episode")
     # where .bootstrap is set, next_observations is what the learner bootstraps from - for a truncated episode, its terminal observation
     print(f"{int(batch.bootstrap.sum())} of them bootstrap from next_observations ({int((batch.bootstrap & batch.terminal).sum())} truncated, from the terminal observation)")
+    # the n-step target of the same learner: rewards summed over up to three steps, cut short where the episode stopped
+    nb = buf.sample_nstep(256, n_steps=3, gamma=0.99)
+    q_next = torch.zeros(256, device=nb.rewards.device)  # Q(nb.next_observations, policy(nb.next_observations)) goes here
+    target = nb.rewards + nb.discounts * nb.bootstrap * q_next
+    print(f"n-step: target {tuple(target.shape)}, steps taken {torch.bincount(nb.steps.long(), minlength=4).tolist()[1:]} (1, 2, 3)")
     stacked = 2 * batch.observations[0].numel() * batch.observations.element_size()
     print(f"bytes held per transition: {buf.bytes_per_transition} (a store of stacked obs + next_obs: {stacked})")
 

@@ -206,6 +206,8 @@ class TdeTerminal(C.Structure):
 
 TDE_TERMINAL_VERSION = 1         # include/tde_terminal.h
 TERMINAL_HAS = 0x40              # in the done byte a terminal sample returns: next_observations is the terminal observation
+TDE_NSTEP_VERSION = 1            # include/tde_nstep.h
+NSTEP_MAX = 64                   # the longest look-ahead of an n-step sample
 
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7

@@ -17,6 +17,8 @@ REPLAY_SYMBOLS = ["tde_replay_version", "tde_replay_begin", "tde_replay_push", "
 ONPOLICY_SYMBOLS = ["tde_onpolicy_version", "tde_gae", "tde_onpolicy_gather"]
 # every symbol include/tde_terminal.h declares (additive over the replay header: TDE_TERMINAL_VERSION)
 TERMINAL_SYMBOLS = ["tde_terminal_version", "tde_terminal_stash", "tde_terminal_push", "tde_terminal_sample"]
+# every symbol include/tde_nstep.h declares (additive over the terminal header: TDE_NSTEP_VERSION)
+NSTEP_SYMBOLS = ["tde_nstep_version", "tde_nstep_sample"]
 
 _lib = None
 
@@ -113,6 +115,15 @@ def load():
     L.tde_terminal_push.argtypes = [rpp, tmp, i32, vp, vp, i64, vp]
     L.tde_terminal_sample.argtypes = [rpp, tmp, i32, i32, i32, vp, u64, u64] + [vp] * 6 + [vp]
     for s in TERMINAL_SYMBOLS:
+        getattr(L, s).restype = C.c_int
+    missing = [s for s in NSTEP_SYMBOLS if not hasattr(L, s)]
+    if missing:
+        raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")
+    if L.tde_nstep_version() != _abi.TDE_NSTEP_VERSION:
+        raise TdeError(f"n-step version mismatch: library {L.tde_nstep_version()} vs python {_abi.TDE_NSTEP_VERSION}")
+    L.tde_nstep_version.argtypes = []
+    L.tde_nstep_sample.argtypes = [rpp, tmp, i32, i32, i32, vp, u64, u64, i32, f32] + [vp] * 8 + [vp]
+    for s in NSTEP_SYMBOLS:
         getattr(L, s).restype = C.c_int
     _lib = L
     return L

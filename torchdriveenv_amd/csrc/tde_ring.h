@@ -1,4 +1,4 @@
-// tde_ring.h — what the three units over the replay ring (tde_replay.hip, tde_onpolicy.hip, tde_terminal.hip) share: what a learner
+// tde_ring.h — what the units over the replay ring (tde_replay.hip, tde_onpolicy.hip, tde_terminal.hip, tde_nstep.hip) share: what a learner
 // sees of a stored transition, stated once.
 //   * device side: the "ended" mask, the ring's wrap, the row copy, the pick of a sample (the draw, and the validity rule of a given
 //     pair), the frame rule, the expansion of a layer plane into frames of obs / next_obs, the scalars of a sampled transition;

@@ -909,3 +909,22 @@ def terminal_sample(rp, tm, dev, first, count, n, out, idx_in=None, seed=0, draw
     _lib.check(_call(dev, _lib.load().tde_terminal_sample, C.byref(rp), C.byref(tm), int(first), int(count), *head,
                      int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), *outs, _lib.current_stream(dev)), "tde_terminal_sample")
     return out
+
+
+# ---- n-step returns from the ring (include/tde_nstep.h) ---------------------------------------------------------------------------------
+def nstep_sample(rp, tm, dev, first, count, n, n_steps, gamma, out, idx_in=None, seed=0, draw=0):
+    """tde_nstep_sample on the current stream: replay_sample's (tm None) / terminal_sample's arguments and outputs with a look-ahead of
+    up to `n_steps` stored steps - "rewards" is the discounted sum over the m steps taken, "next_observations" and "dones" are those of
+    the last of them - and two more tensors of `out`: "discounts" float32 [n] (gamma ** m) and "steps" uint8 [n] (m)"""
+    dev = torch.device(dev)
+    n_steps, gamma = int(n_steps), float(gamma)
+    if not 1 <= n_steps <= _abi.NSTEP_MAX:
+        raise ValueError(f"n_steps must be in [1, {_abi.NSTEP_MAX}], got {n_steps}")
+    if not 0.0 <= gamma <= 1.0:
+        raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+    head, outs = _sample_args(rp, dev, n, out, idx_in)
+    pg, ps = _chk(out["discounts"], torch.float32, head[0], "discounts", dev), _chk(out["steps"], torch.uint8, head[0], "steps", dev)
+    _lib.check(_call(dev, _lib.load().tde_nstep_sample, C.byref(rp), None if tm is None else C.byref(tm), int(first), int(count), *head,
+                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), n_steps, gamma, *outs, pg, ps, _lib.current_stream(dev)),
+               "tde_nstep_sample")
+    return out

@@ -10,6 +10,11 @@ sampled.  Vector and state observations are kept as float32 rows.
     obs, *_ = env.step(actions);  buf.push(actions)            # every step
     env.reset(mask=m);            buf.begin(mask=m)            # a reset of the caller's own
     batch = buf.sample(256)                                    # observations, actions, next_observations, dones, rewards
+    batch = buf.sample_nstep(256, n_steps=3, gamma=0.99)       # the same with n-step rewards, and discounts, steps
+
+sample_nstep() (include/tde_nstep.h, csrc/tde_nstep.hip) looks up to n_steps stored steps ahead of the drawn one and stops where the
+episode stopped: `rewards` is the discounted sum over the steps taken, `next_observations` and `dones` are those of the last of them,
+and the learner's target is rewards + discounts * bootstrap * Q(next_observations).
 
 On an env built with terminal_obs=True the buffer also keeps the terminal frames (include/tde_terminal.h, csrc/tde_terminal.hip): a
 transition that ended its episode then returns the observation the env showed before it was re-spawned as `next_observations`, and
@@ -40,6 +45,16 @@ class ReplaySamples(namedtuple("ReplaySamples", ["observations", "actions", "nex
         handle_timeout_termination)"""
         d = self.dones
         return ((d & (3 | _abi.REPLAY_CUT)) == 0) | (((d & 3) == 2) & ((d & _abi.TERMINAL_HAS) != 0))
+
+
+class NStepSamples(namedtuple("NStepSamples", ReplaySamples._fields + ("discounts", "steps"))):
+    """ReplaySamples over a look-ahead of m <= n_steps stored steps from the drawn one (observations, actions, indices are the drawn
+    step's): rewards float32 [n] is r_0 + gamma r_1 + ... + gamma^(m-1) r_(m-1), next_observations and dones are those of the last step
+    taken, discounts float32 [n] is gamma^m and steps uint8 [n] is m (0 for a pair that gathered zeros).  The n-step target is
+    rewards + discounts * bootstrap * Q(next_observations)."""
+    __slots__ = ()
+    terminal = ReplaySamples.terminal
+    bootstrap = ReplaySamples.bootstrap
 
 
 class ReplayBuffer:
@@ -113,6 +128,7 @@ class ReplayBuffer:
         self.first = self.w = self.count = self.draws = 0
         self._begun = False
         self._out = {}
+        self._nstep_out = {}
 
     # ---- bookkeeping --------------------------------------------------------------------------------------------------------
     def __len__(self):
@@ -234,6 +250,51 @@ class ReplayBuffer:
         if idx is None:
             self.draws += 1
         return ReplaySamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"], out["indices"])
+
+    def sample_nstep(self, n, n_steps, gamma=0.99, idx=None, check=True):
+        """`n` n-step transitions -> NStepSamples: sample()'s pick (the same draw from the same counter, or idx under the same `check`)
+        with a look-ahead of up to `n_steps` (1 .. NSTEP_MAX) stored steps from each picked step, which stops at the first step that
+        ended its episode or was cut, and at the newest stored step.  One launch (tde_nstep_sample), through the terminal pool when
+        the buffer has one.  The tensors it returns are its own, reused by the next sample_nstep of the same size."""
+        n_steps, gamma = int(n_steps), float(gamma)
+        if not 1 <= n_steps <= _abi.NSTEP_MAX:
+            raise ValueError(f"n_steps must be in [1, {_abi.NSTEP_MAX}], got {n_steps}")
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        n, idx = self._request(n, idx, check)
+        out = self._nstep_out.get(n)
+        if out is None:
+            out = self._nstep_out[n] = {**self._alloc(n), "discounts": torch.empty(n, dtype=torch.float32, device=self.dev),
+                                        "steps": torch.empty(n, dtype=torch.uint8, device=self.dev)}
+        ops.nstep_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, n_steps, gamma, out, idx, self.seed, self.draws)
+        if idx is None:
+            self.draws += 1
+        return NStepSamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"], out["indices"],
+                            out["discounts"], out["steps"])
+
+    def _request(self, n, idx, check):
+        """(n, idx) of a sample_nstep call as the launch takes them, under the rules sample() states for its own arguments"""
+        if idx is not None:
+            idx = torch.as_tensor(idx, device=self.dev).to(torch.int32).reshape(-1, 2).contiguous()
+            if n is None:
+                n = idx.shape[0]
+            if idx.shape[0] != int(n):
+                raise ValueError(f"idx must hold {n} (slot, env) pairs")
+        if n is None or int(n) < 1:
+            raise ValueError("n must be >= 1")
+        if self.count < 1:
+            raise ValueError("the buffer holds no transition yet")
+        if idx is None and self.count <= self.n_stack - 1:
+            raise ValueError(f"sample_nstep() draws steps whose whole frame stack is in the ring: it needs more than {self.n_stack - 1} stored steps, the buffer holds {self.count}")
+        if idx is not None and check:
+            s, e = idx[:, 0].long(), idx[:, 1].long()
+            ok = (s >= 0) & (s < self.C) & (e >= 0) & (e < self.B)
+            s, e = s.clamp(0, self.C - 1), e.clamp(0, self.B - 1)
+            off = (s - self.first) % self.C
+            ok &= (off < self.count) & (torch.clamp(self.age[s, e].long(), max=self.n_stack - 1) <= off)
+            if not bool(ok.all()):
+                raise ValueError("idx holds pairs that are not stored transitions with their whole frame stack in the ring (valid_pairs())")
+        return int(n), idx
 
     @property
     def _tensors(self):
