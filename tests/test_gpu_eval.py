@@ -209,6 +209,47 @@ def test_evaluate_planner_records_every_job_once_under_its_scenario():
         env.reset(options={"scenario": 4})
 
 
+_both = {}                                    # (obs_mode, frame_stack) -> the ext and the ctypes env, kept for the reset test
+
+
+@pytest.mark.parametrize("obs_mode,frame_stack", [("state", 1), ("birdview", 2)])
+def test_evaluate_is_the_same_through_both_bindings(obs_mode, frame_stack):
+    """evaluate() through the extension's handle and through ops.CtypesHandle: every field of the results byte for byte, the flags
+    restored.  3 envs x 8 jobs: envs re-spawn mid-evaluation (eval_advance, and with the birdview FrameStack.rerender with a mask)"""
+    from torchdriveenv_amd.config import EnvConfig
+    from torchdriveenv_amd.env import BatchedWaypointEnv
+
+    w = _worlds(16)[0]
+    res = {}
+    for binding in ("ext", "ctypes"):
+        env = BatchedWaypointEnv(EnvConfig(seed=9, max_environment_steps=24, distance_cutoff=0.25), w, num_envs=3, agents_per_env=16,
+                                 obs_mode=obs_mode, frame_stack=frame_stack, binding=binding)
+        assert env.binding == binding
+        full = int(env.tde_cfg.flags)
+        res[binding] = env.evaluate("planner", repeats=2)
+        assert int(env.tde_cfg.flags) == full and env.auto_reset, binding
+        _both.setdefault((obs_mode, frame_stack), {})[binding] = env
+    assert len(res["ext"]) == 8 and res["ext"].scenario.tolist() == [0, 1, 2, 3, 0, 1, 2, 3]
+    for f in ("episode_return", "length", "reached", "scenario", "bits", "psi_smoothness", "speed_smoothness"):
+        a, b = getattr(res["ext"], f), getattr(res["ctypes"], f)
+        assert a.dtype == b.dtype and a.numpy().tobytes() == b.numpy().tobytes(), f
+
+
+@pytest.mark.parametrize("obs_mode,frame_stack", [("state", 1), ("birdview", 2)])
+def test_reset_to_scenario_and_masked_reset_are_the_same_through_both_bindings(obs_mode, frame_stack):
+    """on the envs the evaluation above left: reset(options={"scenario": ...}), then reset(mask=...), through either handle"""
+    if (obs_mode, frame_stack) not in _both:                         # (run alone: the evaluation makes the envs)
+        test_evaluate_is_the_same_through_both_bindings(obs_mode, frame_stack)
+    e_ext, e_ct = (_both[(obs_mode, frame_stack)][b] for b in ("ext", "ctypes"))
+    for kw in (dict(options={"scenario": [2, -1, 0]}), dict(mask=[1, 0, 1])):
+        o_ext, o_ct = e_ext.reset(**kw), e_ct.reset(**kw)
+        assert torch.equal(o_ext, o_ct), kw
+        for k in ("x", "scn", "episode"):
+            assert torch.equal(e_ext.state[k], e_ct.state[k]), (kw, k)
+        if "options" in kw:
+            assert e_ext.state["scn"][0] == 2 and e_ext.state["scn"][2] == 0
+
+
 def test_graph_capture_of_step_and_advance_replays_to_the_same_records():
     B, A = 6, 16
     w, _, dw, _ = _worlds(A)

@@ -478,7 +478,10 @@ def test_extension_equals_ctypes_equals_oracle(small_world):
     B = 96
     e_ext = BatchedWaypointEnv(cfg, small_world, num_envs=B, device=DEV, obs_mode="state", binding="ext")
     e_ct = BatchedWaypointEnv(cfg, small_world, num_envs=B, device=DEV, obs_mode="state", binding="ctypes")
-    assert e_ext._h is not None and e_ct._h is None
+    from torchdriveenv_amd import _ext
+
+    assert type(e_ext._h) is _ext.load().EnvHandle and type(e_ct._h) is ops.CtypesHandle
+    assert e_ext.binding == "ext" and e_ct.binding == "ctypes"
     hs = EnvState(B, small_world.A)
     ocfg = e_ext.tde_cfg
     oracle.env_reset(ocfg, small_world, hs)

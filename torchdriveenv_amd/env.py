@@ -8,6 +8,7 @@
 
 What stays in Python is only argument marshalling; every number comes from libtde_hip.so.  There is no CPU fallback.
 """
+import contextlib
 import dataclasses
 import math
 import warnings
@@ -627,8 +628,9 @@ class BatchedWaypointEnv:
                  frame_stack=1, auto_reset=True, with_info=True, background=None, env_base=0, binding="ext",
                  info_magnitudes=True, road_meshes=None, near_range=None, traffic_lights=None, start_headings=None, light_radius=150.0,
                  heading_samples=16, near_field=None, vector_obs=None, planner=None, plan_refine=None, plan_react=None, terminal_obs=False):
-        """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp), "ctypes" = through
-        the ctypes binding of the same C-ABI (ops.py); both call the very same entry points of libtde_hip.so.
+        """binding: "ext" = launches go through the PyTorch-ROCm C++ extension (csrc/tde_torch_ext.cpp: its EnvHandle), "ctypes" =
+        through the ctypes binding of the same C-ABI (ops.py: ops.CtypesHandle, which has EnvHandle's methods); both call the very same
+        entry points of libtde_hip.so, and the env launches through whichever handle it holds (`self.binding` names it).
         info_magnitudes (default): info["offroad"] / info["collision"] hold the MAGNITUDES the reference reports there (ref
         gym_env.py:427-428: sum over the ego's corners of clamp(distance - threshold, 0); sum of the IoUs with the agents the ego
         overlaps), written by the step kernel itself for the egos it flagged, before a finished env is re-spawned
@@ -758,22 +760,23 @@ class BatchedWaypointEnv:
         self.observation_space = (_box(0, 255, (3 * self.frame_stack, self._res, self._res), np.uint8) if obs_mode == "birdview" else
                                   _box(-np.inf, np.inf, (self.vector_obs.dim if obs_mode == "vector" else 8,), np.float32))
         self._vobs = self._ray_dir = None
-        self._plan_out = self._plan_diag = self._plan_struct = self._refine = None
+        self._plan_out = self._plan_diag = self._refine = None
         self._plan_fc = self._plan_lat = None          # planner.predict == "route" / "queue": the forecast buffer, the lattice as one-knot sequences
         if obs_mode == "vector":
             self._vobs = torch.zeros((self.num_envs, self.vector_obs.dim), dtype=torch.float32, device=self.torch_device)
             self._ray_dir = torch.from_numpy(self.vector_obs.ray_directions()).to(self.torch_device)
         self.reward_range = (-float("inf"), float("inf"))           # ref gym_env.py:97
         self._vec = None
-        self._h = None
         self._mag = self.state["magnitudes"]                         # float32 [B, 4] written by the step (None: indicators)
-        self._hnf = None
         self._nf_mask = None
+        # every launch goes through self._h: the extension's EnvHandle or ops.CtypesHandle, which have the same methods
+        self.binding = binding
         if binding == "ext":
             from . import _ext
             self._h = _ext.env_handle(self.tde_cfg, self.dworld, self.state)
-            if self.dnf is not None:
-                self._hnf = _ext.near_field_of(self.dnf)
+            self._hnf = _ext.near_field_of(self.dnf) if self.dnf is not None else None
+        else:
+            self._h, self._hnf = ops.CtypesHandle(self.tde_cfg, self.dworld, self.state), self.dnf
         # terminal_obs: the newest frame each env showed when it last finished (tde_terminal_stash), and what step() needs around it
         self.terminal_frames = self._term_mask = self._term_packed = self._term_pack_struct = None
         if self.terminal_obs:
@@ -818,21 +821,13 @@ class BatchedWaypointEnv:
             # the SB3-style auto-reset: the re-spawn and the re-spawned views' first observation in ONE C-ABI call
             if self._stack is not None:
                 self._obs = self._stack.reset_rerender(self.tde_cfg, self.dworld, self.state, m, self._fov)
-            elif self._h is not None:
-                self._h.reset_render(m, int(self.tde_cfg.flags), self._obs, self._res, self._res, self._fov, 1, None, 0, self._rflags)
             else:
-                ops.env_reset_render(self.tde_cfg, self.dworld, self.state, m, self._obs, self._res, self._res, self._fov, 1,
-                                     flags=self._rflags)
+                self._h.reset_render(m, int(self.tde_cfg.flags), self._obs, self._res, self._res, self._fov, 1, None, 0, self._rflags)
             return self._obs
         if scn is not None:
-            if self._h is not None:
-                self._h.reset_to(scn, m, int(self.tde_cfg.flags))
-            else:
-                ops.env_reset_to(self.tde_cfg, self.dworld, self.state, scn, m)
-        elif self._h is not None:
-            self._h.reset(m, int(self.tde_cfg.flags))
+            self._h.reset_to(scn, m, int(self.tde_cfg.flags))
         else:
-            ops.env_reset(self.tde_cfg, self.dworld, self.state, m)
+            self._h.reset(m, int(self.tde_cfg.flags))
         self._spawn_near_field(m)                                    # (near-field envs: reset -> spawn -> render)
         if self.obs_mode == "vector":
             return self._vector_obs(m)                               # (a masked reset rewrites the re-spawned envs' rows only)
@@ -856,10 +851,17 @@ class BatchedWaypointEnv:
             if self._nf_mask is None:
                 self._nf_mask = torch.empty(self.num_envs, dtype=torch.uint8, device=self.torch_device)
             mask = torch.bitwise_or(st["terminated"], st["truncated"], out=self._nf_mask)
-        if self._h is not None:
-            self._h.near_field_spawn(self._hnf, mask, int(self.tde_cfg.flags))
-        else:
-            ops.near_field_spawn(self.tde_cfg, self.dworld, self.state, self.dnf, mask)
+        self._h.near_field_spawn(self._hnf, mask, int(self.tde_cfg.flags))
+
+    @contextlib.contextmanager
+    def _without_autoreset(self):
+        """tde_cfg.flags without F_AUTORESET inside the block (a step then leaves the envs it finished as they ended), restored after it"""
+        full = int(self.tde_cfg.flags)
+        self.tde_cfg.flags = full & ~_abi.F_AUTORESET
+        try:
+            yield
+        finally:
+            self.tde_cfg.flags = full
 
     def _flag_views(self):
         """the state's terminated / truncated bytes seen as bool (no copy), formed once: the buffers never move"""
@@ -877,10 +879,7 @@ class BatchedWaypointEnv:
             a = torch.as_tensor(actions, dtype=torch.float32, device=self.torch_device).reshape(self.num_envs, 2).contiguous()
         if self.terminal_obs and self.auto_reset:                    # (the VecEnv adapter clears the flag and re-spawns the envs itself)
             return self._step_terminal(a)
-        if self._h is not None:
-            self._h.step(a, int(self.tde_cfg.flags))
-        else:
-            ops.env_step(self.tde_cfg, self.dworld, self.state, action=a)
+        self._h.step(a, int(self.tde_cfg.flags))
         if self.dnf is not None and self.auto_reset:
             self._spawn_near_field(done=True)                        # the envs the step re-spawned, before they are observed
         st = self.state
@@ -918,16 +917,9 @@ class BatchedWaypointEnv:
         the observation, which for a finished env is its terminal one -> tde_terminal_stash of the finished envs' newest frame into
         terminal_frames -> reset(mask=done): the masked re-spawn and re-render.  Same results as step() without the option."""
         st = self.state
-        full = int(self.tde_cfg.flags)
-        self.tde_cfg.flags = full & ~_abi.F_AUTORESET
-        try:
-            if self._h is not None:
-                self._h.step(a, int(self.tde_cfg.flags))
-            else:
-                ops.env_step(self.tde_cfg, self.dworld, st, action=a)
+        with self._without_autoreset():
+            self._h.step(a, int(self.tde_cfg.flags))
             obs = st["obs"] if self.obs_mode == "state" else self._vector_obs() if self.obs_mode == "vector" else self.get_obs()
-        finally:
-            self.tde_cfg.flags = full
         src, off, stride = self._terminal_source(obs)
         ops.terminal_stash(self.torch_device, st["done_bits"], src, off, stride, self.terminal_frames)
         obs = self.reset(mask=torch.bitwise_or(st["terminated"], st["truncated"], out=self._term_mask))
@@ -947,13 +939,8 @@ class BatchedWaypointEnv:
         post = flags | (full & _abi.F_AUTORESET)            # (WaypointVecEnv.step_wait clears the flag: it re-spawns the envs itself)
         self.tde_cfg.flags = flags
         try:
-            if self._h is not None:
-                self._h.step(a, flags)
-                self._h.post_step(self._mag, post)
-            else:
-                ops.env_step(self.tde_cfg, self.dworld, st, action=a)
-                self.tde_cfg.flags = post
-                ops.env_post_step(self.tde_cfg, self.dworld, st, self._mag)
+            self._h.step(a, flags)
+            self._h.post_step(self._mag, post)
         finally:
             self.tde_cfg.flags = full
         if full & _abi.F_AUTORESET:
@@ -986,22 +973,18 @@ class BatchedWaypointEnv:
             raise NotImplementedError("rollout() with near_field: the rollout kernels re-spawn finished envs inside one launch, where "
                                       "the near-field spawner cannot run; step() the envs instead")
         a = torch.as_tensor(actions, dtype=torch.float32, device=self.torch_device).contiguous()
-        if self._h is not None:
-            reward = torch.empty(a.shape[:2], dtype=torch.float32, device=self.torch_device)
-            done = torch.empty(a.shape[:2], dtype=torch.uint8, device=self.torch_device)
-            self._h.rollout(a, reward, done, int(self.tde_cfg.flags))
-            return reward, done
-        return ops.env_rollout(self.tde_cfg, self.dworld, self.state, a)
+        reward = torch.empty(a.shape[:2], dtype=torch.float32, device=self.torch_device)
+        done = torch.empty(a.shape[:2], dtype=torch.uint8, device=self.torch_device)
+        self._h.rollout(a, reward, done, int(self.tde_cfg.flags))
+        return reward, done
 
     def get_obs(self, fresh=None):
         if self.obs_mode == "vector":
             return self._vector_obs()
         if self.obs_mode == "state":
             # x, y, psi, v, target offset (forward, left) in the ego frame, target-exists flag, environment_steps
-            if self._h is not None:
-                self._h.state_obs(self.state["obs"])
-                return self.state["obs"]
-            return ops.state_obs(self.dworld, self.state, self.state["obs"])
+            self._h.state_obs(self.state["obs"])
+            return self.state["obs"]
         if self.frame_stack > 1:
             if self._stack is None:
                 self._stack = ops.FrameStack(self.num_envs, self.frame_stack, self._res, self._res, self.torch_device,
@@ -1016,11 +999,8 @@ class BatchedWaypointEnv:
     def _vector_obs(self, only=None):
         """tde_vector_obs into the env's [B, D] buffer (the rows of `only`, uint8 [B], or all) -> the buffer"""
         vo = self.vector_obs
-        if self._h is not None:
-            self._h.vector_obs(self._vobs, self._ray_dir, int(vo.k_neighbours), int(vo.n_rays), float(vo.neighbour_radius),
-                               float(vo.ray_range), float(vo.ray_step), only, int(self.tde_cfg.flags))
-        else:
-            ops.vector_obs(self.tde_cfg, self.dworld, self.state, vo, self._ray_dir, self._vobs, only)
+        self._h.vector_obs(self._vobs, self._ray_dir, int(vo.k_neighbours), int(vo.n_rays), float(vo.neighbour_radius),
+                           float(vo.ray_range), float(vo.ray_step), only, int(self.tde_cfg.flags))
         return self._vobs
 
     def plan_actions(self, out=None, only=None, diag=False):
@@ -1053,7 +1033,11 @@ class BatchedWaypointEnv:
             T = int(pl.horizon) + (int(self.plan_refine.tail) if self.plan_refine is not None else 0)
             if self._plan_fc is None:
                 self._plan_fc = self._forecast_args(T, only, None)[0]
-            fc = self._forecast(self._plan_fc, only) if pl.predict == "route" else self._forecast_scene(self._plan_fc, None, only)
+            fc = self._plan_fc
+            if pl.predict == "route":
+                self._h.forecast_agents(fc, only, int(self.tde_cfg.flags))
+            else:
+                self._h.forecast_scene(fc, None, only, int(self.tde_cfg.flags))
         if self.plan_refine is not None:
             if self._plan_diag is None:
                 self._plan_diag = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.torch_device)
@@ -1063,13 +1047,8 @@ class BatchedWaypointEnv:
             la = self._plan_lattice()
             self._score_plans(la["seq"], int(pl.horizon), 0, only, la["cost"], la["fail"], out, d, fc)
             return (out, d) if diag else out
-        if self._h is not None:
-            self._h.plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings], *self._plan_scalars(), only, d,
-                                int(self.tde_cfg.flags))
-        else:
-            if self._plan_struct is None:
-                self._plan_struct = ops.planner_struct(pl)
-            ops.plan_action(self.tde_cfg, self.dworld, self.state, self._plan_struct, out, only, d)
+        self._h.plan_action(out, [float(v) for v in pl.accelerations], [float(v) for v in pl.steerings], *self._plan_scalars(), only, d,
+                            int(self.tde_cfg.flags))
         return (out, d) if diag else out
 
     def _plan_lattice(self):
@@ -1099,38 +1078,13 @@ class BatchedWaypointEnv:
         return int(pl.horizon), float(pl.v_target), float(pl.margin), float(pl.w_progress), float(pl.w_speed), float(pl.w_steer)
 
     def _score_plans(self, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast=None, react=False):
-        """tde_score_plans (forecast: tde_score_plans_forecast; react: tde_score_plans_scene) through the env's binding (arguments
+        """tde_score_plans (forecast: tde_score_plans_forecast; react: tde_score_plans_scene) through the env's handle (arguments
         already checked)"""
-        if self._h is not None:
-            args = (seq, knot_len, tail, cost, fail_step, *self._plan_scalars(), only, action, diag, int(self.tde_cfg.flags))
-            if react:
-                self._h.score_plans_scene(*args)
-            else:
-                self._h.score_plans(*args, forecast)
+        args = (seq, knot_len, tail, cost, fail_step, *self._plan_scalars(), only, action, diag, int(self.tde_cfg.flags))
+        if react:
+            self._h.score_plans_scene(*args)
         else:
-            if self._plan_struct is None:
-                self._plan_struct = ops.planner_struct(self.planner)
-            args = (self.tde_cfg, self.dworld, self.state, self._plan_struct, seq, knot_len, tail, only, cost, fail_step, action, diag)
-            if react:
-                ops.score_plans_scene(*args)
-            else:
-                ops.score_plans(*args, forecast)
-
-    def _forecast(self, out, only):
-        """tde_forecast_agents into `out` (float32 [B, T, A, 4]) through the env's binding (arguments already checked) -> out"""
-        if self._h is not None:
-            self._h.forecast_agents(out, only, int(self.tde_cfg.flags))
-        else:
-            ops.forecast_agents(self.tde_cfg, self.dworld, self.state, out.shape[1], only, out)
-        return out
-
-    def _forecast_scene(self, out, ego_actions, only):
-        """tde_forecast_scene into `out` (float32 [B, T, A, 4]) through the env's binding (arguments already checked) -> out"""
-        if self._h is not None:
-            self._h.forecast_scene(out, ego_actions, only, int(self.tde_cfg.flags))
-        else:
-            ops.forecast_scene(self.tde_cfg, self.dworld, self.state, out.shape[1], ego_actions, only, out)
-        return out
+            self._h.score_plans(*args, forecast)
 
     def _forecast_args(self, T, only, out):
         """what forecast_agents() and forecast_scene() share: T (None: the planner's horizon) an integer in range, `out` checked, or
@@ -1160,7 +1114,8 @@ class BatchedWaypointEnv:
             ops.check_ego_actions(ego_actions, self.num_envs, out.shape[1])
             if ego_actions.device != self.torch_device:
                 raise ValueError(f"ego_actions is on {ego_actions.device}, expected {self.torch_device}")
-        return self._forecast_scene(out, ego_actions, only)
+        self._h.forecast_scene(out, ego_actions, only, int(self.tde_cfg.flags))
+        return out
 
     def forecast_agents(self, T=None, only=None, out=None):
         """where the environment's own rules put every other agent at each of the next T steps when nobody is in its cone
@@ -1170,7 +1125,9 @@ class BatchedWaypointEnv:
         (None: the planner's horizon); only: uint8 [B], the other envs' rows are left as they are (zeros in a fresh buffer); out: a
         float32 [B, T, A, 4] device tensor to write into (16 * B * T * A bytes the caller keeps).  score_plans(forecast=) takes the
         result."""
-        return self._forecast(*self._forecast_args(T, only, out))
+        out, only = self._forecast_args(T, only, out)
+        self._h.forecast_agents(out, only, int(self.tde_cfg.flags))
+        return out
 
     def score_plans(self, seq, knot_len=None, tail=0, only=None, forecast=None, react=False):
         """how each of N action sequences per ego fares on the state as it is (tde_score_plans with self.planner's horizon, margin,
@@ -1256,20 +1213,15 @@ class BatchedWaypointEnv:
         ev.active.copy_((ev.plan[0] >= 0).to(torch.uint8))
         obs = self.reset(options={"scenario": ev.plan[0].clamp(min=-1)})
         st = self.state
-        full = int(self.tde_cfg.flags)
         respawned = torch.empty(B, dtype=torch.uint8, device=dev)
-        self.tde_cfg.flags = full & ~_abi.F_AUTORESET
-        try:
+        with self._without_autoreset():
             flags = int(self.tde_cfg.flags)
             for t in range(ev.R * int(self.tde_cfg.max_steps)):
                 if t % 8 == 0 and not bool(ev.active.any()):
                     break
                 a = self.plan_actions() if isinstance(policy, str) else policy(obs)
                 obs = self.step(a)[0]
-                if self._h is not None:
-                    self._h.eval_advance(ev.plan, ev.round, ev.active, ev.acc, ev.results, flags)
-                else:
-                    ops.eval_advance(self.tde_cfg, self.dworld, st, ev)
+                self._h.eval_advance(ev.plan, ev.round, ev.active, ev.acc, ev.results, flags)
                 if self.dnf is not None or self.obs_mode != "state":
                     # the envs the advance re-spawned: finished at this step and still evaluating
                     torch.bitwise_or(st["terminated"], st["truncated"], out=respawned).bitwise_and_(ev.active)
@@ -1281,19 +1233,13 @@ class BatchedWaypointEnv:
                             obs = self._obs = self._stack.rerender(self.tde_cfg, self.dworld, st, respawned, self._fov)
                         else:
                             self._render1(self._obs, only=respawned)
-        finally:
-            self.tde_cfg.flags = full
         if bool(ev.active.any()):
             raise RuntimeError("evaluate(): envs still active after ceil(jobs / B) * max_steps steps")
         return EvalResult.from_records(ev.records().reshape(-1)[:len(jobs)], jobs)
 
     def _render1(self, out, only=None):
         """single-frame raster of every (or the masked) view into `out`"""
-        if self._h is not None:
-            self._h.render(out, self._res, self._res, self._fov, 1, None, 0, self._rflags, None, only)
-        else:
-            ops.render_ego(self.tde_cfg, self.dworld, self.state, self._res, self._res, self._fov, 1, out,
-                           flags=self._rflags, only=only)
+        self._h.render(out, self._res, self._res, self._fov, 1, None, 0, self._rflags, None, only)
 
     def get_info(self):
         """info schema of the reference (ref gym_env.py:419-437), one entry per env; a mapping whose tensors are formed
@@ -1573,13 +1519,9 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
         self._act_dev.copy_(self._act_pin, non_blocking=True)
         # terminal_observation needs the pre-reset frame: run the step without in-kernel reset, then re-spawn the
         # finished envs with the masked reset kernel
-        env.tde_cfg.flags &= ~_abi.F_AUTORESET
-        try:
+        with env._without_autoreset():
             obs, _, _, _, _ = env.step(self._act_dev)
-        finally:
-            if auto:
-                env.tde_cfg.flags |= _abi.F_AUTORESET
-        one_sync = auto and env.obs_mode == "state" and env._h is not None
+        one_sync = auto and env.obs_mode == "state" and env.binding == "ext"
         pre = None
         if one_sync:
             # compact observation: the observation the step left goes to an internal ring (the finished envs' terminal

@@ -181,14 +181,26 @@ class EvalBuffers:
         plan = torch.as_tensor(plan, dtype=torch.int32)
         if plan.dim() != 2 or plan.shape[0] < 1:
             raise ValueError(f"plan must be int32 [R >= 1, B], got {tuple(plan.shape)}")
-        self.R, self.B = int(plan.shape[0]), int(plan.shape[1])
-        self.plan = plan.to(device).contiguous()
-        self.round = torch.zeros(self.B, dtype=torch.int32, device=device)
-        self.active = torch.zeros(self.B, dtype=torch.uint8, device=device)
-        self.acc = torch.zeros((self.B, 48), dtype=torch.uint8, device=device)
-        self.results = torch.zeros((self.R, self.B, 48), dtype=torch.uint8, device=device)
-        self.struct = _abi.TdeEval(self.plan.data_ptr(), self.round.data_ptr(), self.active.data_ptr(), self.acc.data_ptr(),
-                                   self.results.data_ptr(), self.R, 0)
+        R, B = int(plan.shape[0]), int(plan.shape[1])
+        self._bind(plan.to(device).contiguous(), torch.zeros(B, dtype=torch.int32, device=device),
+                   torch.zeros(B, dtype=torch.uint8, device=device), torch.zeros((B, 48), dtype=torch.uint8, device=device),
+                   torch.zeros((R, B, 48), dtype=torch.uint8, device=device))
+
+    @classmethod
+    def over(cls, plan, round, active, acc, results):
+        """the EvalBuffers of five device arrays the caller already holds, laid out as __init__ makes them"""
+        if not torch.is_tensor(plan) or plan.dim() != 2 or plan.shape[0] < 1:
+            raise ValueError("plan must be int32 [R >= 1, B]")
+        ev = cls.__new__(cls)
+        ev._bind(plan, round, active, acc, results)
+        return ev
+
+    def _bind(self, plan, round, active, acc, results):
+        self.R, self.B = R, B = int(plan.shape[0]), int(plan.shape[1])
+        self.plan, self.round, self.active, self.acc, self.results = plan, round, active, acc, results
+        self.struct = _abi.TdeEval(_chk(plan, torch.int32, R * B, "plan"), _chk(round, torch.int32, B, "round"),
+                                   _chk(active, torch.uint8, B, "active"), _chk(acc, torch.uint8, B * 48, "acc"),
+                                   _chk(results, torch.uint8, R * B * 48, "results"), R, 0)
 
     def records(self):
         """the results on the host: a numpy record array [R, B] of _abi.EPISODE_RECORD_DTYPE (synchronises)"""
@@ -306,21 +318,26 @@ def state_obs(dworld, state, out=None):
 
 def vector_obs(cfg, dworld, state, vo, ray_dir=None, out=None, only=None):
     """tde_vector_obs: the vector observation of every env (or of those in `only`, uint8 [B] on the device; the other rows of `out`
-    are left as they are) -> float32 [B, D] on the device, D = vo.dim.  vo: config.VectorObs; ray_dir: its ray_directions() as a
-    float32 [n_rays, 2] device tensor (formed from vo when None).  Asynchronous."""
+    are left as they are) -> float32 [B, D] on the device, D = vo.dim.  vo: config.VectorObs (or the tde_vector_obs made of one:
+    `ray_dir` is then required and its address goes into the struct); ray_dir: its ray_directions() as a float32 [n_rays, 2] device
+    tensor (formed from vo when None).  Asynchronous."""
     from .config import check_vector_obs
 
-    vo = check_vector_obs(vo)
     L = _lib.load()
     dev = torch.device(state.device)
-    if ray_dir is None:
-        ray_dir = torch.from_numpy(vo.ray_directions()).to(dev)
+    if isinstance(vo, _abi.TdeVectorObs):
+        s, n_rays, dim = vo, vo.n_rays, _abi.VO_EGO + _abi.VO_NBR * vo.k_nbr + _abi.VO_RAY * vo.n_rays
+    else:
+        vo = check_vector_obs(vo)
+        n_rays, dim = vo.n_rays, vo.dim
+        s = _abi.TdeVectorObs(None, vo.k_neighbours, vo.n_rays, vo.neighbour_radius, vo.ray_range, vo.ray_step, 0)
+        if ray_dir is None:
+            ray_dir = torch.from_numpy(vo.ray_directions()).to(dev)
     if out is None:
-        out = torch.empty((state.B, vo.dim), dtype=torch.float32, device=dev)
-    pr = _chk(ray_dir, torch.float32, 2 * vo.n_rays, "ray_dir", dev)
-    po = _chk(out, torch.float32, state.B * vo.dim, "out", dev)
+        out = torch.empty((state.B, dim), dtype=torch.float32, device=dev)
+    s.ray_dir = _chk(ray_dir, torch.float32, 2 * n_rays, "ray_dir", dev)
+    po = _chk(out, torch.float32, state.B * dim, "out", dev)
     pm = _chk(only, torch.uint8, state.B, "only", dev, optional=True)
-    s = _abi.TdeVectorObs(pr, vo.k_neighbours, vo.n_rays, vo.neighbour_radius, vo.ray_range, vo.ray_step, 0)
     _lib.check(_call(dev, L.tde_vector_obs, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(s), pm, po,
                      _lib.current_stream(dev)), "tde_vector_obs")
     return out
@@ -659,6 +676,102 @@ def env_step_render(cfg, dworld, state, streams, action=None, out=None, H=64, W=
     return out
 
 
+class CtypesHandle:
+    """The ctypes binding in the shape of the C++ extension's EnvHandle (csrc/tde_torch_ext.cpp): one object per (cfg, dworld, state)
+    with EnvHandle's methods - same names, same positional arguments in the same order (tests/test_binding_parity_cpu.py) - so that a
+    caller holds either and launches the same way.  Every method that takes the config's `flags` stores it into `cfg` first (the
+    caller's own TdeConfig, not a copy; EnvHandle's `cfg_.flags = flags`) and then calls the function of this module that states the
+    launch.  `flags` of render() and `rflags` are the RENDER flags, as in EnvHandle.  step_render has no counterpart: it takes raw
+    stream handles, and env_step_render above is its ctypes form."""
+
+    def __init__(self, cfg, dworld, state):
+        self.cfg, self.dworld, self.state = cfg, dworld, state
+        self._planners = {}                       # the scalars of plan_action / score_plans* -> their _abi.TdePlanner
+
+    def _planner(self, *key):
+        """the tde_planner of (horizon, v_target, margin, w_progress, w_speed, w_steer, accel, steer), made once per value (the
+        plan-set judges do not read the lattice: theirs is empty, as EnvHandle's planner_of leaves it)"""
+        t = self._planners.get(key)
+        if t is None:
+            t = self._planners[key] = _abi.TdePlanner()
+            t.horizon, t.v_target, t.margin, t.w_progress, t.w_speed, t.w_steer, accel, steer = key
+            t.accel[:len(accel)], t.steer[:len(steer)] = accel, steer
+            t.n_a, t.n_s = len(accel), len(steer)
+        return t
+
+    def step(self, action, flags):
+        self.cfg.flags = flags
+        env_step(self.cfg, self.dworld, self.state, action)
+
+    def reset(self, mask, flags):
+        self.cfg.flags = flags
+        env_reset(self.cfg, self.dworld, self.state, mask)
+
+    def reset_to(self, scn, mask, flags):
+        self.cfg.flags = flags
+        env_reset_to(self.cfg, self.dworld, self.state, scn, mask)
+
+    def rollout(self, actions, reward, done, flags):
+        self.cfg.flags = flags
+        env_rollout(self.cfg, self.dworld, self.state, actions, reward, done)
+
+    def render(self, out, H, W, fov, n_stack, layers, phase, flags, fresh, only):
+        render_ego(self.cfg, self.dworld, self.state, H, W, fov, n_stack, out, layers, phase, flags, fresh, only)
+
+    def reset_render(self, mask, flags, out, H, W, fov, n_stack, layers, phase, rflags):
+        self.cfg.flags = flags
+        env_reset_render(self.cfg, self.dworld, self.state, mask, out, H, W, fov, n_stack, layers, phase, rflags)
+
+    def state_obs(self, out):
+        state_obs(self.dworld, self.state, out)
+
+    def vector_obs(self, out, ray_dir, k_nbr, n_rays, nbr_radius, ray_range, ray_step, only, flags):
+        self.cfg.flags = flags
+        vector_obs(self.cfg, self.dworld, self.state, _abi.TdeVectorObs(None, k_nbr, n_rays, nbr_radius, ray_range, ray_step, 0), ray_dir,
+                   out, only)
+
+    def plan_action(self, out, accel, steer, horizon, v_target, margin, w_progress, w_speed, w_steer, only, diag, flags):
+        self.cfg.flags = flags
+        pl = self._planner(horizon, v_target, margin, w_progress, w_speed, w_steer, tuple(accel), tuple(steer))
+        plan_action(self.cfg, self.dworld, self.state, pl, out, only, diag)
+
+    def score_plans(self, seq, knot_len, tail, cost, fail_step, horizon, v_target, margin, w_progress, w_speed, w_steer, only, action, diag,
+                    flags, forecast=None):
+        self.cfg.flags = flags
+        pl = self._planner(horizon, v_target, margin, w_progress, w_speed, w_steer, (), ())
+        score_plans(self.cfg, self.dworld, self.state, pl, seq, knot_len, tail, only, cost, fail_step, action, diag, forecast)
+
+    def score_plans_scene(self, seq, knot_len, tail, cost, fail_step, horizon, v_target, margin, w_progress, w_speed, w_steer, only, action,
+                          diag, flags):
+        self.cfg.flags = flags
+        pl = self._planner(horizon, v_target, margin, w_progress, w_speed, w_steer, (), ())
+        score_plans_scene(self.cfg, self.dworld, self.state, pl, seq, knot_len, tail, only, cost, fail_step, action, diag)
+
+    def forecast_agents(self, out, only, flags):
+        self.cfg.flags = flags
+        forecast_agents(self.cfg, self.dworld, self.state, out.shape[1], only, out)
+
+    def forecast_scene(self, out, ego_actions, only, flags):
+        self.cfg.flags = flags
+        forecast_scene(self.cfg, self.dworld, self.state, out.shape[1], ego_actions, only, out)
+
+    def ego_infractions(self, out, flags):
+        self.cfg.flags = flags
+        ego_infractions(self.cfg, self.dworld, self.state, out)
+
+    def post_step(self, magnitudes, flags):
+        self.cfg.flags = flags
+        env_post_step(self.cfg, self.dworld, self.state, magnitudes)
+
+    def eval_advance(self, plan, round, active, acc, results, flags):
+        self.cfg.flags = flags
+        eval_advance(self.cfg, self.dworld, self.state, EvalBuffers.over(plan, round, active, acc, results))
+
+    def near_field_spawn(self, nf, mask, flags):
+        self.cfg.flags = flags
+        near_field_spawn(self.cfg, self.dworld, self.state, nf, mask)
+
+
 class FrameStack:
     """Device-side VecFrameStack(n_stack, channels_order="first") (ref examples/rl_training.py:160) kept as a ring of
     one-byte-per-pixel layer planes: every call writes all n_stack frames of `obs` (oldest first) from the ring, so no
@@ -666,40 +779,34 @@ class FrameStack:
 
     def __init__(self, B, n_stack, H=64, W=64, device="cuda", flags=0, handle=None):
         self.n_stack, self.H, self.W, self.flags = int(n_stack), H, W, int(flags)
-        self.handle = handle                      # optional _ext.EnvHandle: launches go through the C++ extension
+        self.handle = handle                      # optional EnvHandle / CtypesHandle of (cfg, dworld, state): the launches go through it
         self.obs = torch.zeros((B, 3 * self.n_stack, H, W), dtype=torch.uint8, device=device)
         self.layers = torch.full((B, self.n_stack, H * W), _abi.LAYER_BLANK, dtype=torch.uint8, device=device)
         self.phase = 0
 
+    def _launcher(self, cfg, dworld, state):
+        """the handle the launches go through: the one given, else the ctypes binding of these arguments"""
+        return self.handle if self.handle is not None else CtypesHandle(cfg, dworld, state)
+
     def render(self, cfg, dworld, state, fov=35.0, fresh=None):
         """append the current frame of every view; `fresh` (uint8 [B]): views whose episode just (re)started - their
         older frames become blank, as VecFrameStack shows them after a reset"""
-        if self.handle is not None:
-            self.handle.render(self.obs, self.H, self.W, fov, self.n_stack, self.layers, self.phase, self.flags, fresh, None)
-        else:
-            render_ego(cfg, dworld, state, self.H, self.W, fov, self.n_stack, self.obs, self.layers, self.phase,
-                       self.flags, fresh=fresh)
+        self._launcher(cfg, dworld, state).render(self.obs, self.H, self.W, fov, self.n_stack, self.layers, self.phase, self.flags, fresh, None)
         self.phase = (self.phase + 1) % self.n_stack
         return self.obs
 
     def reset_rerender(self, cfg, dworld, state, mask, fov=35.0):
         """masked reset + rerender() of the same views as one C-ABI call (tde_env_reset_render)"""
         last = (self.phase - 1) % self.n_stack
-        if self.handle is not None:
-            self.handle.reset_render(mask, int(cfg.flags), self.obs, self.H, self.W, fov, self.n_stack, self.layers, last, self.flags)
-        else:
-            env_reset_render(cfg, dworld, state, mask, self.obs, self.H, self.W, fov, self.n_stack, self.layers, last, self.flags)
+        self._launcher(cfg, dworld, state).reset_render(mask, int(cfg.flags), self.obs, self.H, self.W, fov, self.n_stack, self.layers, last,
+                                                        self.flags)
         return self.obs
 
     def rerender(self, cfg, dworld, state, mask, fov=35.0):
         """re-render the NEWEST frame of the masked views in place (they were re-spawned after the last `render`) and
         blank their older frames; the other views and the ring position are untouched"""
         last = (self.phase - 1) % self.n_stack
-        if self.handle is not None:
-            self.handle.render(self.obs, self.H, self.W, fov, self.n_stack, self.layers, last, self.flags, mask, mask)
-        else:
-            render_ego(cfg, dworld, state, self.H, self.W, fov, self.n_stack, self.obs, self.layers, last, self.flags,
-                       fresh=mask, only=mask)
+        self._launcher(cfg, dworld, state).render(self.obs, self.H, self.W, fov, self.n_stack, self.layers, last, self.flags, mask, mask)
         return self.obs
 
     def clear(self, mask=None):
