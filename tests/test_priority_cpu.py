@@ -1,0 +1,382 @@
+"""CPU checks of prioritized replay (include/tde_priority.h, torchdriveenv_amd/replay.py): the header beside the others, the symbols of
+the built library, every host-side rejection of the entry points, of the ops wrappers and of the two new methods (all before any launch:
+no GPU needed), the Python statement (tests/priority_ref.py) against a brute-force walk and against valid_pairs()' rule, the weights,
+the distribution of the statement's draw, and the case table (tests/priority_cases.py) that tests/test_gpu_priority.py runs on the GPU,
+held to the conditions that make it mean something."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import priority_cases as K
+from tests import priority_ref as P
+from tests import ring_util as U
+from tests.test_replay_cpu import BAD_STRUCTS, _Host
+from torchdriveenv_amd import _abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- header, symbols, constants -----------------------------------------------------------------------------------------------------
+def test_header_compiles_beside_the_others_and_alone(tmp_path):
+    c, exe = tmp_path / "pr.c", str(tmp_path / "pr")
+    body = ("int main(void){return (TDE_ABI_VERSION - 14) | (TDE_REPLAY_VERSION - 1) | (TDE_ONPOLICY_VERSION - 1) | (TDE_TERMINAL_VERSION - 1) |"
+            " (TDE_NSTEP_VERSION - 1) | (TDE_PRIORITY_VERSION - 1) | (TDE_PRIORITY_ONE != 65536u) | (TDE_PRIORITY_QMAX != 268435456u) |"
+            " (TDE_PRIORITY_TAG != 0x5052u) | (sizeof(&tde_priority_sample) != sizeof(&tde_priority_version));}\n")
+    for order in (("tde_hip.h", "tde_replay.h", "tde_onpolicy.h", "tde_terminal.h", "tde_nstep.h", "tde_priority.h"),
+                  ("tde_priority.h", "tde_nstep.h", "tde_onpolicy.h", "tde_hip.h")):
+        c.write_text("".join(f'#include "{h}"\n' for h in order) + body)
+        subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
+        assert subprocess.run([exe]).returncode == 0
+    c.write_text('#include "tde_priority.h"\nint main(void){tde_replay r; tde_priority p; r.C = TDE_PRIORITY_VERSION; p.leaf = 0; p.sums = 0;'
+                 ' p.qmax = 0; return (r.C - 1) | (p.leaf != 0) | (sizeof(*p.sums) != 8) | (sizeof(*p.leaf) != 4) | (sizeof(*p.qmax) != 4);}\n')
+    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
+    assert subprocess.run([exe]).returncode == 0
+
+
+def test_header_lib_and_abi_agree():
+    from torchdriveenv_amd import _lib, build
+
+    text = open(os.path.join(ROOT, "include", "tde_priority.h")).read()
+    declared = re.findall(r"TDE_API\s+\w+\s+(tde_\w+)\(", text)
+    want = ["tde_priority_version", "tde_priority_words", "tde_priority_reset", "tde_priority_push", "tde_priority_update", "tde_priority_sample"]
+    assert sorted(declared) == sorted(_lib.PRIORITY_SYMBOLS) and _lib.PRIORITY_SYMBOLS == want
+    assert int(re.search(r"#define TDE_PRIORITY_VERSION (\d+)", text).group(1)) == _abi.TDE_PRIORITY_VERSION == 1
+    assert (_abi.PRIORITY_ONE, _abi.PRIORITY_QMAX, _abi.PRIORITY_TAG) == (1 << 16, 1 << 28, 0x5052) == (P.ONE, P.QMAX, P.TAG)
+    assert [n for n, _ in _abi.TdePriority._fields_] == re.findall(r"uint\d+_t \*(\w+);", text) == ["leaf", "sums", "qmax"]
+    L = _lib.load()
+    assert all(hasattr(L, s) for s in _lib.PRIORITY_SYMBOLS) and L.tde_priority_version() == 1
+    older = (set(_lib.SYMBOLS) | set(_lib.REPLAY_SYMBOLS) | set(_lib.ONPOLICY_SYMBOLS) | set(_lib.TERMINAL_SYMBOLS) | set(_lib.NSTEP_SYMBOLS))
+    assert not set(_lib.PRIORITY_SYMBOLS) & older
+    assert [len(getattr(L, s).argtypes) for s in _lib.PRIORITY_SYMBOLS] == [0, 2, 3, 6, 8, 10]
+    assert "tde_priority.hip" in build.UNITS and any(d.endswith("tde_priority.h") for d in build.DEPS)
+    # the older lists and versions are as they were
+    assert len(_lib.SYMBOLS) == 31 and _abi.TDE_ABI_VERSION == 14 == L.tde_abi_version()
+    assert L.tde_replay_version() == 1 and L.tde_onpolicy_version() == 1 and L.tde_terminal_version() == 1 and L.tde_nstep_version() == 1
+    assert (len(_lib.REPLAY_SYMBOLS), len(_lib.ONPOLICY_SYMBOLS), len(_lib.TERMINAL_SYMBOLS), len(_lib.NSTEP_SYMBOLS)) == (5, 3, 4, 2)
+
+
+def test_a_library_without_the_priority_symbols_is_a_stale_build(monkeypatch):
+    from torchdriveenv_amd import _lib
+
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "PRIORITY_SYMBOLS", _lib.PRIORITY_SYMBOLS + ["tde_priority_not_there"])
+    with pytest.raises(_lib.TdeError, match=r"lacks symbols \['tde_priority_not_there'\]: stale build\?"):
+        _lib.load()
+    monkeypatch.undo()
+    _lib.load()
+
+
+def test_words_is_the_inner_nodes_of_a_64_ary_tree():
+    from torchdriveenv_amd import _lib, ops
+
+    L = _lib.load()
+    for C_, B, want in ((4, 5, 1), (12, 5, 1), (2, 32, 1), (5, 13, 2 + 1), (40, 130, 82 + 2 + 1), (64, 64, 64 + 1), (64, 8192, 8192 + 128 + 2 + 1),
+                        (2, 2**30, 2**25 + 2**19 + 2**13 + 2**7 + 2 + 1), (2**31 - 1, 2**31 - 1, None)):
+        got = L.tde_priority_words(C_, B)
+        assert got == K.tree_words(C_ * B) == ops.priority_words(C_, B) and (want is None or got == want), (C_, B, got)
+    for C_, B in ((1, 5), (0, 5), (-1, 5), (4, 0), (4, -3)):
+        assert L.tde_priority_words(C_, B) == -1 and L.tde_last_error() == b"tde_priority_words: C must be >= 2 and B >= 1"
+        with pytest.raises(ValueError, match="tde_priority_words: C must be >= 2 and B >= 1"):
+            ops.priority_words(C_, B)
+
+
+# ---- every host-side refusal, before any launch -------------------------------------------------------------------------------------
+def test_entry_points_reject_bad_arguments_without_a_launch():
+    from torchdriveenv_amd import _lib
+
+    L = _lib.load()
+    h = _Host()                                             # C = 6, B = 3, n_stack = 3, plane = 64
+    ptr = lambda a: a.ctypes.data
+    buf = np.zeros(18 + 4, np.uint32)
+    leaf = buf[(-(ptr(buf) // 4)) % 4:][:18]                # 16-byte aligned
+    sums, qmax = np.zeros(1, np.uint64), np.zeros(1, np.uint32)
+    idx, p, q = np.zeros((4, 2), np.int32), np.zeros(5, np.float32), np.zeros(5, np.uint32)
+    assert ptr(leaf) % 16 == 0
+
+    def pr(**over):
+        a = {**dict(leaf=ptr(leaf), sums=ptr(sums), qmax=ptr(qmax)), **over}
+        return _abi.TdePriority(a["leaf"], a["sums"], a["qmax"])
+
+    def head(kw):
+        return (None if kw.pop("null_pr", False) else C.byref(kw.pop("pr", None) or pr()),
+                None if kw.pop("null_rp", False) else C.byref(kw.pop("rp", None) or h.rp()))
+
+    def reset(**kw):
+        return L.tde_priority_reset(*head(kw), None)
+
+    def push(w=3, first=0, count=4, **kw):
+        return L.tde_priority_push(*head(kw), w, first, count, None)
+
+    def update(first=0, count=4, N=4, idx_=ptr(idx), p_=ptr(p), **kw):
+        return L.tde_priority_update(*head(kw), first, count, N, idx_, p_, None)
+
+    def sample(first=0, count=4, N=4, idx_=ptr(idx), q_=ptr(q), **kw):
+        return L.tde_priority_sample(*head(kw), first, count, N, 1, 0, idx_, q_, None)
+
+    def refused(fn, fragment, **kw):
+        rc, err = fn(**kw), L.tde_last_error()
+        assert rc != 0 and fragment in err and err.startswith(b"tde_priority_" + fn.__name__.encode() + b": "), (fn.__name__, fragment, rc, err)
+
+    for fn in (reset, push, update, sample):
+        refused(fn, b"NULL argument", null_pr=True)
+        refused(fn, b"NULL argument", null_rp=True)
+        for over, fragment in BAD_STRUCTS:                  # the ring's own rules, as every replay entry point states them
+            refused(fn, fragment, rp=h.rp(**over))
+        for name in ("leaf", "sums", "qmax"):
+            refused(fn, b"a NULL array in the priorities", pr=pr(**{name: None}))
+        refused(fn, b"leaf must be 16-byte aligned", pr=pr(leaf=ptr(leaf) + 4))
+        refused(fn, b"sums 8-byte", pr=pr(sums=ptr(sums) + 4))
+        refused(fn, b"qmax 4-byte", pr=pr(qmax=ptr(qmax) + 2))
+    for fn in (push, update, sample):
+        refused(fn, b"count must be <= C - 1", count=6, **(dict(w=5) if fn is push else {}))
+        for first in (-1, 6):
+            refused(fn, b"first must be in [0, C)", first=first)
+    for w in (-1, 6):
+        refused(push, b"w must be in [0, C)", w=w)
+    for count in (0, -1):
+        refused(push, b"count must be >= 1", count=count)
+    for w, first, count in ((2, 0, 4), (4, 0, 4), (3, 1, 4), (0, 4, 2)):
+        refused(push, b"w must be the newest stored slot", w=w, first=first, count=count)
+    for fn in (update, sample):
+        for n in (0, -2):
+            refused(fn, b"N must be >= 1", N=n)
+        refused(fn, b"count must be >= 0", count=-1)
+    refused(update, b"NULL argument", idx_=None)
+    refused(update, b"NULL argument", p_=None)
+    refused(update, b"idx and p must be 4-byte aligned", idx_=ptr(idx) + 2)
+    refused(update, b"idx and p must be 4-byte aligned", p_=ptr(p) + 1)
+    refused(sample, b"a NULL output", idx_=None)
+    refused(sample, b"a NULL output", q_=None)
+    refused(sample, b"idx and q must be 4-byte aligned", idx_=ptr(idx) + 2)
+    refused(sample, b"idx and q must be 4-byte aligned", q_=ptr(q) + 2)
+    # nothing was written by any of the calls above
+    for a in (h.frames, h.action, h.reward, h.done, h.age, buf, sums, qmax, idx, p, q):
+        assert not a.view(np.uint8).any()
+
+
+def test_ops_wrappers_reject_host_tensors_and_bad_arguments():
+    import torch
+
+    from torchdriveenv_amd import ops
+
+    z = torch.zeros
+    rp, pr = _abi.TdeReplay(6, 4, 3, 64, 0, None, None, None, None, None), _abi.TdePriority(None, None, None)
+    with pytest.raises(ValueError, match="leaf must be torch.int32"):
+        ops.priority_struct(rp, z((6, 4), dtype=torch.int64), z(1, dtype=torch.int64), z(1, dtype=torch.int32))
+    with pytest.raises(ValueError, match="leaf must live on a HIP device"):
+        ops.priority_struct(rp, z((6, 4), dtype=torch.int32), z(1, dtype=torch.int64), z(1, dtype=torch.int32))
+    with pytest.raises(ValueError, match="leaf is required"):
+        ops.priority_struct(rp, None, None, None)
+    with pytest.raises(ValueError, match="n must be >= 1"):
+        ops.priority_sample(pr, rp, "cuda:0", 0, 4, 0, None, None)
+    with pytest.raises(ValueError, match="idx must live on a HIP device"):
+        ops.priority_sample(pr, rp, "cuda:0", 0, 4, 2, z((2, 2), dtype=torch.int32), z(2, dtype=torch.int32))
+    with pytest.raises(ValueError, match="idx is required"):
+        ops.priority_sample(pr, rp, "cuda:0", 0, 4, 2, None, None)
+    with pytest.raises(ValueError, match="p must live on a HIP device"):
+        ops.priority_update(pr, rp, "cuda:0", 0, 4, z((2, 2), dtype=torch.int32), z(2))
+    with pytest.raises(ValueError, match="p must be torch.float32"):
+        ops.priority_update(pr, rp, "cuda:0", 0, 4, z((2, 2), dtype=torch.int32), z(2, dtype=torch.float64))
+    with pytest.raises(ValueError, match="p is required"):
+        ops.priority_update(pr, rp, "cuda:0", 0, 4, None, None)
+
+
+def test_the_new_methods_refuse_without_a_gpu():
+    import inspect
+
+    import torch
+
+    from torchdriveenv_amd.config import Prioritized, check_prioritized
+    from torchdriveenv_amd.env import BatchedWaypointEnv
+    from torchdriveenv_amd.replay import NStepSamples, PrioritizedSamples, ReplayBuffer
+
+    sig = inspect.signature(BatchedWaypointEnv.replay_buffer).parameters
+    assert list(sig) == ["self", "capacity_steps", "seed", "terminal_per_step", "prioritized"] and sig["prioritized"].default is None
+    sig = inspect.signature(ReplayBuffer.sample_prioritized).parameters
+    assert list(sig) == ["self", "n", "n_steps", "gamma", "beta"]
+    assert (sig["n_steps"].default, sig["gamma"].default, sig["beta"].default) == (1, 0.99, None)
+    assert list(inspect.signature(ReplayBuffer.update_priorities).parameters) == ["self", "indices", "td_errors"]
+    assert PrioritizedSamples._fields == NStepSamples._fields + ("priorities", "weights")
+    assert Prioritized() == Prioritized(alpha=0.6, beta=0.4, eps=1e-6) == check_prioritized({})
+    for bad in (dict(alpha=-0.1), dict(alpha=1.5), dict(alpha=float("nan")), dict(beta=-0.1), dict(beta=2), dict(eps=0), dict(eps=-1),
+                dict(eps=float("inf")), dict(eps=float("nan"))):
+        with pytest.raises(ValueError, match="prioritized: "):
+            check_prioritized(bad)
+    with pytest.raises(TypeError, match="must be a Prioritized"):
+        check_prioritized(0.6)
+    # a buffer in host memory: every refusal comes before the first device call
+    buf = ReplayBuffer.__new__(ReplayBuffer)
+    buf.dev, buf.C, buf.B, buf.n_stack, buf.first, buf.count, buf.draws = torch.device("cpu"), 6, 3, 3, 1, 4, 5
+    buf.tstruct = None
+    with pytest.raises(ValueError, match=r"sample_prioritized\(\) needs a buffer built with prioritized=Prioritized"):
+        buf.sample_prioritized(4)
+    buf.pstruct = None
+    with pytest.raises(ValueError, match=r"update_priorities\(\) needs a buffer built with prioritized=Prioritized"):
+        buf.update_priorities([(1, 0)], [0.5])
+    assert buf._tensors == ("frames", "action", "reward", "done", "age")
+    buf.pstruct, buf.prioritized = object(), Prioritized()
+    assert buf._tensors[-2:] == ("leaf", "qmax")
+    for n in (0, -1, None):
+        with pytest.raises(ValueError, match="n must be >= 1"):
+            buf.sample_prioritized(n)
+    for n_steps in (0, -1, 65):
+        with pytest.raises(ValueError, match=r"n_steps must be in \[1, 64\]"):
+            buf.sample_prioritized(4, n_steps)
+    for gamma in (-0.01, 1.01, float("nan")):
+        with pytest.raises(ValueError, match=r"gamma must be in \[0, 1\]"):
+            buf.sample_prioritized(4, 3, gamma)
+    for beta in (-0.01, 1.01, float("nan")):
+        with pytest.raises(ValueError, match=r"beta must be in \[0, 1\]"):
+            buf.sample_prioritized(4, 3, 0.99, beta)
+    buf.count = 0
+    with pytest.raises(ValueError, match="holds no transition yet"):
+        buf.sample_prioritized(4)
+    assert buf.draws == 5                                   # a refused call draws nothing
+    with pytest.raises(ValueError, match="at least one"):
+        buf.update_priorities(torch.zeros((0, 2), dtype=torch.int32), torch.zeros(0))
+    with pytest.raises(ValueError, match="td_errors must hold 2 values"):
+        buf.update_priorities([(1, 0), (2, 1)], [0.5, 0.25, 0.125])
+    # a state with priorities and a buffer without them, and the reverse
+    for has, state in ((None, {"leaf": 0}), (object(), {})):
+        buf.pstruct = has
+        with pytest.raises(ValueError, match="priorities, this buffer is with" + ("out" if has is None else " ")):
+            buf.load_state_dict(state)
+
+
+# ---- the statement -------------------------------------------------------------------------------------------------------------------
+def test_quantisation_edges():
+    for p, want in K.QUANT_EDGES:
+        assert int(P.quantise(np.array([p]))[0]) == want, (p, want)
+    assert {1, 2, P.ONE, P.QMAX} <= {w for _, w in K.QUANT_EDGES}
+    q = np.arange(1, 1 << 12, dtype=np.int64) * 4097        # the scaling is exact: q / 65536 comes back as q
+    assert np.array_equal(P.quantise(q.astype(np.float32) / np.float32(65536)), q)
+
+
+def test_pick_equals_a_linear_walk():
+    rng = np.random.default_rng(3)
+    for n in (1, 5, 64, 65, 300):
+        leaves = (rng.integers(0, 1 << 20, n) * (rng.uniform(size=n) < 0.6)).astype(np.uint32)
+        leaves[rng.integers(n)] = P.QMAX
+        T = int(leaves.astype(np.int64).sum())
+        edges = np.cumsum(leaves.astype(np.int64))
+        us = sorted({0, T - 1, *[int(e) for e in edges if e < T], *[int(e) - 1 for e in edges if e >= 1],
+                     *rng.integers(0, T, 50).tolist()})
+        got = P.pick(leaves, us)
+        for u, l in zip(us, got):
+            acc, walk = 0, None
+            for j, v in enumerate(leaves):
+                acc += int(v)
+                if u < acc:
+                    walk = j
+                    break
+            assert walk == l and leaves[l] > 0, (n, u, l, walk)
+
+
+def test_strata_partition_the_total_exactly():
+    for T, n in ((55, 55), (55, 11), (55, 256), (10**12 + 7, 256), (2**28 + 54, 7), (3, 1), (2**40, 4096)):
+        us = P.strata(T, n, K.SEED, K.BIG_DRAW)
+        base, rem = divmod(T, n)
+        assert len(us) == n and all(0 <= u < T for u in us)
+        if base:
+            lo = [i * base + min(i, rem) for i in range(n)] + [T]
+            assert all(lo[i] <= us[i] < lo[i + 1] for i in range(n)) and lo[n - 1] + base + (n - 1 < rem) == T
+    assert P.strata(55, 7, K.SEED, 0) != P.strata(55, 7, K.SEED, 2**32) != P.strata(55, 7, K.SEED + 1, 2**32)
+
+
+def test_invariant_is_valid_pairs_rule_through_two_wraps():
+    for n_stack in (1, 3):
+        ring = U.HandRing(4, 5, n_stack, plane=16, seed=5)
+        hp = K.HandPriorities(ring)
+        ring.begin(ring.rows())
+        hp.reset()
+        seen = set()
+        for t in range(2 * 4 + 3):
+            if t == 5:
+                hp.begin(mask=[1, 0, 1, 0, 0])              # cuts two envs; no priority changes
+            hp.step((ring.rng.uniform(size=5) < 0.3) * ring.rng.integers(1, 4, 5))
+            pairs = {tuple(x) for x in ring.ref.valid_pairs().tolist()}
+            assert pairs == {tuple(x) for x in np.argwhere(hp.ref.leaf != 0).tolist()} == {tuple(x) for x in np.argwhere(P.valid_mask(ring.ref)).tolist()}
+            seen.add(len(pairs) == ring.count * 5)
+        assert seen == ({True} if n_stack == 1 else {True, False})      # with a stack, some stored pairs are not drawable
+
+
+def test_weights_against_float64():
+    import torch
+
+    from torchdriveenv_amd.replay import priority_weights
+
+    rng = np.random.default_rng(9)
+    q = np.concatenate([rng.integers(1, P.QMAX + 1, 200), [1, P.QMAX, P.ONE, 0, 0, P.QMAX - 1]]).astype(np.int32)
+    for beta in (0.0, 0.4, 0.5, 1.0):
+        got = priority_weights(torch.from_numpy(q), beta)
+        want = P.weights(q, beta)
+        assert got.dtype is torch.float32 and np.allclose(got.numpy().astype(np.float64), want, rtol=1e-6, atol=0)
+        assert (got.numpy()[q == 0] == 0).all() and got.max() == 1.0
+    assert (priority_weights(torch.zeros(4, dtype=torch.int32), 0.4) == 0).all()
+
+
+def test_distribution_of_the_statements_draw():
+    """fixed priorities, 100 draws of 256: every expected count is at least 500, every observed one within 5 sqrt(E) of it (a binomial
+    five-sigma bound; stratification only tightens it)"""
+    ring = U.HandRing(4, 5, 1, plane=16, seed=1)
+    hp = K.HandPriorities(ring)
+    ring.begin(ring.rows())
+    hp.reset()
+    for _ in range(3):
+        hp.step()
+    pairs = hp.set_all(np.array([1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 2, 2, 3, 3, 4]) * 1000)
+    T, draws, n = hp.ref.total, 100, 256
+    expect = {tuple(pr): draws * n * int(hp.ref.leaf[pr[0], pr[1]]) / T for pr in pairs.tolist()}
+    assert min(expect.values()) >= 500
+    count = dict.fromkeys(expect, 0)
+    for d in range(draws):
+        idx, q, _ = hp.ref.draw(K.SEED, d, n)
+        for s, e in idx.tolist():
+            count[(s, e)] += 1
+    for k, E in expect.items():
+        assert abs(count[k] - E) <= 5 * np.sqrt(E), (k, count[k], E)
+
+
+# ---- the case table means something -----------------------------------------------------------------------------------------------------
+def test_case_table_hits_edges_and_zero_blocks():
+    assert K.SHAPES == {"one_level": dict(C=4, B=5), "partial_block": dict(C=12, B=5), "three_levels": dict(C=40, B=130)}
+    assert [K.tree_words(c["C"] * c["B"]) for c in K.SHAPES.values()] == [1, 1, 82 + 2 + 1] and 5200 % 64 != 0
+    on_edge = past_zero = base_zero = one_sample = wide_draw = qmax_pick = 0
+    for shape in K.SHAPES:
+        for n_stack in (1, 3):
+            hp = K.filled(shape, n_stack)
+            g = hp.ring.ref
+            assert g.count == g.C - 1 and 0 < g.w < g.C - 1             # wrapped: the open slot lies between live slots
+            assert (n_stack == 1) == bool(P.valid_mask(g).sum() == g.count * g.B)
+            for kind in K.KINDS:
+                pairs = hp.set_all(K.priorities_of(kind, hp))
+                edges = set(np.cumsum(hp.ref.leaf.reshape(-1).astype(np.int64)).tolist()) | {0}
+                for n, seed, draw in K.draw_settings(kind, len(pairs)):
+                    idx, q, us = hp.draw(n, seed, draw)
+                    T = hp.ref.total
+                    assert (q > 0).all() and {tuple(x) for x in idx.tolist()} <= {tuple(x) for x in pairs.tolist()}
+                    on_edge += sum(u in edges for u in us)
+                    past_zero += K.past_zero_block(hp.ref.leaf, idx, g.B)
+                    base_zero += n > T
+                    one_sample += n == 1
+                    wide_draw += draw >= 2**32
+                    qmax_pick += int((q == P.QMAX).sum()) if kind == "qmax_among_ones" else 0
+    assert on_edge >= 100 and past_zero >= 10 and base_zero >= 6 and one_sample and wide_draw and qmax_pick >= 1000
+    hp = K.filled("three_levels", 3)
+    flat = hp.ref.leaf.reshape(-1)
+    assert any(not flat[64 * b:64 * b + 64].any() for b in range(1, 80)) and (flat == 0).sum() > 130      # a zero block, zeros besides
+
+
+def test_case_table_update_names_every_kind_of_ignored_pair():
+    hp = K.filled("partial_block", 3)
+    g = hp.ring.ref
+    ok = P.valid_mask(g)
+    stored_not_whole = [(s, e) for s in range(g.C) for e in range(g.B) if (s - g.first) % g.C < g.count and not ok[s, e]]
+    assert stored_not_whole and not ok[g.w].any()
+    before = hp.ref.leaf.copy()
+    bad = [(-1, 0), (g.C, 0), (0, -1), (0, g.B), (U.INT32_MIN, 0), (0, U.INT32_MAX), (g.w, 2), stored_not_whole[0]]
+    assert hp.update(bad, np.full(len(bad), 3.0, np.float32)) == 0 and np.array_equal(hp.ref.leaf, before) and hp.ref.qmax == P.ONE

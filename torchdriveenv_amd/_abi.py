@@ -209,6 +209,15 @@ TERMINAL_HAS = 0x40              # in the done byte a terminal sample returns: n
 TDE_NSTEP_VERSION = 1            # include/tde_nstep.h
 NSTEP_MAX = 64                   # the longest look-ahead of an n-step sample
 
+
+class TdePriority(C.Structure):
+    """tde_priority (include/tde_priority.h): the integer priorities beside a replay ring; device addresses"""
+    _fields_ = [("leaf", _p), ("sums", _p), ("qmax", _p)]
+
+
+TDE_PRIORITY_VERSION = 1         # include/tde_priority.h
+PRIORITY_ONE, PRIORITY_QMAX, PRIORITY_TAG = 1 << 16, 1 << 28, 0x5052      # q of priority 1.0, the largest q, the draws' Philox tag
+
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7
 RENDER_LEFT_HANDED, RENDER_PLAIN_EGO = 1 << 0, 1 << 1

@@ -19,6 +19,9 @@ ONPOLICY_SYMBOLS = ["tde_onpolicy_version", "tde_gae", "tde_onpolicy_gather"]
 TERMINAL_SYMBOLS = ["tde_terminal_version", "tde_terminal_stash", "tde_terminal_push", "tde_terminal_sample"]
 # every symbol include/tde_nstep.h declares (additive over the terminal header: TDE_NSTEP_VERSION)
 NSTEP_SYMBOLS = ["tde_nstep_version", "tde_nstep_sample"]
+# every symbol include/tde_priority.h declares (additive over the replay header: TDE_PRIORITY_VERSION)
+PRIORITY_SYMBOLS = ["tde_priority_version", "tde_priority_words", "tde_priority_reset", "tde_priority_push", "tde_priority_update",
+                    "tde_priority_sample"]
 
 _lib = None
 
@@ -125,6 +128,20 @@ def load():
     L.tde_nstep_sample.argtypes = [rpp, tmp, i32, i32, i32, vp, u64, u64, i32, f32] + [vp] * 8 + [vp]
     for s in NSTEP_SYMBOLS:
         getattr(L, s).restype = C.c_int
+    missing = [s for s in PRIORITY_SYMBOLS if not hasattr(L, s)]
+    if missing:
+        raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")
+    if L.tde_priority_version() != _abi.TDE_PRIORITY_VERSION:
+        raise TdeError(f"priority version mismatch: library {L.tde_priority_version()} vs python {_abi.TDE_PRIORITY_VERSION}")
+    prp = C.POINTER(_abi.TdePriority)
+    L.tde_priority_version.argtypes = []
+    L.tde_priority_words.argtypes = [i32, i32]
+    L.tde_priority_reset.argtypes = [prp, rpp, vp]
+    L.tde_priority_push.argtypes = [prp, rpp, i32, i32, i32, vp]
+    L.tde_priority_update.argtypes = [prp, rpp, i32, i32, i32, vp, vp, vp]
+    L.tde_priority_sample.argtypes = [prp, rpp, i32, i32, i32, u64, u64, vp, vp, vp]
+    for s in PRIORITY_SYMBOLS:
+        getattr(L, s).restype = C.c_int64 if s == "tde_priority_words" else C.c_int
     _lib = L
     return L
 

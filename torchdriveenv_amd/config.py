@@ -414,3 +414,32 @@ def check_planner(pl):
     if pl.predict not in PLANNER_PREDICT:
         raise ValueError(f"planner: predict must be one of {PLANNER_PREDICT}, got {pl.predict!r}")
     return pl
+
+
+@dataclass
+class Prioritized:
+    """env.replay_buffer(..., prioritized=Prioritized()): prioritized experience replay (Schaul et al.; include/tde_priority.h).  A
+    transition is drawn with probability proportional to its priority p = (|td_error| + eps) ** alpha, kept on the device as an integer
+    (16.16 fixed point, so every sum is exact), and new transitions enter with the largest priority seen.
+      alpha   how much the TD error decides, in [0, 1]: 0 is the uniform draw over valid_pairs()
+      beta    the exponent of the importance weights sample_prioritized() returns, in [0, 1] (its own `beta` argument overrides it: a
+              learner anneals it to 1)
+      eps     added to |td_error|, > 0: no transition becomes undrawable"""
+    alpha: float = 0.6
+    beta: float = 0.4
+    eps: float = 1e-6
+
+
+def check_prioritized(pz):
+    """validate a Prioritized (a dict is accepted as Prioritized(**dict)); returns it"""
+    if isinstance(pz, dict):
+        pz = Prioritized(**pz)
+    if not isinstance(pz, Prioritized):
+        raise TypeError("prioritized must be a Prioritized (or a dict of its fields)")
+    if not 0.0 <= float(pz.alpha) <= 1.0:
+        raise ValueError(f"prioritized: alpha must be in [0, 1], got {pz.alpha}")
+    if not 0.0 <= float(pz.beta) <= 1.0:
+        raise ValueError(f"prioritized: beta must be in [0, 1], got {pz.beta}")
+    if not 0.0 < float(pz.eps) < float("inf"):
+        raise ValueError(f"prioritized: eps must be finite and > 0, got {pz.eps}")
+    return pz

@@ -1,4 +1,4 @@
-// tde_ring.h — what the units over the replay ring (tde_replay.hip, tde_onpolicy.hip, tde_terminal.hip, tde_nstep.hip) share: what a learner
+// tde_ring.h — what the units over the replay ring (tde_replay.hip, tde_onpolicy.hip, tde_terminal.hip, tde_nstep.hip, tde_priority.hip) share: what a learner
 // sees of a stored transition, stated once.
 //   * device side: the "ended" mask, the ring's wrap, the row copy, the pick of a sample (the draw, and the validity rule of a given
 //     pair), the frame rule, the expansion of a layer plane into frames of obs / next_obs, the scalars of a sampled transition;
@@ -81,6 +81,10 @@ TDE_DEV RingPick ring_pick(const SampleArgs &s, int i)
 // the frame rule: the frame `d` slots behind a slot (of that age, `off` slots after `first`) is shown iff it belongs to the episode
 // and has not been overwritten (it lies at or behind `first`)
 TDE_DEV bool ring_shown(int d, int age, int off) { return d <= age && d <= off; }
+
+// the stack rule: a stored slot of that age, `off` slots after `first`, still has every frame of its stack in the ring (ring_shown for
+// each d < n_stack at once) - what makes a stored pair one of valid_pairs()
+TDE_DEV bool ring_whole(int age, int n_stack, int off) { return min(age, n_stack - 1) <= off; }
 
 // a frame of obs / next_obs as one wavefront sees it: whether it writes the frame at all, and the plane or zeros (show implies write)
 struct RingFrame {

@@ -1286,14 +1286,17 @@ class BatchedWaypointEnv:
             else:
                 self.state.arrays[k].copy_(v)
 
-    def replay_buffer(self, capacity_steps, seed=None, terminal_per_step=None):
+    def replay_buffer(self, capacity_steps, seed=None, terminal_per_step=None, prioritized=None):
         """a replay.ReplayBuffer of `capacity_steps` time slots bound to this env (index draws seeded by `seed`; None: the env's seed).
         On a terminal_obs env the buffer also keeps up to `terminal_per_step` terminal frames per step (None: max(1, num_envs // 8));
         that pool costs capacity_steps * terminal_per_step * (H * W, or 4 * D) bytes beside the ring's capacity_steps * num_envs * ... -
-        an eighth more by default - plus 4 * capacity_steps * num_envs bytes of references.  Without the option it must be None."""
+        an eighth more by default - plus 4 * capacity_steps * num_envs bytes of references.  Without the option it must be None.
+        prioritized: a config.Prioritized - the buffer keeps an integer priority per transition (4 bytes, and an eighth of a byte of
+        sums) and offers sample_prioritized() / update_priorities(); None: nothing is allocated and nothing about the buffer changes."""
         from .replay import ReplayBuffer
 
-        return ReplayBuffer(self, capacity_steps, seed=self.seed_value if seed is None else seed, terminal_per_step=terminal_per_step)
+        return ReplayBuffer(self, capacity_steps, seed=self.seed_value if seed is None else seed, terminal_per_step=terminal_per_step,
+                            prioritized=prioritized)
 
     def rollout_buffer(self, n_steps, gamma=0.99, gae_lambda=0.95, seed=None, terminal_per_step=None):
         """an onpolicy.RolloutBuffer of `n_steps` steps bound to this env (minibatch permutations seeded by `seed`; None: the env's seed;

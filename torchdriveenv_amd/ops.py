@@ -1035,3 +1035,60 @@ def nstep_sample(rp, tm, dev, first, count, n, n_steps, gamma, out, idx_in=None,
                      int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), n_steps, gamma, *outs, pg, ps, _lib.current_stream(dev)),
                "tde_nstep_sample")
     return out
+
+
+# ---- prioritized replay over the ring (include/tde_priority.h) ---------------------------------------------------------------------------
+def priority_words(C_, B):
+    """tde_priority_words: int64 words of `sums` a ring of C_ slots and B envs needs (host only)"""
+    n = _lib.load().tde_priority_words(int(C_), int(B))
+    if n < 0:
+        raise ValueError(_lib.load().tde_last_error().decode())
+    return int(n)
+
+
+def priority_struct(rp, leaf, sums, qmax):
+    """_abi.TdePriority over the caller's tensors beside the ring `rp`: leaf int32 [C, B] (q < 2^28: the bits of the header's uint32),
+    sums int64 [priority_words(C, B)], qmax int32 [1], on the ring's HIP device"""
+    dev = leaf.device if torch.is_tensor(leaf) else None
+    return _abi.TdePriority(_chk(leaf, torch.int32, rp.C * rp.B, "leaf", dev), _chk(sums, torch.int64, priority_words(rp.C, rp.B), "sums", dev),
+                            _chk(qmax, torch.int32, 1, "qmax", dev))
+
+
+def priority_reset(pr, rp, dev):
+    """tde_priority_reset on the current stream: every leaf and sum zero, qmax = PRIORITY_ONE"""
+    dev = torch.device(dev)
+    _lib.check(_call(dev, _lib.load().tde_priority_reset, C.byref(pr), C.byref(rp), _lib.current_stream(dev)), "tde_priority_reset")
+
+
+def priority_push(pr, rp, dev, w, first, count):
+    """tde_priority_push on the current stream, after replay_push filled slot `w`: first and count are the host's values after it
+    advanced.  The pushed pairs enter with qmax, the open slot and the stacks the ring just overwrote leave"""
+    dev = torch.device(dev)
+    _lib.check(_call(dev, _lib.load().tde_priority_push, C.byref(pr), C.byref(rp), int(w), int(first), int(count), _lib.current_stream(dev)),
+               "tde_priority_push")
+
+
+def priority_update(pr, rp, dev, first, count, idx, p):
+    """tde_priority_update on the current stream: the pairs idx int32 [n, 2] (slot, env) take the priorities p float32 [n] (quantised to
+    16.16 fixed point, the largest where a pair is named twice); pairs that are no longer valid_pairs() are ignored"""
+    dev = torch.device(dev)
+    pp = _chk(p, torch.float32, None, "p", dev)
+    n = p.numel()
+    if n < 1:
+        raise ValueError("p must hold at least one priority")
+    pi = _chk(idx, torch.int32, 2 * n, "idx", dev)
+    _lib.check(_call(dev, _lib.load().tde_priority_update, C.byref(pr), C.byref(rp), int(first), int(count), n, pi, pp,
+                     _lib.current_stream(dev)), "tde_priority_update")
+
+
+def priority_sample(pr, rp, dev, first, count, n, idx, q, seed=0, draw=0):
+    """tde_priority_sample on the current stream: `n` pairs drawn in proportion to their priorities from (seed, draw) into idx int32
+    [n, 2] (slot, env) and their priorities into q int32 [n]; (-1, -1) and 0 when nothing is drawable"""
+    dev = torch.device(dev)
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    pi, pq = _chk(idx, torch.int32, 2 * n, "idx", dev), _chk(q, torch.int32, n, "q", dev)
+    _lib.check(_call(dev, _lib.load().tde_priority_sample, C.byref(pr), C.byref(rp), int(first), int(count), n, int(seed) & (2**64 - 1),
+                     int(draw) & (2**64 - 1), pi, pq, _lib.current_stream(dev)), "tde_priority_sample")
+    return idx, q

@@ -19,12 +19,20 @@ and the learner's target is rewards + discounts * bootstrap * Q(next_observation
 On an env built with terminal_obs=True the buffer also keeps the terminal frames (include/tde_terminal.h, csrc/tde_terminal.hip): a
 transition that ended its episode then returns the observation the env showed before it was re-spawned as `next_observations`, and
 `batch.bootstrap` says where the learner should use it.
+
+With prioritized=Prioritized(...) the buffer keeps an integer priority per stored transition on the device (include/tde_priority.h,
+csrc/tde_priority.hip):
+
+    buf = env.replay_buffer(capacity_steps=128, prioritized=Prioritized(alpha=0.6, beta=0.4))
+    batch = buf.sample_prioritized(256, n_steps=3)             # NStepSamples' fields, and priorities, weights
+    buf.update_priorities(batch.indices, td_errors)            # p = (|td| + eps) ** alpha
 """
 from collections import namedtuple
 
 import torch
 
 from . import _abi, ops
+from .config import check_prioritized
 
 
 class ReplaySamples(namedtuple("ReplaySamples", ["observations", "actions", "next_observations", "dones", "rewards", "indices"])):
@@ -57,6 +65,24 @@ class NStepSamples(namedtuple("NStepSamples", ReplaySamples._fields + ("discount
     bootstrap = ReplaySamples.bootstrap
 
 
+class PrioritizedSamples(namedtuple("PrioritizedSamples", NStepSamples._fields + ("priorities", "weights"))):
+    """NStepSamples of pairs drawn in proportion to their priorities: priorities int32 [n] is the integer priority q of each pick
+    (16.16 fixed point; 0 for a row that picked nothing) and weights float32 [n] the importance weight (min_j q_j / q_i) ** beta -
+    (N * P(i)) ** -beta normalised by the batch's largest; a row with q = 0 has weight 0."""
+    __slots__ = ()
+    terminal = ReplaySamples.terminal
+    bootstrap = ReplaySamples.bootstrap
+
+
+def priority_weights(q, beta):
+    """float32 [n] importance weights of the integer priorities q [n]: (min of the nonzero q / q) ** beta, 0 where q is 0.  In float64
+    (a q of 2^28 is not a float32), rounded once."""
+    live = q > 0
+    qd = q.to(torch.float64)
+    smallest = torch.where(live, qd, torch.full_like(qd, float("inf"))).min()
+    return torch.where(live, (smallest / qd.clamp(min=1.0)) ** float(beta), torch.zeros_like(qd)).to(torch.float32)
+
+
 class ReplayBuffer:
     """A ring of `capacity_steps` time slots, one entry per env and slot, bound to a BatchedWaypointEnv (auto_reset=True, with_info=True).
 
@@ -81,10 +107,16 @@ class ReplayBuffer:
     those of `observations` moved down by one - with TERMINAL_HAS set in dones, also when the transition was cut as well.
     `.terminal` keeps its meaning; `.bootstrap` is where the learner should use next_observations.  The pool costs capacity_steps *
     terminal_per_step * (H * W or 4 * D) bytes (default terminal_per_step = max(1, num_envs // 8): an eighth of the ring) plus
-    4 * capacity_steps * num_envs bytes of references."""
+    4 * capacity_steps * num_envs bytes of references.
 
-    def __init__(self, env, capacity_steps, seed=0, terminal_per_step=None):
+    With prioritized=Prioritized(alpha, beta, eps): push() also gives the new transitions the largest priority seen and retires the
+    priorities of the transitions the ring overwrote (tde_priority_push), sample_prioritized() draws in proportion to the priorities
+    and update_priorities() takes the learner's TD errors.  sample() and sample_nstep() stay the uniform draws they are.  It costs 4
+    bytes per transition and an eighth of a byte of sums."""
+
+    def __init__(self, env, capacity_steps, seed=0, terminal_per_step=None, prioritized=None):
         C_ = int(capacity_steps)
+        self.prioritized = check_prioritized(prioritized) if prioritized is not None else None
         self.terminal_obs = bool(getattr(env, "terminal_obs", False))
         if terminal_per_step is not None and not self.terminal_obs:
             raise ValueError("terminal_per_step needs an env built with terminal_obs=True")
@@ -125,10 +157,17 @@ class ReplayBuffer:
                          torch.zeros((C_, self.M, self.D), dtype=torch.float32, device=self.dev))
             self.ref = torch.full((C_, self.B), -1, dtype=torch.int32, device=self.dev)
             self.tstruct = ops.terminal_struct(self.struct, self.M, self.pool, self.ref)
+        self.leaf, self.sums, self.qmax, self.pstruct = None, None, None, None
+        if self.prioritized is not None:
+            self.leaf = torch.zeros((C_, self.B), dtype=torch.int32, device=self.dev)
+            self.sums = torch.zeros(ops.priority_words(C_, self.B), dtype=torch.int64, device=self.dev)
+            self.qmax = torch.full((1,), _abi.PRIORITY_ONE, dtype=torch.int32, device=self.dev)
+            self.pstruct = ops.priority_struct(self.struct, self.leaf, self.sums, self.qmax)
         self.first = self.w = self.count = self.draws = 0
         self._begun = False
         self._out = {}
         self._nstep_out = {}
+        self._prio_out = {}
 
     # ---- bookkeeping --------------------------------------------------------------------------------------------------------
     def __len__(self):
@@ -166,6 +205,8 @@ class ReplayBuffer:
             mask = torch.ones(self.B, dtype=torch.uint8, device=self.dev)
         src, off, stride = self._source()
         ops.replay_begin(self.struct, self.dev, self.w, src, off, stride, mask)
+        if self.pstruct is not None and not self._begun:
+            ops.priority_reset(self.pstruct, self.struct, self.dev)
         self._begun = True
 
     def push(self, actions):
@@ -187,6 +228,8 @@ class ReplayBuffer:
             self.first = (self.first + 1) % self.C           # the ring is full: the oldest step's frame was just overwritten
         else:
             self.count += 1
+        if self.pstruct is not None:
+            ops.priority_push(self.pstruct, self.struct, self.dev, (self.w - 1) % self.C, self.first, self.count)
 
     def valid_pairs(self):
         """int32 [m, 2] device tensor of every stored (slot, env) whose whole frame stack is still in the ring (what sample(idx=) may be
@@ -272,6 +315,56 @@ class ReplayBuffer:
         return NStepSamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"], out["indices"],
                             out["discounts"], out["steps"])
 
+    def _need_priorities(self, what):
+        if getattr(self, "pstruct", None) is None:
+            raise ValueError(f"{what} needs a buffer built with prioritized=Prioritized(...)")
+
+    def sample_prioritized(self, n, n_steps=1, gamma=0.99, beta=None):
+        """`n` transitions drawn in proportion to their priorities -> PrioritizedSamples: sample_nstep()'s batch (n_steps = 1: sample()'s)
+        of the picked pairs, their integer priorities, and the importance weights under `beta` (None: the Prioritized's).  Two launches:
+        the pick (tde_priority_sample: a stratified draw from (seed, the buffer's draw counter), which then advances as sample()'s does)
+        and tde_nstep_sample with the picked pairs, through the terminal pool when the buffer has one.  The tensors it returns are its
+        own, reused by the next sample_prioritized of the same size."""
+        self._need_priorities("sample_prioritized()")
+        if n is None or int(n) < 1:
+            raise ValueError("n must be >= 1")
+        n, n_steps, gamma = int(n), int(n_steps), float(gamma)
+        beta = float(self.prioritized.beta if beta is None else beta)
+        if not 1 <= n_steps <= _abi.NSTEP_MAX:
+            raise ValueError(f"n_steps must be in [1, {_abi.NSTEP_MAX}], got {n_steps}")
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        if not 0.0 <= beta <= 1.0:
+            raise ValueError(f"beta must be in [0, 1], got {beta}")
+        if self.count < 1:
+            raise ValueError("the buffer holds no transition yet")
+        out = self._prio_out.get(n)
+        if out is None:
+            out = self._prio_out[n] = {**self._alloc(n), "discounts": torch.empty(n, dtype=torch.float32, device=self.dev),
+                                       "steps": torch.empty(n, dtype=torch.uint8, device=self.dev),
+                                       "picked": torch.empty((n, 2), dtype=torch.int32, device=self.dev),
+                                       "priorities": torch.empty(n, dtype=torch.int32, device=self.dev)}
+        ops.priority_sample(self.pstruct, self.struct, self.dev, self.first, self.count, n, out["picked"], out["priorities"], self.seed,
+                            self.draws)
+        ops.nstep_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, n_steps, gamma, out, out["picked"])
+        self.draws += 1
+        return PrioritizedSamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"],
+                                  out["indices"], out["discounts"], out["steps"], out["priorities"],
+                                  priority_weights(out["priorities"], beta))
+
+    def update_priorities(self, indices, td_errors):
+        """the learner's TD errors of a batch: the pairs `indices` (int [n, 2]: batch.indices) take the priority (|td| + eps) ** alpha
+        (tde_priority_update: the largest where a pair is named twice); pairs the ring has overwritten since are ignored"""
+        self._need_priorities("update_priorities()")
+        idx = torch.as_tensor(indices, device=self.dev).to(torch.int32).reshape(-1, 2).contiguous()
+        td = torch.as_tensor(td_errors, device=self.dev).to(torch.float32).reshape(-1)
+        if idx.shape[0] < 1:
+            raise ValueError("indices must hold at least one (slot, env) pair")
+        if td.shape[0] != idx.shape[0]:
+            raise ValueError(f"td_errors must hold {idx.shape[0]} values, one per pair of indices, got {td.shape[0]}")
+        p = ((td.abs() + float(self.prioritized.eps)) ** float(self.prioritized.alpha)).contiguous()
+        ops.priority_update(self.pstruct, self.struct, self.dev, self.first, self.count, idx, p)
+
     def _request(self, n, idx, check):
         """(n, idx) of a sample_nstep call as the launch takes them, under the rules sample() states for its own arguments"""
         if idx is not None:
@@ -298,7 +391,8 @@ class ReplayBuffer:
 
     @property
     def _tensors(self):
-        return ("frames", "action", "reward", "done", "age") + (("pool", "ref") if self.tstruct is not None else ())
+        return (("frames", "action", "reward", "done", "age") + (("pool", "ref") if self.tstruct is not None else ())
+                + (("leaf", "qmax") if getattr(self, "pstruct", None) is not None else ()))
 
     def state_dict(self):
         return {**{k: getattr(self, k).clone() for k in self._tensors}, "first": self.first, "w": self.w, "count": self.count,
@@ -308,6 +402,9 @@ class ReplayBuffer:
         if ("pool" in sd) != (self.tstruct is not None):
             raise ValueError("the state is of a buffer " + ("with" if "pool" in sd else "without") + " terminal frames, this buffer is "
                              + ("with" if self.tstruct is not None else "without") + " (terminal_obs=True of the env)")
+        if ("leaf" in sd) != (self.pstruct is not None):
+            raise ValueError("the state is of a buffer " + ("with" if "leaf" in sd else "without") + " priorities, this buffer is "
+                             + ("with" if self.pstruct is not None else "without") + " (prioritized=Prioritized(...))")
         for k in self._tensors:
             if tuple(sd[k].shape) != tuple(getattr(self, k).shape):
                 raise ValueError(f"{k} has shape {tuple(sd[k].shape)}, this buffer's is {tuple(getattr(self, k).shape)}")
@@ -315,3 +412,7 @@ class ReplayBuffer:
             getattr(self, k).copy_(sd[k])
         self.first, self.w, self.count, self.draws = int(sd["first"]), int(sd["w"]), int(sd["count"]), int(sd["draws"])
         self.seed, self._begun = int(sd.get("seed", self.seed)), bool(sd.get("begun", True))
+        if self.pstruct is not None:
+            # the sums are not part of the state: an update that names no stored pair changes no leaf and makes them current
+            none = torch.full((1, 2), -1, dtype=torch.int32, device=self.dev)
+            ops.priority_update(self.pstruct, self.struct, self.dev, self.first, self.count, none, torch.zeros(1, device=self.dev))
