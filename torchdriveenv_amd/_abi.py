@@ -217,6 +217,8 @@ class TdePriority(C.Structure):
 
 TDE_PRIORITY_VERSION = 1         # include/tde_priority.h
 PRIORITY_ONE, PRIORITY_QMAX, PRIORITY_TAG = 1 << 16, 1 << 28, 0x5052      # q of priority 1.0, the largest q, the draws' Philox tag
+TDE_SEQUENCE_VERSION = 1         # include/tde_sequence.h
+SEQUENCE_MAX = 256               # the longest window of a sequence sample
 
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7

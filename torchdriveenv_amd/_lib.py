@@ -22,6 +22,8 @@ NSTEP_SYMBOLS = ["tde_nstep_version", "tde_nstep_sample"]
 # every symbol include/tde_priority.h declares (additive over the replay header: TDE_PRIORITY_VERSION)
 PRIORITY_SYMBOLS = ["tde_priority_version", "tde_priority_words", "tde_priority_reset", "tde_priority_push", "tde_priority_update",
                     "tde_priority_sample"]
+# every symbol include/tde_sequence.h declares (additive over the terminal header: TDE_SEQUENCE_VERSION)
+SEQUENCE_SYMBOLS = ["tde_sequence_version", "tde_sequence_sample"]
 
 _lib = None
 
@@ -142,6 +144,15 @@ def load():
     L.tde_priority_sample.argtypes = [prp, rpp, i32, i32, i32, u64, u64, vp, vp, vp]
     for s in PRIORITY_SYMBOLS:
         getattr(L, s).restype = C.c_int64 if s == "tde_priority_words" else C.c_int
+    missing = [s for s in SEQUENCE_SYMBOLS if not hasattr(L, s)]
+    if missing:
+        raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")
+    if L.tde_sequence_version() != _abi.TDE_SEQUENCE_VERSION:
+        raise TdeError(f"sequence version mismatch: library {L.tde_sequence_version()} vs python {_abi.TDE_SEQUENCE_VERSION}")
+    L.tde_sequence_version.argtypes = []
+    L.tde_sequence_sample.argtypes = [rpp, tmp, i32, i32, i32, vp, u64, u64, i32] + [vp] * 6 + [vp]
+    for s in SEQUENCE_SYMBOLS:
+        getattr(L, s).restype = C.c_int
     _lib = L
     return L
 

@@ -1092,3 +1092,27 @@ def priority_sample(pr, rp, dev, first, count, n, idx, q, seed=0, draw=0):
     _lib.check(_call(dev, _lib.load().tde_priority_sample, C.byref(pr), C.byref(rp), int(first), int(count), n, int(seed) & (2**64 - 1),
                      int(draw) & (2**64 - 1), pi, pq, _lib.current_stream(dev)), "tde_priority_sample")
     return idx, q
+
+
+# ---- windows of consecutive steps from the ring (include/tde_sequence.h) -----------------------------------------------------------------
+def sequence_sample(rp, tm, dev, first, count, n, T, out, idx_in=None, seed=0, draw=0):
+    """tde_sequence_sample on the current stream, through the terminal pool when tm is not None: `n` windows of up to `T` stored steps
+    into the tensors of `out` - "observations" uint8 [n, T + 1, 3 * n_stack, plane] (planes mode) or float32 [n, T + 1, D] (rows mode),
+    "actions" float32 [n, T, 2], "rewards" float32 [n, T], "dones" uint8 [n, T], "lengths" int32 [n], "indices" int32 [n, 2] - whose
+    starts are drawn from (seed, draw) or, with idx_in (int32 [n, 2] (slot, env) pairs), as given"""
+    dev = torch.device(dev)
+    n, T = int(n), int(T)
+    if not 1 <= T <= _abi.SEQUENCE_MAX:
+        raise ValueError(f"T must be in [1, {_abi.SEQUENCE_MAX}], got {T}")
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    dt, per = _ring_frame(rp, stacked=True)
+    po = _chk(out["observations"], dt, n * (T + 1) * per, "observations", dev)
+    pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
+    pa, pr = _chk(out["actions"], torch.float32, 2 * n * T, "actions", dev), _chk(out["rewards"], torch.float32, n * T, "rewards", dev)
+    pd, pl = _chk(out["dones"], torch.uint8, n * T, "dones", dev), _chk(out["lengths"], torch.int32, n, "lengths", dev)
+    pin = _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)
+    _lib.check(_call(dev, _lib.load().tde_sequence_sample, C.byref(rp), None if tm is None else C.byref(tm), int(first), int(count), n, pin,
+                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), T, pi, po, pa, pr, pd, pl, _lib.current_stream(dev)),
+               "tde_sequence_sample")
+    return out

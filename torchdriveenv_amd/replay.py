@@ -11,6 +11,7 @@ sampled.  Vector and state observations are kept as float32 rows.
     env.reset(mask=m);            buf.begin(mask=m)            # a reset of the caller's own
     batch = buf.sample(256)                                    # observations, actions, next_observations, dones, rewards
     batch = buf.sample_nstep(256, n_steps=3, gamma=0.99)       # the same with n-step rewards, and discounts, steps
+    batch = buf.sample_sequence(64, length=80)                 # windows of consecutive steps for a recurrent learner (tde_sequence.h)
 
 sample_nstep() (include/tde_nstep.h, csrc/tde_nstep.hip) looks up to n_steps stored steps ahead of the drawn one and stops where the
 episode stopped: `rewards` is the discounted sum over the steps taken, `next_observations` and `dones` are those of the last of them,
@@ -72,6 +73,39 @@ class PrioritizedSamples(namedtuple("PrioritizedSamples", NStepSamples._fields +
     __slots__ = ()
     terminal = ReplaySamples.terminal
     bootstrap = ReplaySamples.bootstrap
+
+
+class SequenceSamples(namedtuple("SequenceSamples", ["observations", "actions", "rewards", "dones", "lengths", "indices", "priorities",
+                                                    "weights"])):
+    """n windows of up to T consecutive steps of one env each, all device tensors: observations uint8 [n, T + 1, 3 * frame_stack, H, W] or
+    float32 [n, T + 1, D] - observations[i, k] is what the env showed at step k of window i, observations[i, lengths[i]] the next
+    observation of its last step (zeros, the terminal observation, or the following step's, as ReplaySamples.next_observations) -
+    actions float32 [n, T, 2], rewards float32 [n, T], dones uint8 [n, T], lengths int32 [n] (the steps the window holds: it stops at
+    the first step that ended its episode or was cut, and at the newest stored step; 0 for a pair that gathered zeros), indices int32
+    [n, 2] the (slot, env) of step 0.  Everything behind a window's length is zeros.  priorities int32 [n] and weights float32 [n] are
+    those of PrioritizedSamples for a prioritized draw, None otherwise."""
+    __slots__ = ()
+
+    @property
+    def mask(self):
+        """bool [n, T]: step k of window i is one of its lengths[i] steps"""
+        T = self.dones.shape[1]
+        return torch.arange(T, device=self.lengths.device)[None, :] < self.lengths[:, None]
+
+    @property
+    def _last_done(self):
+        return self.dones.gather(1, (self.lengths.long() - 1).clamp(min=0)[:, None])[:, 0]
+
+    @property
+    def terminal(self):
+        """bool [n]: ReplaySamples.terminal of the window's last step (step lengths - 1)"""
+        return (self._last_done & (3 | _abi.REPLAY_CUT)) != 0
+
+    @property
+    def bootstrap(self):
+        """bool [n]: ReplaySamples.bootstrap of the window's last step: the learner should bootstrap from observations[i, lengths[i]]"""
+        d = self._last_done
+        return ((d & (3 | _abi.REPLAY_CUT)) == 0) | (((d & 3) == 2) & ((d & _abi.TERMINAL_HAS) != 0))
 
 
 def priority_weights(q, beta):
@@ -168,6 +202,7 @@ class ReplayBuffer:
         self._out = {}
         self._nstep_out = {}
         self._prio_out = {}
+        self._seq_out = {}
 
     # ---- bookkeeping --------------------------------------------------------------------------------------------------------
     def __len__(self):
@@ -365,8 +400,70 @@ class ReplayBuffer:
         p = ((td.abs() + float(self.prioritized.eps)) ** float(self.prioritized.alpha)).contiguous()
         ops.priority_update(self.pstruct, self.struct, self.dev, self.first, self.count, idx, p)
 
-    def _request(self, n, idx, check):
-        """(n, idx) of a sample_nstep call as the launch takes them, under the rules sample() states for its own arguments"""
+    def sample_sequence(self, n, length, idx=None, check=True, prioritized=False, beta=None):
+        """`n` windows of up to `length` (T in 1 .. SEQUENCE_MAX) consecutive steps of one env each -> SequenceSamples, for recurrent
+        learners (DRQN, R2D2, recurrent SAC / TD3).  A window starts at a step picked as sample_nstep() picks one - idx (int [n, 2]
+        (slot, env) pairs; n may be None) under the same `check`, or a draw from (seed, the buffer's draw counter), which advances by one -
+        and stops where sample_nstep's look-ahead stops: at the first step that ended its episode or was cut, and at the newest stored
+        step.  A drawn start leaves room for `length` steps whenever the buffer holds that many, so that only an episode's end shortens
+        a drawn window; with length == 1 the draw is sample()'s.  One entry point (tde_sequence_sample) rebuilds all T + 1 stacked
+        observations from the layer planes, through the terminal pool when the buffer has one.
+
+        prioritized=True (a buffer built with prioritized=Prioritized(...)): the starts are picked in proportion to their priorities
+        by tde_priority_sample, the pick sample_prioritized() makes from the same counter, and `priorities` and `weights` (under
+        `beta`; None: the Prioritized's) are filled as there.  Priorities stay per transition: the learner writes a window's back with
+        update_priorities(batch.indices, seq_priority), and R2D2's mix of the max and the mean TD error over the window is the caller's
+        one line of torch, e.g. 0.9 * td.abs().amax(1) + 0.1 * (td.abs() * batch.mask).sum(1) / batch.lengths.clamp(min=1).  A
+        prioritized start is any stored step, so one near the newest step gives a short window.
+
+        The tensors it returns are its own, kept per (n, length) and reused by the next sample_sequence of the same size."""
+        T = int(length)
+        if not 1 <= T <= _abi.SEQUENCE_MAX:
+            raise ValueError(f"length must be in [1, {_abi.SEQUENCE_MAX}], got {T}")
+        if prioritized:
+            self._need_priorities("sample_sequence(prioritized=True)")
+            if idx is not None:
+                raise ValueError("sample_sequence() takes idx or prioritized=True, not both")
+            beta = float(self.prioritized.beta if beta is None else beta)
+            if not 0.0 <= beta <= 1.0:
+                raise ValueError(f"beta must be in [0, 1], got {beta}")
+            if n is None or int(n) < 1:
+                raise ValueError("n must be >= 1")
+            if self.count < 1:
+                raise ValueError("the buffer holds no transition yet")
+            n = int(n)
+        else:
+            if beta is not None:
+                raise ValueError("beta needs prioritized=True")
+            n, idx = self._request(n, idx, check, "sample_sequence()")
+        out = self._seq_out.get((n, T))
+        if out is None:
+            obs = ((n, T + 1, 3 * self.n_stack, self.H, self.W), torch.uint8) if self.planes else ((n, T + 1, self.D), torch.float32)
+            out = self._seq_out[(n, T)] = {"observations": torch.empty(obs[0], dtype=obs[1], device=self.dev),
+                                           "actions": torch.empty((n, T, 2), dtype=torch.float32, device=self.dev),
+                                           "rewards": torch.empty((n, T), dtype=torch.float32, device=self.dev),
+                                           "dones": torch.empty((n, T), dtype=torch.uint8, device=self.dev),
+                                           "lengths": torch.empty(n, dtype=torch.int32, device=self.dev),
+                                           "indices": torch.empty((n, 2), dtype=torch.int32, device=self.dev)}
+        priorities = weights = None
+        if prioritized:
+            if "picked" not in out:
+                out["picked"] = torch.empty((n, 2), dtype=torch.int32, device=self.dev)
+                out["priorities"] = torch.empty(n, dtype=torch.int32, device=self.dev)
+            ops.priority_sample(self.pstruct, self.struct, self.dev, self.first, self.count, n, out["picked"], out["priorities"], self.seed,
+                                self.draws)
+            ops.sequence_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, T, out, out["picked"])
+            priorities, weights = out["priorities"], priority_weights(out["priorities"], beta)
+        else:
+            ops.sequence_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, T, out, idx, self.seed, self.draws)
+        if idx is None:
+            self.draws += 1
+        return SequenceSamples(out["observations"], out["actions"], out["rewards"], out["dones"], out["lengths"], out["indices"],
+                               priorities, weights)
+
+    def _request(self, n, idx, check, what="sample_nstep()"):
+        """(n, idx) of a sample_nstep / sample_sequence call as the launch takes them, under the rules sample() states for its own
+        arguments"""
         if idx is not None:
             idx = torch.as_tensor(idx, device=self.dev).to(torch.int32).reshape(-1, 2).contiguous()
             if n is None:
@@ -378,7 +475,7 @@ class ReplayBuffer:
         if self.count < 1:
             raise ValueError("the buffer holds no transition yet")
         if idx is None and self.count <= self.n_stack - 1:
-            raise ValueError(f"sample_nstep() draws steps whose whole frame stack is in the ring: it needs more than {self.n_stack - 1} stored steps, the buffer holds {self.count}")
+            raise ValueError(f"{what} draws steps whose whole frame stack is in the ring: it needs more than {self.n_stack - 1} stored steps, the buffer holds {self.count}")
         if idx is not None and check:
             s, e = idx[:, 0].long(), idx[:, 1].long()
             ok = (s >= 0) & (s < self.C) & (e >= 0) & (e < self.B)
