@@ -229,3 +229,91 @@ def test_sample_prioritized_over_an_env(world, obs_mode, frame_stack, kw, termin
     st = statement_of(buf)
     assert st.leaf[stale[0, 0], 0] == 0 and np.array_equal(st.leaf != 0, P.valid_mask(st.ring)) and int(buf.sums[0]) == st.total
     assert (st.leaf[(buf.w - 1) % buf.C] == P.QMAX).all()   # the pushed step entered with qmax
+
+
+# ---- 5. every depth of the tree, leaf counts that fill their blocks, installed leaves ------------------------------------------------------------
+@pytest.mark.parametrize("shape,n_stack", [(s, 1) for s in K.DEPTH_SHAPES] + [(s, 3) for s in K.DEPTH_STACKED])
+def test_depth_shapes_reset_push_update(shape, n_stack):
+    """reset over rubbish (every leaf and EVERY word of sums zero), pushes until the ring wraps, two updates of hundreds of pairs spread
+    over the flat range and one more push, a draw of 256 after each (tests/priority_cases.depth_run): leaf, sums[0], qmax and the
+    canaries after every call, every pick the statement's"""
+    c = K.DEPTH_SHAPES[shape]
+    hp, rounds = K.depth_run(shape, n_stack, DEV)
+    assert hp.t["sums"].numel() == c["words"] and hp.ring.count == c["C"] - 1
+    assert all((q > 0).all() for _, _, q in rounds)
+    hp.ring.check_state()                                   # no call wrote the ring
+
+
+@pytest.mark.parametrize("shape,pattern", K.INSTALLED_CASES)
+def test_installed_leaves_are_picked_as_the_statement_picks(shape, pattern):
+    """a named pattern of leaves put into the device tree, every draw setting; a second pattern over it without a reset, drawn again;
+    a real push and a real update on top, drawn once more (tests/priority_cases.installed_run; tests/test_priority_cpu.py vouches for
+    what the patterns and the draws reach)"""
+    n = K.DEPTH_SHAPES[shape]["n"]
+    hp, recs = K.installed_run(shape, pattern, DEV)
+    assert {r["stage"] for r in recs} == {0, 1, 2} and all((r["q"] > 0).all() for r in recs)
+    for name, want in (("last_only", n - 1), ("first_only", 0)):       # the one live pair, whatever the position
+        for r in recs:
+            assert r["stage"] == 2 or r["pattern"] != name or ((r["l"] == want).all() and (r["q"] == 1).all()), (name, r["N"])
+    assert pattern not in ("last_only", "first_only") or sum(r["pattern"] == pattern for r in recs) == 4
+    hp.ring.check_state()
+
+
+@pytest.mark.parametrize("shape", ("tail_4", "tail_2"))
+def test_nothing_drawable_at_depth(shape):
+    hp = K.depth_ring(shape, 1, DEV)
+    hp.reset()
+    assert hp.ref.total == 0
+    for n in (1, 256):
+        idx, q, _ = hp.draw(n, K.SEED, n)
+        assert (idx == -1).all() and not q.any()
+
+
+def test_buffer_with_a_two_level_tree(world):
+    """the buffer over an env with C * B = 96 leaves: a root over two level-1 nodes, so that pushes, update_priorities and the rebuild
+    of load_state_dict have inner nodes besides the total to keep"""
+    cfg = EnvConfig(seed=7, distance_cutoff=0.25, max_environment_steps=5, frame_stack=3, simulator=SimulatorConfig(renderer=RendererConfig(res=64)))
+    env = BatchedWaypointEnv(cfg, world, num_envs=B, device=DEV, obs_mode="birdview", frame_stack=3)
+    buf = env.replay_buffer(24, seed=3, prioritized=Prioritized())
+    assert buf.C * buf.B >= 65 and buf.sums.numel() == K.tree_words(buf.C * buf.B) >= 3
+    rng = np.random.default_rng(1)
+    env.reset()
+    buf.begin()
+    for t in range(30):                                     # the ring of 24 slots wraps
+        if t == 14:
+            mask = torch.tensor([1, 0, 0, 1], dtype=torch.uint8, device=DEV)
+            env.reset(mask=mask)
+            buf.begin(mask=mask)
+        a = torch.from_numpy(np.stack([rng.uniform(-1, 1, B), rng.uniform(-0.3, 0.3, B)], -1).astype(np.float32)).to(DEV)
+        env.step(a)
+        buf.push(a)
+        st = statement_of(buf)
+        assert np.array_equal(st.leaf != 0, P.valid_mask(st.ring)) and int(buf.sums[0]) == st.total
+        assert (st.leaf[st.leaf != 0] == P.ONE).all()
+    assert buf.count == 23 and 0 < buf.w < 23
+    every = buf.valid_pairs()
+    assert len(every) > 64                                  # drawable pairs under both level-1 nodes
+    td = torch.from_numpy(np.exp(rng.uniform(np.log(1e-4), np.log(1e4), len(every))).astype(np.float32)).to(DEV)
+    buf.update_priorities(every, td)
+    st = statement_of(buf)
+    assert np.array_equal(st.leaf != 0, P.valid_mask(st.ring)) and int(buf.sums[0]) == st.total
+    assert len(np.unique(st.leaf)) > len(every) // 2 and st.qmax == st.leaf.max() > P.ONE
+    draws = buf.draws
+    got = buf.sample_prioritized(64, 3)
+    idx, q, _ = st.draw(buf.seed, draws, 64)
+    assert np.array_equal(got.indices.cpu().numpy(), idx) and np.array_equal(got.priorities.cpu().numpy().view(np.uint32), q)
+    flat = idx[:, 0].astype(np.int64) * B + idx[:, 1]
+    assert (flat < 64).any() and (flat >= 64).any()         # picks under both children of the root
+    # the state into a second buffer, whose sums held nothing: load_state_dict rebuilds them, and the next draw is the first buffer's
+    sd = buf.state_dict()
+    first = buf.sample_prioritized(64, 3)
+    keep = {f: getattr(first, f).clone() for f in first._fields}
+    other = env.replay_buffer(24, seed=99, prioritized=Prioritized())
+    other.sums.fill_(0x0123456789)                          # (nor is what they held before of any account)
+    other.load_state_dict(sd)
+    assert int(other.sums[0]) == st.total and other.seed == buf.seed
+    again = other.sample_prioritized(64, 3)
+    idx, q, _ = st.draw(buf.seed, draws + 1, 64)
+    assert np.array_equal(again.indices.cpu().numpy(), idx)
+    for f in first._fields:
+        assert same_bytes(keep[f], getattr(again, f)), f

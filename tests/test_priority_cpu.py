@@ -75,7 +75,9 @@ def test_words_is_the_inner_nodes_of_a_64_ary_tree():
 
     L = _lib.load()
     for C_, B, want in ((4, 5, 1), (12, 5, 1), (2, 32, 1), (5, 13, 2 + 1), (40, 130, 82 + 2 + 1), (64, 64, 64 + 1), (64, 8192, 8192 + 128 + 2 + 1),
-                        (2, 2**30, 2**25 + 2**19 + 2**13 + 2**7 + 2 + 1), (2**31 - 1, 2**31 - 1, None)):
+                        (2, 2**30, 2**25 + 2**19 + 2**13 + 2**7 + 2 + 1), (2**31 - 1, 2**31 - 1, None),
+                        *[(c["C"], c["B"], c["words"]) for c in K.DEPTH_SHAPES.values()], (7, 100, 12), (17, 241, 68), (64, 4096, 4161),
+                        (5, 52429, 4165)):
         got = L.tde_priority_words(C_, B)
         assert got == K.tree_words(C_ * B) == ops.priority_words(C_, B) and (want is None or got == want), (C_, B, got)
     for C_, B in ((1, 5), (0, 5), (-1, 5), (4, 0), (4, -3)):
@@ -380,3 +382,123 @@ def test_case_table_update_names_every_kind_of_ignored_pair():
     before = hp.ref.leaf.copy()
     bad = [(-1, 0), (g.C, 0), (0, -1), (0, g.B), (U.INT32_MIN, 0), (0, U.INT32_MAX), (g.w, 2), stored_not_whole[0]]
     assert hp.update(bad, np.full(len(bad), 3.0, np.float32)) == 0 and np.array_equal(hp.ref.leaf, before) and hp.ref.qmax == P.ONE
+
+
+# ---- the depth table means something ----------------------------------------------------------------------------------------------------
+def test_depth_shapes_are_the_depths_and_leaf_counts_they_claim():
+    from torchdriveenv_amd import ops
+
+    for name, c in K.DEPTH_SHAPES.items():
+        lens = K.tree_lens(c["n"])
+        assert c["C"] * c["B"] == c["n"] and len(lens) - 1 == c["K"] and sum(lens[1:]) == c["words"], name
+        assert K.tree_words(c["n"]) == c["words"] == ops.priority_words(c["C"], c["B"]), name
+        assert (c["n"] % 64 == 0) == name.startswith("full_") and (c["n"] % 64 == 1) == name.startswith("tail_")
+        for k in range(c["K"]):                             # full: every level exactly full; tail: every level ends in a one-child node
+            assert not name.startswith("full_") or lens[k] == 64 ** (c["K"] - k)
+            assert not name.startswith("tail_") or lens[k] == 64 ** (c["K"] - 1 - k) + 1
+    assert {c["K"] for c in K.DEPTH_SHAPES.values()} == {1, 2, 3, 4}
+    assert {64, 65, 4096, 4097, 262144, 262145} <= {c["n"] for c in K.DEPTH_SHAPES.values()}
+    c = K.DEPTH_SHAPES["tail_4"]
+    assert c["B"] > 256 and c["n"] > 1024 * 256             # the push in more than one workgroup, the reset's loop in a second trip
+    assert all(K.DEPTH_SHAPES[s]["C"] >= 4 for s in K.DEPTH_STACKED)
+    for shape, pattern in K.INSTALLED_CASES:                # deterministic, of the shape's size, drawable
+        n = K.DEPTH_SHAPES[shape]["n"]
+        a, b = K.PATTERNS[pattern](n), K.PATTERNS[pattern](n)
+        assert a.dtype == np.uint32 and a.shape == (n,) and np.array_equal(a, b) and a.any() and a.max() <= P.QMAX, (shape, pattern)
+    assert set(K.OVER) == set(K.PATTERNS) and all(v in K.PATTERNS and v not in ("ones", "far_apart_late") for v in K.OVER.values())
+
+
+@pytest.fixture(scope="module")
+def installed_records():
+    """the draws of every installed case, statement only: {shape: [record]}"""
+    out = {shape: [] for shape in K.DEPTH_SHAPES}
+    for shape, pattern in K.INSTALLED_CASES:
+        hp, recs = K.installed_run(shape, pattern)
+        assert hp.installed and len({r["stage"] for r in recs}) == 3
+        out[shape] += [dict(r, case=pattern) for r in recs]
+    return out
+
+
+def test_installed_leaves_pick_first_last_and_tail_children_at_every_level(installed_records):
+    """a flat pick l is child (l >> 6k) & 63 of its node at level k: every level of every shape sees child 0 picked, child 63 (but for a
+    root of fewer than 64 children), and the last existing child of the level's tail node"""
+    for shape, recs in installed_records.items():
+        lens = K.tree_lens(K.DEPTH_SHAPES[shape]["n"])
+        depth = len(lens) - 1
+        l = np.concatenate([r["l"] for r in recs])
+        assert (l >= 0).all() and (l < lens[0]).all()
+        for k in range(depth):
+            at = l >> (6 * k)                               # the pick's node of level k (its leaf at k = 0)
+            assert ((at & 63) == 0).any(), (shape, k, "child 0")
+            assert (k == depth - 1 and lens[k] < 64) or ((at & 63) == 63).any(), (shape, k, "child 63")
+            assert lens[k] % 64 == 0 or (at == lens[k] - 1).any(), (shape, k, "the tail node's last child")
+    # and in one descent: lane 0 at every level (first_only), the last lane at every level (last_only)
+    for shape, recs in installed_records.items():
+        n = K.DEPTH_SHAPES[shape]["n"]
+        for name, want in (("first_only", 0), ("last_only", n - 1)):
+            mine = [r for r in recs if r["pattern"] == name and r["stage"] < 2]
+            assert len(mine) >= 4 and all((r["l"] == want).all() and (r["q"] == 1).all() for r in mine), (shape, name)
+
+
+def test_installed_far_apart_picks_behind_zero_subtrees(installed_records):
+    for shape, recs in installed_records.items():
+        depth = K.DEPTH_SHAPES[shape]["K"]
+        far = [r for r in recs if r["pattern"].startswith("far_apart")]
+        assert far
+        for k in range(1, depth):                           # a wholly-zero level-k subtree: 64^k leaves
+            assert any(K.behind_zero_subtree(r["leaf"], r["l"], 64**k) for r in far), (shape, k)
+        # besides: a zero subtree with live leaves on both sides, wherever the shape has room for one
+        for k in range(1, depth):
+            if K.tree_lens(K.DEPTH_SHAPES[shape]["n"])[k] >= 3:
+                size = 64**k
+                assert any(r["leaf"][:size].any() and not r["leaf"][size:2 * size].any() and (r["l"] >= 2 * size).any()
+                           for r in far if r["pattern"] == "far_apart"), (shape, k)
+
+
+def test_installed_draws_hit_edges_and_wide_spans(installed_records):
+    on_edge = wide_span = base_zero = wide_draw = short_group = 0
+    biggest = 0
+    for shape, recs in installed_records.items():
+        edges, seen = None, None
+        for r in recs:
+            T = int(r["leaf"].astype(np.int64).sum())
+            assert T > 0 and len(r["us"]) == r["N"] and (r["q"] > 0).all() and (r["q"] == r["leaf"][r["l"]]).all()
+            assert r["N"] <= 4096 or K.DEPTH_SHAPES[shape]["n"] <= K.ONES_MAX
+            if seen is not r["leaf"]:
+                seen, edges = r["leaf"], set(np.cumsum(r["leaf"].astype(np.int64)).tolist()) | {0}
+            hits = sum(u in edges for u in r["us"])
+            assert r["pattern"] != "lane_edges" or r["N"] < 256 or hits >= r["N"] // 8, (shape, r["N"], hits)
+            assert r["pattern"] != "ones" or r["N"] != K.DEPTH_SHAPES[shape]["n"] or hits == r["N"]
+            on_edge += hits
+            wide_span += r["N"] == 1 and T > 2**32
+            base_zero += r["N"] > T
+            wide_draw += r["draw"] >= 2**32
+            short_group += r["N"] % 4 != 0 and r["N"] > 4
+            biggest = max(biggest, T)
+    assert on_edge >= 100 and wide_span and base_zero >= 10 and wide_draw and short_group
+    assert biggest == 262145 * P.QMAX                       # the largest total the table's shapes allow: about 2^46
+
+
+def test_depth_run_updates_spread_pairs_and_draws_them():
+    """the pushes, updates and draws of tests/test_gpu_priority.test_depth_shapes_reset_push_update, statement only"""
+    for shape, n_stack in [(s, 1) for s in K.DEPTH_SHAPES] + [(s, 3) for s in K.DEPTH_STACKED]:
+        hp, rounds = K.depth_run(shape, n_stack)
+        g = hp.ring.ref
+        assert g.count == g.C - 1 and not hp.installed      # wrapped, and the invariant held after every call
+        valid = np.argwhere(P.valid_mask(g))
+        (first, _, _), (second, _, _), _ = rounds
+        assert len(first) == min(K.UPDATED, len(valid)) or n_stack > 1
+        flat = lambda pairs: pairs[:, 0].astype(np.int64) * g.B + pairs[:, 1]
+        assert len(set(flat(first).tolist())) == len(first) and len(first) >= min(K.UPDATED, 30)
+        if len(valid) > K.UPDATED:
+            assert not set(flat(first).tolist()) & set(flat(second).tolist()) and len(second) >= 100
+            # spread over the whole flat range: the first and the last valid pair, and every eighth of the leaves in between
+            assert np.array_equal(first[0], rounds[0][0][0]) and flat(first).min() < g.C * g.B // 8 and flat(first).max() >= 7 * g.C * g.B // 8
+            assert len(set((flat(first) * 8 // (g.C * g.B)).tolist())) == 8
+        for named, l, q in rounds:
+            assert (q > 0).all() and len(l) == 256
+        for named, l, _ in rounds[:2]:                      # the ends of what an update named are drawn right after it
+            assert {int(flat(named)[0]), int(flat(named)[-1])} <= set(l.tolist()), (shape, n_stack)
+        last = flat(rounds[0][0])[-1]
+        assert g.C * g.B % 64 != 1 or n_stack > 1 or last == g.C * g.B - 1      # in a tail shape that is the leaf alone under the last node of every level
+        assert hp.ref.qmax > P.ONE                          # an update raised it: the last push entered above ONE
