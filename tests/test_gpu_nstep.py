@@ -104,6 +104,20 @@ def test_a_saturated_age_along_the_look_ahead(shape):
             check_nstep(ring, n_steps, 0.99, pool, pairs)
 
 
+def test_the_look_ahead_at_its_full_width():
+    """n_steps = 64 where 64 stored steps lie ahead (C = 12 above never has them): endings in lane 63 and one beyond it, m = count - off
+    = 64, and the newest step; tests/test_nstep_cpu.py::test_long_ring_reaches_the_full_width_of_the_look_ahead vouches for the pairs"""
+    from tests import sequence_cases as S
+
+    pairs = S.long_pairs()
+    for pool in (False, True):
+        ring = S.long_ring(pool=pool, dev=DEV)
+        assert ring.check_state() == (0, 280, 280)
+        got = check_nstep(ring, 64, 0.99, pool, pairs)
+        assert got["steps"].max() == 64 and got["steps"].min() == 1 and 63 in got["steps"]
+        check_nstep(ring, 64, 0.99, pool, pairs[1::2])      # env 1 alone: no ending anywhere
+
+
 # ---- 2. pairs that gather zeros ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(U.INVALID_RINGS))
 @pytest.mark.parametrize("mode", list(U.INVALID_MODES))

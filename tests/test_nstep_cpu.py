@@ -262,6 +262,26 @@ def test_case_table_age_saturates_along_the_look_ahead():
     assert ring.ref.age[ring.w, 1] == 2 and N.look_ahead(ring.ref, slots[0], 1, 64) == ring.count - 2
 
 
+def test_long_ring_reaches_the_full_width_of_the_look_ahead():
+    """what tests/test_gpu_nstep.py::test_the_look_ahead_at_its_full_width runs: n_steps = 64 over the long ring of tests/sequence_cases.py"""
+    from tests import sequence_cases as S
+
+    for pool in (False, True):
+        ring = S.long_ring(pool=pool)
+        assert (ring.C, ring.B, ring.n_stack, ring.plane) == (300, 2, 2, 16) and (ring.first, ring.count) == (0, 280)
+        pairs, ref = S.long_pairs(), ring.ref
+        got = N.gather(ref, pairs, 64, 0.99, terminal=pool)
+        assert got["steps"].tolist() == [64, 64, 64, 64, 64, 64, 63, 64, 1, 64, 64, 64, 64, 64, 1, 64, 64, 64, 64, 64, 50, 64, 49, 64, 52, 64, 1, 1]
+        m = {tuple(p): int(k) for p, k in zip(pairs.tolist(), got["steps"])}
+        last = lambda s: int(ref.done[(s + m[(s, 0)] - 1) % ref.C, 0])
+        assert m[(10, 0)] == 64 and last(10) & 3 == 1                              # terminated at the last step: the ending is in lane 63
+        assert m[(75, 0)] == 64 and last(75) & 3 == 2                              # truncated at the last step
+        assert m[(9, 0)] == 64 and not last(9) & ENDED and ref.done[9 + 64, 0] & ENDED         # no ending, and one a step beyond
+        assert m[(11, 0)] == 63 and last(11) & ENDED
+        assert m[(216, 1)] == 64 == ref.count - int(ref.offset(216))              # the stored range ends with the look-ahead
+        assert m[(279, 0)] == m[(279, 1)] == 1 and int(ref.offset(279)) == ref.count - 1       # the newest stored step
+
+
 def test_case_table_tells_the_stated_order_from_a_fused_multiply_add():
     ring = K.history_ring(D=5)
     differ = 0

@@ -211,6 +211,61 @@ def test_replay_buffer_argument_checks_need_no_gpu():
     assert callable(BatchedWaypointEnv.replay_buffer)
 
 
+def _host_buffer(**over):
+    """a buffer in host memory with the attributes the refusals read and nothing else: every refusal comes before the first device call"""
+    import torch
+
+    from torchdriveenv_amd.replay import ReplayBuffer
+
+    buf = ReplayBuffer.__new__(ReplayBuffer)
+    buf.dev, buf.C, buf.B, buf.n_stack, buf.first, buf.count, buf.draws = torch.device("cpu"), 6, 3, 3, 1, 4, 5
+    buf.age = torch.tensor([[0] * 3, [0, 1, 2], [1, 2, 3], [2, 0, 4], [3, 1, 5], [4, 2, 6]], dtype=torch.uint8)
+    for k, v in over.items():
+        setattr(buf, k, v)
+    return buf
+
+
+def test_sample_refuses_what_sample_nstep_refuses():
+    buf = _host_buffer()
+    for n in (0, -1, None):
+        with pytest.raises(ValueError, match="n must be >= 1"):
+            buf.sample(n)
+    with pytest.raises(ValueError, match=r"idx must hold 3 \(slot, env\) pairs"):
+        buf.sample(3, idx=[(1, 0), (2, 0)])
+    # slot 0 is the open slot's successor, (1, 2) lacks its older frames (age 2 at off 0), env 3 and slot 6 do not exist
+    for bad in ((0, 0), (1, 2), (2, 2), (5, 0), (2, 3), (6, 0), (-1, 0), (2, -1)):
+        with pytest.raises(ValueError, match=r"not stored transitions with their whole frame stack in the ring \(valid_pairs\(\)\)"):
+            buf.sample(None, idx=[(1, 0), bad, (3, 1)])
+    buf.count = 2
+    with pytest.raises(ValueError, match=r"sample\(\) draws steps .* needs more than 2 stored steps, the buffer holds 2"):
+        buf.sample(4)
+    buf.count = 0
+    with pytest.raises(ValueError, match="holds no transition yet"):
+        buf.sample(4)
+    assert buf.draws == 5                                   # a refused call draws nothing
+
+
+def test_which_refusal_wins_when_a_call_is_bad_twice():
+    from torchdriveenv_amd.config import Prioritized
+
+    def message(call):
+        with pytest.raises(ValueError) as err:
+            call()
+        return str(err.value)
+
+    buf = _host_buffer()
+    assert message(lambda: buf.sample_nstep(0, 0)) == "n_steps must be in [1, 64], got 0"
+    assert message(lambda: buf.sample_sequence(0, 0)) == "length must be in [1, 256], got 0"
+    assert message(lambda: buf.sample_prioritized(0, 0)) == "sample_prioritized() needs a buffer built with prioritized=Prioritized(...)"
+    assert (message(lambda: buf.sample_sequence(4, 8, prioritized=True))
+            == "sample_sequence(prioritized=True) needs a buffer built with prioritized=Prioritized(...)")
+    assert message(lambda: buf.sample_sequence(4, 8, beta=0.5)) == "beta needs prioritized=True"
+    buf = _host_buffer(pstruct=object(), prioritized=Prioritized())
+    assert message(lambda: buf.sample_sequence(4, 8, idx=[(1, 0)] * 4, prioritized=True)) == "sample_sequence() takes idx or prioritized=True, not both"
+    assert message(lambda: buf.sample_prioritized(4, 65, 2.0, 2.0)) == "n_steps must be in [1, 64], got 65"
+    assert buf.draws == 5
+
+
 # ---- the numpy restatement against a hand-written answer: two envs, five steps, env 0 ends its episode at the third step, n_stack 3 ----
 WHITE, GREY, GREEN, BLUE, RED, BLACK = (255, 255, 255), (128, 128, 128), (44, 160, 44), (31, 119, 180), (214, 39, 40), (0, 0, 0)
 P = 16

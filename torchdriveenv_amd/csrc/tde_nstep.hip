@@ -1,11 +1,9 @@
 // tde_nstep.hip — n-step returns from the replay ring, include/tde_nstep.h: its kernels, its host-side checks and its entry point (a
 // translation unit of its own: no existing kernel includes it, and it changes none - the ring is filled by tde_replay.hip, the pool by
 // tde_terminal.hip).
-//   * the pick of a sample, the frame rule, the expansion of a layer plane and the pool row are tde_ring.h's (ring_pick, ring_shown,
-//     ring_expand, ring_pool_row): nothing of them is restated here.
-//   * the look-ahead is wave-uniform and every wavefront repeats it instead of waiting for one that made it: lane j reads the done byte
-//     of slot s + j, the ballot of the ended lanes is the list of the endings, its first set bit is m (a scalar find-first-one: no
-//     vector shift).  Only the wavefront that writes the scalars reads the rewards - lane j that of slot s + j - and sums them in the
+//   * the pick of a sample, the look-ahead, its last step and what follows it, the frame rule, the expansion of a layer plane and the
+//     pool row are tde_ring.h's (ring_pick, ring_ahead, ring_last, ring_shown, ring_expand, ring_pool_row): nothing of them is restated.
+//   * the look-ahead is wave-uniform and every wavefront repeats it instead of waiting for one that made it.  Only the wavefront that writes the scalars reads the rewards - lane j that of slot s + j - and sums them in the
 //     header's order with __fmul_rn / __fadd_rn, which the compiler may not fuse.
 //   * planes mode: one workgroup per sample, one wavefront per WRITTEN frame - frames 0 .. n_stack - 1 of obs from the stack of slot s,
 //     frames 0 .. n_stack - 1 of next_obs from the stack that follows slot L (or the terminal stack of L, or zeros).  A wavefront
@@ -27,18 +25,6 @@ struct NStepArgs : Base {               // SampleArgs / TerminalSampleArgs (kPoo
     uint8_t *steps;
 };
 
-// m of the pick `p` (wave-uniform, by all 64 lanes; 0 for a pair that is no stored transition)
-template <class Args>
-TDE_DEV int nstep_ahead(const Args &s, const RingPick &p, int lane)
-{
-    if (!p.ok) return 0;
-    const int a = min(s.n_steps, s.count - p.off);      // (1 <= a <= C - 1: slot s + lane is a stored slot for lane < a)
-    bool ended = false;
-    if (lane < a) ended = (s.rp.done[(int64_t)ring_slot(p.slot, lane, s.rp.C) * s.rp.B + p.env] & kRingEnded) != 0;
-    const unsigned long long ends = __ballot(ended);
-    return ends ? __ffsll((long long)ends) : a;
-}
-
 // the scalars of sample i, by one whole wavefront: the reward sum in the header's order, then lane 0 writes
 template <class Args>
 TDE_DEV void nstep_scalars(const Args &s, int i, const RingPick &p, int m, int lane)
@@ -57,10 +43,9 @@ TDE_DEV void nstep_scalars(const Args &s, int i, const RingPick &p, int m, int l
     uint32_t d = 0;
     float2 act = make_float2(0.0f, 0.0f);
     if (p.ok) {
-        const int64_t at_last = (int64_t)ring_slot(p.slot, m - 1, C) * B + p.env;
         act = reinterpret_cast<const float2 *>(s.rp.action)[(int64_t)p.slot * B + p.env];
-        d = s.rp.done[at_last];
-        if (ring_pool_row(s, at_last, d) >= 0) d |= TDE_TERMINAL_HAS;
+        const RingLast z = ring_last(s, p.slot, p.env, m);
+        d = z.row >= 0 ? z.done_last | TDE_TERMINAL_HAS : z.done_last;
     }
     reinterpret_cast<float2 *>(s.action)[i] = act;
     s.reward[i] = R;
@@ -76,7 +61,7 @@ __global__ __launch_bounds__(64 * 2 * TDE_REPLAY_MAX_STACK) void nstep_planes_ke
     const int lane = (int)(threadIdx.x & 63u), k = (int)(threadIdx.x >> 6), i = (int)blockIdx.x;
     const int C = s.rp.C, B = s.rp.B, ns = s.rp.n_stack, plane = SIZE64 ? 4096 : s.rp.plane;
     const RingPick p = ring_pick(s, i);
-    const int m = nstep_ahead(s, p, lane);
+    const int m = ring_ahead<TDE_NSTEP_MAX / 64>(s, p, s.n_steps, lane);
     if (k == 0) nstep_scalars(s, i, p, m, lane);
     const bool to_next = k >= ns;
     const int j = to_next ? k - ns : k;
@@ -88,15 +73,14 @@ __global__ __launch_bounds__(64 * 2 * TDE_REPLAY_MAX_STACK) void nstep_planes_ke
         bool live = true;
         if (to_next) {
             const int last = ring_slot(p.slot, m - 1, C);
-            const int64_t at_last = (int64_t)last * B + p.env;
-            const uint32_t done = s.rp.done[at_last];
-            row = ring_pool_row(s, at_last, done);
+            const RingLast z = ring_last(s, p.slot, p.env, m);
+            row = z.row;
             if (row >= 0) {
                 // the terminal stack: the stack of slot L one frame down (d = -1: the pool plane on top)
                 newest = last, off = p.off + m - 1, d -= 1;
             } else {
                 // the stack of slot L + 1, zeros after an end
-                newest = ring_slot(last, 1, C), off = p.off + m, live = (done & kRingEnded) == 0;
+                newest = ring_slot(last, 1, C), off = p.off + m, live = z.live;
             }
         }
         show = live && ring_shown(d, s.rp.age[(int64_t)newest * B + p.env], off);
@@ -117,21 +101,19 @@ __global__ __launch_bounds__(64 * kRingWaves) void nstep_rows_kernel(Args s, int
     if (i >= N) return;
     const int C = s.rp.C, B = s.rp.B, D = s.rp.D;
     const RingPick p = ring_pick(s, i);
-    const int m = nstep_ahead(s, p, lane);
+    const int m = ring_ahead<TDE_NSTEP_MAX / 64>(s, p, s.n_steps, lane);
     nstep_scalars(s, i, p, m, lane);
     const float *rows = reinterpret_cast<const float *>(s.rp.frames), *from = rows;
     bool next = false;
     int64_t at = 0, at1 = 0;
     if (p.ok) {
         const int last = ring_slot(p.slot, m - 1, C);
-        const int64_t at_last = (int64_t)last * B + p.env;
+        const RingLast z = ring_last(s, p.slot, p.env, m);
         at = (int64_t)p.slot * B + p.env;
         at1 = (int64_t)ring_slot(last, 1, C) * B + p.env;
-        const uint32_t done = s.rp.done[at_last];
-        const int r = ring_pool_row(s, at_last, done);
-        next = r >= 0 || (done & kRingEnded) == 0;
+        next = z.row >= 0 || z.live;
         if constexpr (Args::kPool) {
-            if (r >= 0) from = reinterpret_cast<const float *>(s.tm.pool), at1 = (int64_t)last * s.tm.M + r;
+            if (z.row >= 0) from = reinterpret_cast<const float *>(s.tm.pool), at1 = (int64_t)last * s.tm.M + z.row;
         }
     }
     float *o = reinterpret_cast<float *>(s.obs) + (int64_t)i * D, *n = reinterpret_cast<float *>(s.next_obs) + (int64_t)i * D;
@@ -182,20 +164,9 @@ int tde_nstep_sample(const tde_replay *rp, const tde_terminal *tm, int32_t first
                      float *action, float *reward, uint8_t *done, float *discount, uint8_t *steps, void *stream)
 {
     const char *fn = "tde_nstep_sample";
-    int rc;
-    if (tm) {
-        tde::NStepArgs<tde::TerminalSampleArgs> s;
-        if ((rc = check_terminal_struct(fn, rp, tm)) != 0 ||
-            (rc = check_sample(fn, rp, first, count, N, idx_in, seed, draw, idx, obs, next_obs, action, reward, done, s)) != 0 ||
-            (rc = check_nstep(fn, n_steps, gamma, discount, steps, s)) != 0)
-            return rc;
-        s.tm = *tm;
+    return with_ring_args<tde::NStepArgs>(fn, rp, tm, [&](auto &s) {
+        int rc = check_sample(fn, rp, first, count, N, idx_in, seed, draw, idx, obs, next_obs, action, reward, done, s);
+        if (rc || (rc = check_nstep(fn, n_steps, gamma, discount, steps, s)) != 0) return rc;
         return launch_nstep(fn, s, N, stream);
-    }
-    tde::NStepArgs<tde::SampleArgs> s;
-    if ((rc = check_replay_struct(fn, rp)) != 0 ||
-        (rc = check_sample(fn, rp, first, count, N, idx_in, seed, draw, idx, obs, next_obs, action, reward, done, s)) != 0 ||
-        (rc = check_nstep(fn, n_steps, gamma, discount, steps, s)) != 0)
-        return rc;
-    return launch_nstep(fn, s, N, stream);
+    });
 }

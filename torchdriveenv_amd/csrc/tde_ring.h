@@ -1,10 +1,19 @@
-// tde_ring.h — what the units over the replay ring (tde_replay.hip, tde_onpolicy.hip, tde_terminal.hip, tde_nstep.hip, tde_priority.hip) share: what a learner
-// sees of a stored transition, stated once.
+// tde_ring.h — what the six units over the replay ring share: what a learner sees of a stored transition, stated once.
 //   * device side: the "ended" mask, the ring's wrap, the row copy, the pick of a sample (the draw, and the validity rule of a given
-//     pair), the frame rule, the expansion of a layer plane into frames of obs / next_obs, the scalars of a sampled transition;
+//     pair), the frame rule, the expansion of a layer plane into frames of obs / next_obs, the scalars of a sampled transition, the
+//     look-ahead from a pick to the first ending (ring_ahead) and the last step of a look-ahead with what follows it (ring_last);
 //   * kernels: ring_gather_planes_kernel / ring_gather_rows_kernel<Args> - tde_replay_sample (Args = SampleArgs) and
 //     tde_terminal_sample (Args = TerminalSampleArgs: the same with the terminal pool, which the first instantiation does not contain);
-//   * host side: the argument checks that more than one entry point makes.  Each message names its entry point (`fn`).
+//   * host side: the argument checks that more than one entry point makes, and the choice of the argument block of an entry point
+//     that takes the pool or not (with_ring_args).  Each message names its entry point (`fn`).
+// What each unit takes:
+//   tde_replay.hip     the wrap, the row copy, check_slot / check_src, check_sample, the two gather kernels (launch_sample), kRingWaves
+//   tde_terminal.hip   the row copy, the same checks, and the gather kernels over TerminalSampleArgs
+//   tde_onpolicy.hip   the wrap, the "ended" mask, the frame rule, the expansion of a plane (ring_expand), check_stored, kRingWaves
+//   tde_priority.hip   the wrap, the stack rule (ring_whole), check_slot / check_stored, kRingWaves
+//   tde_nstep.hip      the pick, ring_ahead<1>, ring_last, the frame rule, ring_expand, the pool row, check_sample, with_ring_args
+//   tde_sequence.hip   the pick of a given pair, ring_ahead<4>, ring_last, the frame rule, the pool row, the row copy, check_sample
+//                      without a next_obs, with_ring_args
 #pragma once
 #include "tde_raster.h"
 #include "tde_host.h"
@@ -132,6 +141,47 @@ TDE_DEV int ring_pool_row(const Args &s, int64_t at, uint32_t done)
     }
 }
 
+// m, the steps a look-ahead of up to `limit` stored steps takes from the pick `p` (wave-uniform, by all 64 lanes; 0 for a pair that is
+// no stored transition): it stops at the first step that ended its episode or was cut, and at the newest stored step.  Lane j reads
+// the done byte of step base + j, the ballot of the ended lanes lists the endings, its first set bit is m (a scalar find-first-one: no
+// vector shift).  ROUNDS rounds of 64 steps cover `limit` (limit <= 64 * ROUNDS); with ROUNDS == 1 there is no loop.
+template <int ROUNDS, class Args>
+TDE_DEV int ring_ahead(const Args &s, const RingPick &p, int limit, int lane)
+{
+    if (!p.ok) return 0;
+    const int a = min(limit, s.count - p.off);          // (1 <= a <= C - 1: slot s + k is a stored slot for k < a)
+    // (a <= 64 * ROUNDS bounds the rounds at run time; with one round the bound is the constant 1, so that no loop is compiled)
+    for (int base = 0; base < (ROUNDS == 1 ? 1 : a); base += 64) {
+        const int k = base + lane;
+        bool ended = false;
+        if (k < a) ended = (s.rp.done[(int64_t)ring_slot(p.slot, k, s.rp.C) * s.rp.B + p.env] & kRingEnded) != 0;
+        const unsigned long long ends = __ballot(ended);
+        if (ends) return base + __ffsll((long long)ends);
+    }
+    return a;
+}
+
+// the last step L = slot + m - 1 of a look-ahead of m >= 1 steps, and what follows it: the next observation is the pool plane / row
+// over L's stack moved one frame down (row >= 0), or the stack of slot L + 1 (live), or zeros after an ending.  (The one-step
+// gathers below are this with m = 1; they keep their own lines - see ring_gather_planes_kernel.)
+struct RingLast {
+    int64_t at_last;                    // the stored transition at slot L
+    uint32_t done_last;
+    int row;                            // its pool row, or -1
+    bool live;                          // L neither ended its episode nor was cut
+};
+
+template <class Args>
+TDE_DEV RingLast ring_last(const Args &s, int slot, int env, int m)
+{
+    RingLast z;
+    z.at_last = (int64_t)ring_slot(slot, m - 1, s.rp.C) * s.rp.B + env;
+    z.done_last = s.rp.done[z.at_last];
+    z.row = ring_pool_row(s, z.at_last, z.done_last);
+    z.live = (z.done_last & kRingEnded) == 0;
+    return z;
+}
+
 // the scalars of transition i, by one lane
 template <class Args>
 TDE_DEV void ring_scalars(const Args &s, int i, const RingPick &p)
@@ -165,6 +215,7 @@ __global__ __launch_bounds__(64 * (TDE_REPLAY_MAX_STACK + 1)) void ring_gather_p
     const uint8_t *from = s.rp.frames;
     if (p.ok) {
         const int64_t at = (int64_t)p.slot * B + p.env;
+        // (ring_last's rule at m = 1 in this kernel's own lines: through ring_last the general form takes 34 VGPRs, not 32)
         const int age = s.rp.age[at], age1 = s.rp.age[(int64_t)ring_slot(p.slot, 1, C) * B + p.env];
         const uint32_t done = s.rp.done[at];
         const bool ended = (done & kRingEnded) != 0;     // (its own statement: folded into to_next the 64 x 64 form takes 34 VGPRs, not 32)
@@ -198,7 +249,7 @@ __global__ __launch_bounds__(64 * kRingWaves) void ring_gather_rows_kernel(Args 
     if (p.ok) {
         at = (int64_t)p.slot * B + p.env;
         at1 = (int64_t)ring_slot(p.slot, 1, C) * B + p.env;
-        const uint32_t done = s.rp.done[at];
+        const uint32_t done = s.rp.done[at];            // (ring_last's rule at m = 1 in its own lines: through ring_last, 9 more instructions)
         const int r = ring_pool_row(s, at, done);
         next = r >= 0 || (done & kRingEnded) == 0;
         if constexpr (Args::kPool) {
@@ -244,16 +295,17 @@ inline int check_stored(const char *fn, const tde_replay *rp, int32_t first, int
     return 0;
 }
 
-// what tde_replay_sample and tde_terminal_sample take after their structs (checked by the caller); fills the launch's argument block
+// what the samplers take after their structs (checked by the caller); fills the launch's argument block.  want_next: the sampler has a
+// next_obs (tde_sequence_sample has none and passes NULL)
 inline int check_sample(const char *fn, const tde_replay *rp, int32_t first, int32_t count, int32_t N, const int32_t *idx_in, uint64_t seed,
                         uint64_t draw, int32_t *idx, uint8_t *obs, uint8_t *next_obs, float *action, float *reward, uint8_t *done,
-                        tde::SampleArgs &s)
+                        tde::SampleArgs &s, bool want_next = true)
 {
     if (N < 1) return bad_in(fn, "N must be >= 1");
     if (count < 1) return bad_in(fn, "count must be >= 1 (the buffer holds no transition)");
     const int rc = check_stored(fn, rp, first, count);
     if (rc) return rc;
-    if (!idx || !obs || !next_obs || !action || !reward || !done) return bad_in(fn, "a NULL output");
+    if (!idx || !obs || (want_next && !next_obs) || !action || !reward || !done) return bad_in(fn, "a NULL output");
     if (!idx_in && count <= rp->n_stack - 1) return bad_in(fn, "count must be > n_stack - 1 to draw: no stored transition has its whole stack in the ring yet");
     const int64_t al = rp->plane > 0 ? 16 : 4;
     if (!aligned(obs, al) || !aligned(next_obs, al) || !aligned(action, 8) || !aligned(reward, 4) || !aligned(idx, 4) || !aligned(idx_in, 4))
@@ -263,6 +315,23 @@ inline int check_sample(const char *fn, const tde_replay *rp, int32_t first, int
     s.draw_lo = (uint32_t)draw; s.draw_hi = (uint32_t)(draw >> 32);
     s.idx = idx; s.obs = obs; s.next_obs = next_obs; s.action = action; s.reward = reward; s.done = done;
     return 0;
+}
+
+// an entry point that takes the ring and, or not (tm NULL), the terminal pool beside it: checks the struct(s), makes the argument block
+// Block<SampleArgs> or Block<TerminalSampleArgs> with *tm in it, and runs `body` - the entry point's own checks and its launch - on it
+template <template <class> class Block, class Body>
+int with_ring_args(const char *fn, const tde_replay *rp, const tde_terminal *tm, Body body)
+{
+    if (tm) {
+        Block<tde::TerminalSampleArgs> s;
+        const int rc = check_terminal_struct(fn, rp, tm);
+        if (rc) return rc;
+        s.tm = *tm;
+        return body(s);
+    }
+    Block<tde::SampleArgs> s;
+    const int rc = check_replay_struct(fn, rp);
+    return rc ? rc : body(s);
 }
 
 // the launch of either sampler's gather

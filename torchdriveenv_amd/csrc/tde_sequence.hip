@@ -1,12 +1,11 @@
 // tde_sequence.hip — windows of consecutive steps from the replay ring, include/tde_sequence.h: its kernels, its host-side checks and
 // its entry point (a translation unit of its own: no existing kernel includes it, and it changes none - the ring is filled by
 // tde_replay.hip, the pool by tde_terminal.hip).
-//   * the ring's wrap, the pick of a given pair, the frame rule, the pool row, the palette and the "ended" mask are tde_ring.h's
-//     (ring_slot, ring_pick, ring_shown, ring_pool_row, raster_expand, kRingEnded): nothing of them is restated here.  The draw takes
-//     ring_pick's Philox words over a span that keeps a whole window inside the stored range.
-//   * two launches on the caller's stream.  sequence_scalars_kernel, one wavefront per window, finds the window's length m - lane j
-//     reads the done byte of step base + j, the ballot of the ended lanes lists the endings, its first set bit is m (a scalar
-//     find-first-one: no vector shift), 64 steps per round - and writes idx, length and the T actions, rewards and done bytes.  The
+//   * the ring's wrap, the pick of a given pair, the look-ahead, its last step and what follows it, the frame rule, the pool row and
+//     the palette are tde_ring.h's (ring_slot, ring_pick, ring_ahead, ring_last, ring_shown, ring_pool_row, raster_expand): nothing of
+//     them is restated here.  The draw takes ring_pick's Philox words over a span that keeps a whole window inside the stored range.
+//   * two launches on the caller's stream.  sequence_scalars_kernel, one wavefront per window, finds the window's length m (ring_ahead,
+//     64 steps per round) and writes idx, length and the T actions, rewards and done bytes.  The
 //     gather that follows reads (idx, length) back: a window has up to T + n_stack = 264 gathering wavefronts, and one 12-byte load
 //     each replaces a Philox draw and up to four rounds of the length search per wavefront.
 //   * planes mode: output entry k, frame f (oldest first) shows source slot s + q, q = k - (n_stack - 1 - f) - entry m under a pool
@@ -46,22 +45,6 @@ TDE_DEV RingPick sequence_pick(const Args &s, int i)
     return p;
 }
 
-// m of the pick `p` (wave-uniform, by all 64 lanes; 0 for a pair that is no stored transition): tde_nstep.h's rule, 64 steps per round
-template <class Args>
-TDE_DEV int sequence_length(const Args &s, const RingPick &p, int lane)
-{
-    if (!p.ok) return 0;
-    const int a = min(s.T, s.count - p.off);            // (1 <= a <= C - 1: slot s + k is a stored slot for k < a)
-    for (int base = 0; base < a; base += 64) {
-        const int k = base + lane;
-        bool ended = false;
-        if (k < a) ended = (s.rp.done[(int64_t)ring_slot(p.slot, k, s.rp.C) * s.rp.B + p.env] & kRingEnded) != 0;
-        const unsigned long long ends = __ballot(ended);
-        if (ends) return base + __ffsll((long long)ends);
-    }
-    return a;
-}
-
 // one wavefront per window: its length, its indices and its T actions, rewards and done bytes
 template <class Args>
 __global__ __launch_bounds__(64 * kRingWaves) void sequence_scalars_kernel(Args s, int N)
@@ -70,7 +53,7 @@ __global__ __launch_bounds__(64 * kRingWaves) void sequence_scalars_kernel(Args 
     if (i >= N) return;
     const int C = s.rp.C, B = s.rp.B, T = s.T;
     const RingPick p = sequence_pick(s, i);
-    const int m = sequence_length(s, p, lane);
+    const int m = ring_ahead<TDE_SEQUENCE_MAX / 64>(s, p, s.T, lane);
     if (lane == 0) {
         s.idx[2 * (int64_t)i] = p.slot;
         s.idx[2 * (int64_t)i + 1] = p.env;
@@ -95,11 +78,8 @@ __global__ __launch_bounds__(64 * kRingWaves) void sequence_scalars_kernel(Args 
 }
 
 // what the gathers know of window i (wave-uniform): the pair and length the scalars kernel wrote, and the window's last step
-struct SequenceWindow {
+struct SequenceWindow : RingLast {
     int slot, env, off, m;              // m == 0: the pair is no stored transition (slot and env are then only echoes)
-    int64_t at_last;                    // the stored transition at slot L = s + m - 1
-    uint32_t done_last;
-    int row;                            // its pool row, or -1
 };
 
 template <class Args>
@@ -109,12 +89,10 @@ TDE_DEV SequenceWindow sequence_window(const Args &s, int i)
     w.m = s.length[i];
     w.slot = s.idx[2 * (int64_t)i];
     w.env = s.idx[2 * (int64_t)i + 1];
-    w.off = 0, w.at_last = 0, w.done_last = 0, w.row = -1;
+    w.off = 0, w.at_last = 0, w.done_last = 0, w.row = -1, w.live = false;
     if (w.m > 0) {
         w.off = ring_slot(w.slot, -s.first, s.rp.C);
-        w.at_last = (int64_t)ring_slot(w.slot, w.m - 1, s.rp.C) * s.rp.B + w.env;
-        w.done_last = s.rp.done[w.at_last];
-        w.row = ring_pool_row(s, w.at_last, w.done_last);
+        static_cast<RingLast &>(w) = ring_last(s, w.slot, w.env, w.m);
     }
     return w;
 }
@@ -142,7 +120,7 @@ __global__ __launch_bounds__(64 * kRingWaves) void sequence_planes_kernel(Args s
             // the terminal stack of L: the pool plane on top, the stack of L one frame down
             show = lane == 0 || ring_shown(lane - 1, s.rp.age[w.at_last], w.off + w.m - 1);
         } else {
-            // the stack of slot L + 1, zeros after an end
+            // the stack of slot L + 1, zeros after an end (w.live in its own words: read from the window it takes 4 more SGPRs without a pool)
             show = (w.done_last & kRingEnded) == 0 && ring_shown(lane, s.rp.age[(int64_t)ring_slot(w.slot, w.m, C) * B + w.env], w.off + w.m);
         }
     }
@@ -194,7 +172,7 @@ __global__ __launch_bounds__(64 * kRingWaves) void sequence_rows_kernel(Args s)
         } else if (k == w.m && w.m > 0) {
             if (w.row >= 0) {
                 if constexpr (Args::kPool) from = s.tm.pool + ((w.at_last / B) * s.tm.M + w.row) * D * 4;
-            } else if ((w.done_last & kRingEnded) == 0) {
+            } else if (w.live) {
                 from = s.rp.frames + ((int64_t)ring_slot(w.slot, k, C) * B + w.env) * D * 4;
             }
         }
@@ -233,21 +211,20 @@ int launch_sequence(const char *fn, const Args &s, int32_t N, void *stream)
     return launch_status(fn);
 }
 
-// what tde_sequence_sample takes after its structs (checked by the caller); fills the launch's argument block.  A sample's own
-// arguments go through check_sample, which wants a next_obs: the window has none, so obs stands in for it and the block's is cleared.
+// what tde_sequence_sample takes after its structs (checked by the caller); fills the launch's argument block
 template <class Args>
 int check_sequence(const char *fn, const tde_replay *rp, int32_t first, int32_t count, int32_t N, const int32_t *idx_in, uint64_t seed,
                    uint64_t draw, int32_t T, int32_t *idx, uint8_t *obs, float *action, float *reward, uint8_t *done, int32_t *length,
                    Args &s)
 {
     if (T < 1 || T > TDE_SEQUENCE_MAX) return bad_in(fn, "T must be in [1, 256]");
-    const int rc = check_sample(fn, rp, first, count, N, idx_in, seed, draw, idx, obs, obs, action, reward, done, s);
+    const int rc = check_sample(fn, rp, first, count, N, idx_in, seed, draw, idx, obs, nullptr, action, reward, done, s, false);
     if (rc) return rc;
     if (!length) return bad_in(fn, "a NULL output");
     if (!aligned(length, 4)) return bad_in(fn, "length must be 4-byte aligned");
-    s.next_obs = nullptr;
     s.T = T; s.length = length;
     s.vec = rp->plane == 0 && rp->D % 4 == 0 && aligned(obs, 16) && aligned(rp->frames, 16);
+    if constexpr (Args::kPool) s.vec = s.vec && aligned(s.tm.pool, 16);      // (s.tm is set already: with_ring_args copies *tm in before it runs the body)
     return 0;
 }
 
@@ -260,19 +237,8 @@ int tde_sequence_sample(const tde_replay *rp, const tde_terminal *tm, int32_t fi
                         int32_t *length, void *stream)
 {
     const char *fn = "tde_sequence_sample";
-    int rc;
-    if (tm) {
-        tde::SequenceArgs<tde::TerminalSampleArgs> s;
-        if ((rc = check_terminal_struct(fn, rp, tm)) != 0 ||
-            (rc = check_sequence(fn, rp, first, count, N, idx_in, seed, draw, T, idx, obs, action, reward, done, length, s)) != 0)
-            return rc;
-        s.tm = *tm;
-        if (s.vec && !aligned(tm->pool, 16)) s.vec = false;
-        return launch_sequence(fn, s, N, stream);
-    }
-    tde::SequenceArgs<tde::SampleArgs> s;
-    if ((rc = check_replay_struct(fn, rp)) != 0 ||
-        (rc = check_sequence(fn, rp, first, count, N, idx_in, seed, draw, T, idx, obs, action, reward, done, length, s)) != 0)
-        return rc;
-    return launch_sequence(fn, s, N, stream);
+    return with_ring_args<tde::SequenceArgs>(fn, rp, tm, [&](auto &s) {
+        const int rc = check_sequence(fn, rp, first, count, N, idx_in, seed, draw, T, idx, obs, action, reward, done, length, s);
+        return rc ? rc : launch_sequence(fn, s, N, stream);
+    });
 }

@@ -852,17 +852,49 @@ def _replay_src(rp, src, src_offset, src_stride, dev):
     return p + src_offset, src_stride
 
 
-def _sample_args(rp, dev, n, out, idx_in):
-    """what replay_sample and terminal_sample pass after (first, count): n, idx_in, and behind seed and draw the six outputs"""
-    n = int(n)
-    if n < 1:
+def _ring_call(dev, name, *args):
+    """the entry point `name` of the library with `args` and, behind them, the current stream of `dev`; a refusal raises"""
+    _lib.check(_call(dev, getattr(_lib.load(), name), *args, _lib.current_stream(dev)), name)
+
+
+def _u64(seed, draw):
+    """a seed and a draw counter as the two uint64 the entry points take"""
+    return int(seed) & (2**64 - 1), int(draw) & (2**64 - 1)
+
+
+# the scalar rules of a sample, each stated once: the wrappers below and ReplayBuffer's methods call these
+def _check_n(n):
+    if n is None or (n := int(n)) < 1:
         raise ValueError("n must be >= 1")
+    return n
+
+
+def _check_n_steps(n_steps):
+    if not 1 <= (n_steps := int(n_steps)) <= _abi.NSTEP_MAX:
+        raise ValueError(f"n_steps must be in [1, {_abi.NSTEP_MAX}], got {n_steps}")
+    return n_steps
+
+
+def _check_gamma(gamma):
+    if not 0.0 <= (gamma := float(gamma)) <= 1.0:
+        raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+    return gamma
+
+
+def _sample_args(rp, dev, n, out, idx_in, seed, draw, T=None):
+    """what the samplers pass after (first, count): n, idx_in, seed and draw, and behind them the outputs - the six of a transition or, with
+    T (sequence_sample), a window's: T + 1 observations and no next_observations, T actions, rewards and dones, and its length"""
+    n = _check_n(n)
     dt, per = _ring_frame(rp, stacked=True)
-    po, pn = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["next_observations"], dt, n * per, "next_observations", dev)
+    k, ko = (1, 1) if T is None else (T, T + 1)
+    po = _chk(out["observations"], dt, n * ko * per, "observations", dev)
+    pn = _chk(out["next_observations"], dt, n * per, "next_observations", dev) if T is None else None
     pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
-    pa, pr = _chk(out["actions"], torch.float32, 2 * n, "actions", dev), _chk(out["rewards"], torch.float32, n, "rewards", dev)
-    pd = _chk(out["dones"], torch.uint8, n, "dones", dev)
-    return (n, _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)), (pi, po, pn, pa, pr, pd)
+    pa, pr = _chk(out["actions"], torch.float32, 2 * n * k, "actions", dev), _chk(out["rewards"], torch.float32, n * k, "rewards", dev)
+    pd = _chk(out["dones"], torch.uint8, n * k, "dones", dev)
+    pl = _chk(out["lengths"], torch.int32, n, "lengths", dev) if T is not None else None
+    head = (n, _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True), *_u64(seed, draw))
+    return head, ((pi, po, pn, pa, pr, pd) if T is None else (pi, po, pa, pr, pd, pl))
 
 
 def replay_struct(C_, B, n_stack, plane, D, frames, action, reward, done, age):
@@ -885,7 +917,7 @@ def replay_begin(rp, dev, w, src, src_offset=0, src_stride=None, mask=None):
     dev = torch.device(dev)
     ps, stride = _replay_src(rp, src, src_offset, src_stride, dev)
     pm = _chk(mask, torch.uint8, rp.B, "mask", dev, optional=True)
-    _lib.check(_call(dev, _lib.load().tde_replay_begin, C.byref(rp), int(w), ps, stride, pm, _lib.current_stream(dev)), "tde_replay_begin")
+    _ring_call(dev, "tde_replay_begin", C.byref(rp), int(w), ps, stride, pm)
 
 
 def replay_push(rp, dev, w, action, reward, done_bits, src, src_offset=0, src_stride=None):
@@ -895,7 +927,7 @@ def replay_push(rp, dev, w, action, reward, done_bits, src, src_offset=0, src_st
     ps, stride = _replay_src(rp, src, src_offset, src_stride, dev)
     pa, pr = _chk(action, torch.float32, 2 * rp.B, "action", dev), _chk(reward, torch.float32, rp.B, "reward", dev)
     pd = _chk(done_bits, torch.uint8, rp.B, "done_bits", dev)
-    _lib.check(_call(dev, _lib.load().tde_replay_push, C.byref(rp), int(w), pa, pr, pd, ps, stride, _lib.current_stream(dev)), "tde_replay_push")
+    _ring_call(dev, "tde_replay_push", C.byref(rp), int(w), pa, pr, pd, ps, stride)
 
 
 def replay_sample(rp, dev, first, count, n, out, idx_in=None, seed=0, draw=0):
@@ -903,9 +935,8 @@ def replay_sample(rp, dev, first, count, n, out, idx_in=None, seed=0, draw=0):
     "next_observations" uint8 [n, 3 * n_stack, plane] (planes mode) or float32 [n, D] (rows mode), "actions" float32 [n, 2],
     "rewards" float32 [n], "dones" uint8 [n] - drawn from (seed, draw) or, with idx_in (int32 [n, 2] (slot, env) pairs), as given"""
     dev = torch.device(dev)
-    head, outs = _sample_args(rp, dev, n, out, idx_in)
-    _lib.check(_call(dev, _lib.load().tde_replay_sample, C.byref(rp), int(first), int(count), *head, int(seed) & (2**64 - 1),
-                     int(draw) & (2**64 - 1), *outs, _lib.current_stream(dev)), "tde_replay_sample")
+    head, outs = _sample_args(rp, dev, n, out, idx_in, seed, draw)
+    _ring_call(dev, "tde_replay_sample", C.byref(rp), int(first), int(count), *head, *outs)
     return out
 
 
@@ -924,8 +955,8 @@ def replay_pack_struct(B, plane, scratch):
 def replay_pack(rp, dev, rgb, planes):
     """tde_replay_pack on the current stream: colour observations uint8 [B, 3, plane] back to layer planes uint8 [B, plane]"""
     dev = torch.device(dev)
-    _lib.check(_call(dev, _lib.load().tde_replay_pack, C.byref(rp), _chk(rgb, torch.uint8, rp.B * 3 * rp.plane, "rgb", dev), 3 * rp.plane,
-                     _chk(planes, torch.uint8, rp.B * rp.plane, "planes", dev), rp.plane, _lib.current_stream(dev)), "tde_replay_pack")
+    _ring_call(dev, "tde_replay_pack", C.byref(rp), _chk(rgb, torch.uint8, rp.B * 3 * rp.plane, "rgb", dev), 3 * rp.plane,
+               _chk(planes, torch.uint8, rp.B * rp.plane, "planes", dev), rp.plane)
     return planes
 
 
@@ -940,8 +971,7 @@ def gae(rp, dev, first, count, T, values, last_values, gamma, lam, advantages, r
     n = T * rp.B
     pv, pl = _chk(values, torch.float32, n, "values", dev), _chk(last_values, torch.float32, rp.B, "last_values", dev)
     pa, pr = _chk(advantages, torch.float32, n, "advantages", dev), _chk(returns, torch.float32, n, "returns", dev)
-    _lib.check(_call(dev, _lib.load().tde_gae, C.byref(rp), int(first), int(count), T, pv, pl, float(gamma), float(lam), pa, pr,
-                     _lib.current_stream(dev)), "tde_gae")
+    _ring_call(dev, "tde_gae", C.byref(rp), int(first), int(count), T, pv, pl, float(gamma), float(lam), pa, pr)
     return advantages, returns
 
 
@@ -963,8 +993,7 @@ def onpolicy_gather(rp, dev, first, count, T, idx, values, log_probs, advantages
     dt, per = _ring_frame(rp, stacked=True)
     po, pa = _chk(out["observations"], dt, n * per, "observations", dev), _chk(out["actions"], torch.float32, 2 * n, "actions", dev)
     dst = [_chk(out[k], torch.float32, n, k, dev) for k in ("old_values", "old_log_prob", "advantages", "returns")]
-    _lib.check(_call(dev, _lib.load().tde_onpolicy_gather, C.byref(rp), int(first), int(count), T, n, pi, *src, po, pa, *dst,
-                     _lib.current_stream(dev)), "tde_onpolicy_gather")
+    _ring_call(dev, "tde_onpolicy_gather", C.byref(rp), int(first), int(count), T, n, pi, *src, po, pa, *dst)
     return out
 
 
@@ -992,8 +1021,7 @@ def terminal_stash(dev, done_bits, src, src_offset, src_stride, dst):
     pt = _chk(dst, dst.dtype, None, "dst", dev)
     src_offset, src_stride = int(src_offset), int(src_stride)
     _src_bounds(src, B, row, src_offset, src_stride)
-    _lib.check(_call(dev, _lib.load().tde_terminal_stash, B, row, pd, ps + src_offset, src_stride, pt, _lib.current_stream(dev)),
-               "tde_terminal_stash")
+    _ring_call(dev, "tde_terminal_stash", B, row, pd, ps + src_offset, src_stride, pt)
     return dst
 
 
@@ -1004,17 +1032,15 @@ def terminal_push(rp, tm, dev, w, done_bits, term_src):
     dt, per = _ring_frame(rp)
     pd = _chk(done_bits, torch.uint8, rp.B, "done_bits", dev)
     ps = _chk(term_src, dt, rp.B * per, "term_src", dev)
-    _lib.check(_call(dev, _lib.load().tde_terminal_push, C.byref(rp), C.byref(tm), int(w), pd, ps, per * term_src.element_size(),
-                     _lib.current_stream(dev)), "tde_terminal_push")
+    _ring_call(dev, "tde_terminal_push", C.byref(rp), C.byref(tm), int(w), pd, ps, per * term_src.element_size())
 
 
 def terminal_sample(rp, tm, dev, first, count, n, out, idx_in=None, seed=0, draw=0):
     """tde_terminal_sample on the current stream: replay_sample's arguments and outputs; where a transition ended its episode and its
     terminal frame is in the pool, "next_observations" is the terminal observation and "dones" carries _abi.TERMINAL_HAS"""
     dev = torch.device(dev)
-    head, outs = _sample_args(rp, dev, n, out, idx_in)
-    _lib.check(_call(dev, _lib.load().tde_terminal_sample, C.byref(rp), C.byref(tm), int(first), int(count), *head,
-                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), *outs, _lib.current_stream(dev)), "tde_terminal_sample")
+    head, outs = _sample_args(rp, dev, n, out, idx_in, seed, draw)
+    _ring_call(dev, "tde_terminal_sample", C.byref(rp), C.byref(tm), int(first), int(count), *head, *outs)
     return out
 
 
@@ -1023,17 +1049,16 @@ def nstep_sample(rp, tm, dev, first, count, n, n_steps, gamma, out, idx_in=None,
     """tde_nstep_sample on the current stream: replay_sample's (tm None) / terminal_sample's arguments and outputs with a look-ahead of
     up to `n_steps` stored steps - "rewards" is the discounted sum over the m steps taken, "next_observations" and "dones" are those of
     the last of them - and two more tensors of `out`: "discounts" float32 [n] (gamma ** m) and "steps" uint8 [n] (m)"""
+    return _nstep_sample(rp, tm, dev, first, count, n, _check_n_steps(n_steps), _check_gamma(gamma), out, idx_in, seed, draw)
+
+
+def _nstep_sample(rp, tm, dev, first, count, n, n_steps, gamma, out, idx_in=None, seed=0, draw=0):
+    """nstep_sample with an n_steps and a gamma that have passed their rules (ReplayBuffer checks them first, in its methods' own order)"""
     dev = torch.device(dev)
-    n_steps, gamma = int(n_steps), float(gamma)
-    if not 1 <= n_steps <= _abi.NSTEP_MAX:
-        raise ValueError(f"n_steps must be in [1, {_abi.NSTEP_MAX}], got {n_steps}")
-    if not 0.0 <= gamma <= 1.0:
-        raise ValueError(f"gamma must be in [0, 1], got {gamma}")
-    head, outs = _sample_args(rp, dev, n, out, idx_in)
+    head, outs = _sample_args(rp, dev, n, out, idx_in, seed, draw)
     pg, ps = _chk(out["discounts"], torch.float32, head[0], "discounts", dev), _chk(out["steps"], torch.uint8, head[0], "steps", dev)
-    _lib.check(_call(dev, _lib.load().tde_nstep_sample, C.byref(rp), None if tm is None else C.byref(tm), int(first), int(count), *head,
-                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), n_steps, gamma, *outs, pg, ps, _lib.current_stream(dev)),
-               "tde_nstep_sample")
+    _ring_call(dev, "tde_nstep_sample", C.byref(rp), None if tm is None else C.byref(tm), int(first), int(count), *head,
+               n_steps, gamma, *outs, pg, ps)
     return out
 
 
@@ -1057,15 +1082,14 @@ def priority_struct(rp, leaf, sums, qmax):
 def priority_reset(pr, rp, dev):
     """tde_priority_reset on the current stream: every leaf and sum zero, qmax = PRIORITY_ONE"""
     dev = torch.device(dev)
-    _lib.check(_call(dev, _lib.load().tde_priority_reset, C.byref(pr), C.byref(rp), _lib.current_stream(dev)), "tde_priority_reset")
+    _ring_call(dev, "tde_priority_reset", C.byref(pr), C.byref(rp))
 
 
 def priority_push(pr, rp, dev, w, first, count):
     """tde_priority_push on the current stream, after replay_push filled slot `w`: first and count are the host's values after it
     advanced.  The pushed pairs enter with qmax, the open slot and the stacks the ring just overwrote leave"""
     dev = torch.device(dev)
-    _lib.check(_call(dev, _lib.load().tde_priority_push, C.byref(pr), C.byref(rp), int(w), int(first), int(count), _lib.current_stream(dev)),
-               "tde_priority_push")
+    _ring_call(dev, "tde_priority_push", C.byref(pr), C.byref(rp), int(w), int(first), int(count))
 
 
 def priority_update(pr, rp, dev, first, count, idx, p):
@@ -1077,20 +1101,16 @@ def priority_update(pr, rp, dev, first, count, idx, p):
     if n < 1:
         raise ValueError("p must hold at least one priority")
     pi = _chk(idx, torch.int32, 2 * n, "idx", dev)
-    _lib.check(_call(dev, _lib.load().tde_priority_update, C.byref(pr), C.byref(rp), int(first), int(count), n, pi, pp,
-                     _lib.current_stream(dev)), "tde_priority_update")
+    _ring_call(dev, "tde_priority_update", C.byref(pr), C.byref(rp), int(first), int(count), n, pi, pp)
 
 
 def priority_sample(pr, rp, dev, first, count, n, idx, q, seed=0, draw=0):
     """tde_priority_sample on the current stream: `n` pairs drawn in proportion to their priorities from (seed, draw) into idx int32
     [n, 2] (slot, env) and their priorities into q int32 [n]; (-1, -1) and 0 when nothing is drawable"""
     dev = torch.device(dev)
-    n = int(n)
-    if n < 1:
-        raise ValueError("n must be >= 1")
+    n = _check_n(n)
     pi, pq = _chk(idx, torch.int32, 2 * n, "idx", dev), _chk(q, torch.int32, n, "q", dev)
-    _lib.check(_call(dev, _lib.load().tde_priority_sample, C.byref(pr), C.byref(rp), int(first), int(count), n, int(seed) & (2**64 - 1),
-                     int(draw) & (2**64 - 1), pi, pq, _lib.current_stream(dev)), "tde_priority_sample")
+    _ring_call(dev, "tde_priority_sample", C.byref(pr), C.byref(rp), int(first), int(count), n, *_u64(seed, draw), pi, pq)
     return idx, q
 
 
@@ -1101,18 +1121,9 @@ def sequence_sample(rp, tm, dev, first, count, n, T, out, idx_in=None, seed=0, d
     "actions" float32 [n, T, 2], "rewards" float32 [n, T], "dones" uint8 [n, T], "lengths" int32 [n], "indices" int32 [n, 2] - whose
     starts are drawn from (seed, draw) or, with idx_in (int32 [n, 2] (slot, env) pairs), as given"""
     dev = torch.device(dev)
-    n, T = int(n), int(T)
+    T = int(T)
     if not 1 <= T <= _abi.SEQUENCE_MAX:
         raise ValueError(f"T must be in [1, {_abi.SEQUENCE_MAX}], got {T}")
-    if n < 1:
-        raise ValueError("n must be >= 1")
-    dt, per = _ring_frame(rp, stacked=True)
-    po = _chk(out["observations"], dt, n * (T + 1) * per, "observations", dev)
-    pi = _chk(out["indices"], torch.int32, 2 * n, "indices", dev)
-    pa, pr = _chk(out["actions"], torch.float32, 2 * n * T, "actions", dev), _chk(out["rewards"], torch.float32, n * T, "rewards", dev)
-    pd, pl = _chk(out["dones"], torch.uint8, n * T, "dones", dev), _chk(out["lengths"], torch.int32, n, "lengths", dev)
-    pin = _chk(idx_in, torch.int32, 2 * n, "idx", dev, optional=True)
-    _lib.check(_call(dev, _lib.load().tde_sequence_sample, C.byref(rp), None if tm is None else C.byref(tm), int(first), int(count), n, pin,
-                     int(seed) & (2**64 - 1), int(draw) & (2**64 - 1), T, pi, po, pa, pr, pd, pl, _lib.current_stream(dev)),
-               "tde_sequence_sample")
+    head, outs = _sample_args(rp, dev, n, out, idx_in, seed, draw, T)
+    _ring_call(dev, "tde_sequence_sample", C.byref(rp), None if tm is None else C.byref(tm), int(first), int(count), *head, T, *outs)
     return out

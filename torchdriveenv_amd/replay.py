@@ -34,6 +34,17 @@ import torch
 
 from . import _abi, ops
 from .config import check_prioritized
+from .ops import _check_gamma, _check_n, _check_n_steps
+
+
+def _ended(d):
+    """the done byte(s) `d` of a stored step: it ended its episode or was cut - the next slot is not its next observation"""
+    return (d & (3 | _abi.REPLAY_CUT)) != 0
+
+
+def _bootstraps(d):
+    """the done byte(s) `d` of a sample's last step: it did not end, or it was truncated and its terminal observation is there"""
+    return ~_ended(d) | (((d & 3) == 2) & ((d & _abi.TERMINAL_HAS) != 0))
 
 
 class ReplaySamples(namedtuple("ReplaySamples", ["observations", "actions", "next_observations", "dones", "rewards", "indices"])):
@@ -45,15 +56,14 @@ class ReplaySamples(namedtuple("ReplaySamples", ["observations", "actions", "nex
     @property
     def terminal(self):
         """bool [n]: the transition has no next observation (terminated, truncated, or cut by a reset of the caller's)"""
-        return (self.dones & (3 | _abi.REPLAY_CUT)) != 0
+        return _ended(self.dones)
 
     @property
     def bootstrap(self):
         """bool [n]: the learner should bootstrap from next_observations - the transition did not end (not terminal), or it was
         truncated, not terminated, and its terminal observation is there (dones & TERMINAL_HAS: a terminal_obs env; SB3's
         handle_timeout_termination)"""
-        d = self.dones
-        return ((d & (3 | _abi.REPLAY_CUT)) == 0) | (((d & 3) == 2) & ((d & _abi.TERMINAL_HAS) != 0))
+        return _bootstraps(self.dones)
 
 
 class NStepSamples(namedtuple("NStepSamples", ReplaySamples._fields + ("discounts", "steps"))):
@@ -99,13 +109,12 @@ class SequenceSamples(namedtuple("SequenceSamples", ["observations", "actions", 
     @property
     def terminal(self):
         """bool [n]: ReplaySamples.terminal of the window's last step (step lengths - 1)"""
-        return (self._last_done & (3 | _abi.REPLAY_CUT)) != 0
+        return _ended(self._last_done)
 
     @property
     def bootstrap(self):
         """bool [n]: ReplaySamples.bootstrap of the window's last step: the learner should bootstrap from observations[i, lengths[i]]"""
-        d = self._last_done
-        return ((d & (3 | _abi.REPLAY_CUT)) == 0) | (((d & 3) == 2) & ((d & _abi.TERMINAL_HAS) != 0))
+        return _bootstraps(self._last_done)
 
 
 def priority_weights(q, beta):
@@ -115,6 +124,14 @@ def priority_weights(q, beta):
     qd = q.to(torch.float64)
     smallest = torch.where(live, qd, torch.full_like(qd, float("inf"))).min()
     return torch.where(live, (smallest / qd.clamp(min=1.0)) ** float(beta), torch.zeros_like(qd)).to(torch.float32)
+
+
+def _cached(cache, key, alloc, *args):
+    """cache[key], made by alloc(*args) the first time: an output set is kept per size and reused by the next sample of that size"""
+    out = cache.get(key)
+    if out is None:
+        out = cache[key] = alloc(*args)
+    return out
 
 
 class ReplayBuffer:
@@ -199,10 +216,8 @@ class ReplayBuffer:
             self.pstruct = ops.priority_struct(self.struct, self.leaf, self.sums, self.qmax)
         self.first = self.w = self.count = self.draws = 0
         self._begun = False
-        self._out = {}
-        self._nstep_out = {}
-        self._prio_out = {}
-        self._seq_out = {}
+        self._out = {}                  # sample()'s output sets by n; _sets: the other samplers' by (kind, n[, T])
+        self._sets = {}
 
     # ---- bookkeeping --------------------------------------------------------------------------------------------------------
     def __len__(self):
@@ -290,41 +305,31 @@ class ReplayBuffer:
 
     def _buffers(self, n):
         """the output set of sample(n), kept per size (a learner draws a handful of fixed minibatch sizes)"""
-        out = self._out.get(n)
-        if out is None:
-            out = self._out[n] = self._alloc(n)
-        return out
+        return _cached(self._out, n, self._alloc, n)
+
+    def _alloc_nstep(self, n):
+        return {**self._alloc(n), "discounts": torch.empty(n, dtype=torch.float32, device=self.dev),
+                "steps": torch.empty(n, dtype=torch.uint8, device=self.dev)}
+
+    def _alloc_sequence(self, n, T):
+        obs = ((n, T + 1, 3 * self.n_stack, self.H, self.W), torch.uint8) if self.planes else ((n, T + 1, self.D), torch.float32)
+        return {"observations": torch.empty(obs[0], dtype=obs[1], device=self.dev),
+                "actions": torch.empty((n, T, 2), dtype=torch.float32, device=self.dev),
+                "rewards": torch.empty((n, T), dtype=torch.float32, device=self.dev),
+                "dones": torch.empty((n, T), dtype=torch.uint8, device=self.dev),
+                "lengths": torch.empty(n, dtype=torch.int32, device=self.dev),
+                "indices": torch.empty((n, 2), dtype=torch.int32, device=self.dev)}
 
     def sample(self, n, idx=None, check=True):
         """`n` transitions -> ReplaySamples, drawn on the device from (seed, the buffer's draw counter) - or, with idx (int [n, 2]
         (slot, env) pairs; n may be None), those.  check (idx only): refuse pairs that are not valid_pairs() - one host
         synchronisation; without it such a pair gathers zeros or blank older frames."""
-        if idx is not None:
-            idx = torch.as_tensor(idx, device=self.dev).to(torch.int32).reshape(-1, 2).contiguous()
-            if n is None:
-                n = idx.shape[0]
-            if idx.shape[0] != int(n):
-                raise ValueError(f"idx must hold {n} (slot, env) pairs")
-        if n is None or int(n) < 1:
-            raise ValueError("n must be >= 1")
-        n = int(n)
-        if self.count < 1:
-            raise ValueError("the buffer holds no transition yet")
-        if idx is None and self.count <= self.n_stack - 1:
-            raise ValueError(f"sample() draws steps whose whole frame stack is in the ring: it needs more than {self.n_stack - 1} stored steps, the buffer holds {self.count}")
-        if idx is not None and check:
-            s, e = idx[:, 0].long(), idx[:, 1].long()
-            ok = (s >= 0) & (s < self.C) & (e >= 0) & (e < self.B)
-            off = (s.clamp(0, self.C - 1) - self.first) % self.C
-            ok &= off < self.count
-            ok &= torch.clamp(self.age[s.clamp(0, self.C - 1), e.clamp(0, self.B - 1)].long(), max=self.n_stack - 1) <= off
-            if not bool(ok.all()):
-                raise ValueError("idx holds pairs that are not stored transitions with their whole frame stack in the ring (valid_pairs())")
+        n, idx = self._request(n, idx, check, "sample()")
+        out = _cached(self._out, n, self._alloc, n)
         if self.tstruct is not None:
-            out = ops.terminal_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, self._buffers(n), idx, self.seed,
-                                      self.draws)
+            ops.terminal_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, out, idx, self.seed, self.draws)
         else:
-            out = ops.replay_sample(self.struct, self.dev, self.first, self.count, n, self._buffers(n), idx, self.seed, self.draws)
+            ops.replay_sample(self.struct, self.dev, self.first, self.count, n, out, idx, self.seed, self.draws)
         if idx is None:
             self.draws += 1
         return ReplaySamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"], out["indices"])
@@ -334,17 +339,10 @@ class ReplayBuffer:
         with a look-ahead of up to `n_steps` (1 .. NSTEP_MAX) stored steps from each picked step, which stops at the first step that
         ended its episode or was cut, and at the newest stored step.  One launch (tde_nstep_sample), through the terminal pool when
         the buffer has one.  The tensors it returns are its own, reused by the next sample_nstep of the same size."""
-        n_steps, gamma = int(n_steps), float(gamma)
-        if not 1 <= n_steps <= _abi.NSTEP_MAX:
-            raise ValueError(f"n_steps must be in [1, {_abi.NSTEP_MAX}], got {n_steps}")
-        if not 0.0 <= gamma <= 1.0:
-            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        n_steps, gamma = _check_n_steps(n_steps), _check_gamma(gamma)
         n, idx = self._request(n, idx, check)
-        out = self._nstep_out.get(n)
-        if out is None:
-            out = self._nstep_out[n] = {**self._alloc(n), "discounts": torch.empty(n, dtype=torch.float32, device=self.dev),
-                                        "steps": torch.empty(n, dtype=torch.uint8, device=self.dev)}
-        ops.nstep_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, n_steps, gamma, out, idx, self.seed, self.draws)
+        out = _cached(self._sets, ("nstep", n), self._alloc_nstep, n)
+        ops._nstep_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, n_steps, gamma, out, idx, self.seed, self.draws)
         if idx is None:
             self.draws += 1
         return NStepSamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"], out["indices"],
@@ -354,6 +352,30 @@ class ReplayBuffer:
         if getattr(self, "pstruct", None) is None:
             raise ValueError(f"{what} needs a buffer built with prioritized=Prioritized(...)")
 
+    def _beta(self, beta):
+        """the exponent of the importance weights: the caller's, or the Prioritized's"""
+        beta = float(self.prioritized.beta if beta is None else beta)
+        if not 0.0 <= beta <= 1.0:
+            raise ValueError(f"beta must be in [0, 1], got {beta}")
+        return beta
+
+    def _prioritized_pick(self, n, beta, key, alloc, gather, *scalars):
+        """the prioritized pick of `n` checked pairs, for sample_prioritized() and sample_sequence(prioritized=True): the output set
+        `key` = (kind, *what `alloc` takes) with "picked" and "priorities" beside what `alloc` makes, tde_priority_sample from (seed, the
+        draw counter), the gather (ops._nstep_sample or ops.sequence_sample, `scalars` between n and the outputs) of the picked pairs, and
+        the counter's advance -> (out, weights under `beta`)"""
+        if self.count < 1:
+            raise ValueError("the buffer holds no transition yet")
+        out = _cached(self._sets, key, alloc, *key[1:])
+        if "picked" not in out:
+            out["picked"] = torch.empty((n, 2), dtype=torch.int32, device=self.dev)
+            out["priorities"] = torch.empty(n, dtype=torch.int32, device=self.dev)
+        ops.priority_sample(self.pstruct, self.struct, self.dev, self.first, self.count, n, out["picked"], out["priorities"], self.seed,
+                            self.draws)
+        gather(self.struct, self.tstruct, self.dev, self.first, self.count, n, *scalars, out, out["picked"])
+        self.draws += 1
+        return out, priority_weights(out["priorities"], beta)
+
     def sample_prioritized(self, n, n_steps=1, gamma=0.99, beta=None):
         """`n` transitions drawn in proportion to their priorities -> PrioritizedSamples: sample_nstep()'s batch (n_steps = 1: sample()'s)
         of the picked pairs, their integer priorities, and the importance weights under `beta` (None: the Prioritized's).  Two launches:
@@ -361,31 +383,10 @@ class ReplayBuffer:
         and tde_nstep_sample with the picked pairs, through the terminal pool when the buffer has one.  The tensors it returns are its
         own, reused by the next sample_prioritized of the same size."""
         self._need_priorities("sample_prioritized()")
-        if n is None or int(n) < 1:
-            raise ValueError("n must be >= 1")
-        n, n_steps, gamma = int(n), int(n_steps), float(gamma)
-        beta = float(self.prioritized.beta if beta is None else beta)
-        if not 1 <= n_steps <= _abi.NSTEP_MAX:
-            raise ValueError(f"n_steps must be in [1, {_abi.NSTEP_MAX}], got {n_steps}")
-        if not 0.0 <= gamma <= 1.0:
-            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
-        if not 0.0 <= beta <= 1.0:
-            raise ValueError(f"beta must be in [0, 1], got {beta}")
-        if self.count < 1:
-            raise ValueError("the buffer holds no transition yet")
-        out = self._prio_out.get(n)
-        if out is None:
-            out = self._prio_out[n] = {**self._alloc(n), "discounts": torch.empty(n, dtype=torch.float32, device=self.dev),
-                                       "steps": torch.empty(n, dtype=torch.uint8, device=self.dev),
-                                       "picked": torch.empty((n, 2), dtype=torch.int32, device=self.dev),
-                                       "priorities": torch.empty(n, dtype=torch.int32, device=self.dev)}
-        ops.priority_sample(self.pstruct, self.struct, self.dev, self.first, self.count, n, out["picked"], out["priorities"], self.seed,
-                            self.draws)
-        ops.nstep_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, n_steps, gamma, out, out["picked"])
-        self.draws += 1
+        n, n_steps, gamma, beta = _check_n(n), _check_n_steps(n_steps), _check_gamma(gamma), self._beta(beta)
+        out, weights = self._prioritized_pick(n, beta, ("prioritized", n), self._alloc_nstep, ops._nstep_sample, n_steps, gamma)
         return PrioritizedSamples(out["observations"], out["actions"], out["next_observations"], out["dones"], out["rewards"],
-                                  out["indices"], out["discounts"], out["steps"], out["priorities"],
-                                  priority_weights(out["priorities"], beta))
+                                  out["indices"], out["discounts"], out["steps"], out["priorities"], weights)
 
     def update_priorities(self, indices, td_errors):
         """the learner's TD errors of a batch: the pairs `indices` (int [n, 2]: batch.indices) take the priority (|td| + eps) ** alpha
@@ -420,58 +421,36 @@ class ReplayBuffer:
         T = int(length)
         if not 1 <= T <= _abi.SEQUENCE_MAX:
             raise ValueError(f"length must be in [1, {_abi.SEQUENCE_MAX}], got {T}")
+        priorities = weights = None
         if prioritized:
             self._need_priorities("sample_sequence(prioritized=True)")
             if idx is not None:
                 raise ValueError("sample_sequence() takes idx or prioritized=True, not both")
-            beta = float(self.prioritized.beta if beta is None else beta)
-            if not 0.0 <= beta <= 1.0:
-                raise ValueError(f"beta must be in [0, 1], got {beta}")
-            if n is None or int(n) < 1:
-                raise ValueError("n must be >= 1")
-            if self.count < 1:
-                raise ValueError("the buffer holds no transition yet")
-            n = int(n)
+            beta, n = self._beta(beta), _check_n(n)
+            out, weights = self._prioritized_pick(n, beta, ("sequence", n, T), self._alloc_sequence, ops.sequence_sample, T)
+            priorities = out["priorities"]
         else:
             if beta is not None:
                 raise ValueError("beta needs prioritized=True")
             n, idx = self._request(n, idx, check, "sample_sequence()")
-        out = self._seq_out.get((n, T))
-        if out is None:
-            obs = ((n, T + 1, 3 * self.n_stack, self.H, self.W), torch.uint8) if self.planes else ((n, T + 1, self.D), torch.float32)
-            out = self._seq_out[(n, T)] = {"observations": torch.empty(obs[0], dtype=obs[1], device=self.dev),
-                                           "actions": torch.empty((n, T, 2), dtype=torch.float32, device=self.dev),
-                                           "rewards": torch.empty((n, T), dtype=torch.float32, device=self.dev),
-                                           "dones": torch.empty((n, T), dtype=torch.uint8, device=self.dev),
-                                           "lengths": torch.empty(n, dtype=torch.int32, device=self.dev),
-                                           "indices": torch.empty((n, 2), dtype=torch.int32, device=self.dev)}
-        priorities = weights = None
-        if prioritized:
-            if "picked" not in out:
-                out["picked"] = torch.empty((n, 2), dtype=torch.int32, device=self.dev)
-                out["priorities"] = torch.empty(n, dtype=torch.int32, device=self.dev)
-            ops.priority_sample(self.pstruct, self.struct, self.dev, self.first, self.count, n, out["picked"], out["priorities"], self.seed,
-                                self.draws)
-            ops.sequence_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, T, out, out["picked"])
-            priorities, weights = out["priorities"], priority_weights(out["priorities"], beta)
-        else:
+            out = _cached(self._sets, ("sequence", n, T), self._alloc_sequence, n, T)
             ops.sequence_sample(self.struct, self.tstruct, self.dev, self.first, self.count, n, T, out, idx, self.seed, self.draws)
-        if idx is None:
-            self.draws += 1
+            if idx is None:
+                self.draws += 1
         return SequenceSamples(out["observations"], out["actions"], out["rewards"], out["dones"], out["lengths"], out["indices"],
                                priorities, weights)
 
     def _request(self, n, idx, check, what="sample_nstep()"):
-        """(n, idx) of a sample_nstep / sample_sequence call as the launch takes them, under the rules sample() states for its own
-        arguments"""
+        """(n, idx) of a sample / sample_nstep / sample_sequence call as the launch takes them: idx as int32 [n, 2] on the device, n from
+        it when None; refuses an empty request, an empty buffer, a draw before a whole frame stack is stored and, under `check` (one
+        host synchronisation), pairs that are not valid_pairs()"""
         if idx is not None:
             idx = torch.as_tensor(idx, device=self.dev).to(torch.int32).reshape(-1, 2).contiguous()
             if n is None:
                 n = idx.shape[0]
             if idx.shape[0] != int(n):
                 raise ValueError(f"idx must hold {n} (slot, env) pairs")
-        if n is None or int(n) < 1:
-            raise ValueError("n must be >= 1")
+        n = _check_n(n)
         if self.count < 1:
             raise ValueError("the buffer holds no transition yet")
         if idx is None and self.count <= self.n_stack - 1:
@@ -484,7 +463,7 @@ class ReplayBuffer:
             ok &= (off < self.count) & (torch.clamp(self.age[s, e].long(), max=self.n_stack - 1) <= off)
             if not bool(ok.all()):
                 raise ValueError("idx holds pairs that are not stored transitions with their whole frame stack in the ring (valid_pairs())")
-        return int(n), idx
+        return n, idx
 
     @property
     def _tensors(self):
