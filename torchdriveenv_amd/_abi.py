@@ -220,6 +220,21 @@ PRIORITY_ONE, PRIORITY_QMAX, PRIORITY_TAG = 1 << 16, 1 << 28, 0x5052      # q of
 TDE_SEQUENCE_VERSION = 1         # include/tde_sequence.h
 SEQUENCE_MAX = 256               # the longest window of a sequence sample
 
+
+class TdeSnapshotFrames(C.Structure):
+    """tde_snapshot_frames (include/tde_snapshot.h): the frame-stack ring of the rows tde_state_copy moves; device addresses"""
+    _fields_ = [("src_layers", _p), ("dst_layers", _p), ("src_obs", _p), ("dst_obs", _p), ("n_stack", C.c_int32), ("plane", C.c_int32),
+                ("src_phase", C.c_int32), ("dst_phase", C.c_int32)]
+
+
+TDE_SNAPSHOT_VERSION = 1         # include/tde_snapshot.h
+SNAPSHOT_OUTPUTS, SNAPSHOT_CHECK, SNAPSHOT_MAX_STACK = 1 << 0, 1 << 1, 8
+# the group of every tde_state array under tde_state_copy (the header's list): copied always, copied with SNAPSHOT_OUTPUTS, invalidated
+SNAPSHOT_COPIED = (STATE_AGENT_F32 + STATE_AGENT_I32 + STATE_AGENT_U8 + ["slot_route"] + STATE_ENV_I32 + ["action", "obs", "ep_return"])
+SNAPSHOT_OUTPUT_ARRAYS = ["reward", "terminated", "truncated", "tl_violation", "done_bits", "info", "info_reached", "ep_final",
+                          "ep_final_len", "magnitudes"]
+SNAPSHOT_INVALIDATED = ["slot_cache", "env_cache", "act_cache"]
+
 LAYER_BLANK = 5
 LAYER_STOP_RED, LAYER_STOP_GO = 6, 7
 RENDER_LEFT_HANDED, RENDER_PLAIN_EGO = 1 << 0, 1 << 1

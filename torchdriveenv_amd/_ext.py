@@ -24,7 +24,8 @@ def build(force=False, verbose=False):
 
     libbuild.build()
     _lib.load()                                   # mapped first: the fresh extension is test-loaded at the end of the build
-    deps = [SRC, os.path.join(_PKG, "..", "include", "tde_hip.h"), os.path.join(_PKG, "..", "include", "tde_abi.h")]
+    deps = [SRC, os.path.join(_PKG, "..", "include", "tde_hip.h"), os.path.join(_PKG, "..", "include", "tde_abi.h"),
+            os.path.join(_PKG, "..", "include", "tde_snapshot.h")]
     if not force and os.path.exists(SO_PATH) and os.path.getmtime(SO_PATH) >= max(os.path.getmtime(p) for p in deps):
         return SO_PATH
     os.makedirs(BUILD_DIR, exist_ok=True)

@@ -24,6 +24,8 @@ PRIORITY_SYMBOLS = ["tde_priority_version", "tde_priority_words", "tde_priority_
                     "tde_priority_sample"]
 # every symbol include/tde_sequence.h declares (additive over the terminal header: TDE_SEQUENCE_VERSION)
 SEQUENCE_SYMBOLS = ["tde_sequence_version", "tde_sequence_sample"]
+# every symbol include/tde_snapshot.h declares (additive over tde_hip.h: TDE_SNAPSHOT_VERSION)
+SNAPSHOT_SYMBOLS = ["tde_snapshot_version", "tde_state_copy"]
 
 _lib = None
 
@@ -152,6 +154,15 @@ def load():
     L.tde_sequence_version.argtypes = []
     L.tde_sequence_sample.argtypes = [rpp, tmp, i32, i32, i32, vp, u64, u64, i32] + [vp] * 6 + [vp]
     for s in SEQUENCE_SYMBOLS:
+        getattr(L, s).restype = C.c_int
+    missing = [s for s in SNAPSHOT_SYMBOLS if not hasattr(L, s)]
+    if missing:
+        raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")
+    if L.tde_snapshot_version() != _abi.TDE_SNAPSHOT_VERSION:
+        raise TdeError(f"snapshot version mismatch: library {L.tde_snapshot_version()} vs python {_abi.TDE_SNAPSHOT_VERSION}")
+    L.tde_snapshot_version.argtypes = []
+    L.tde_state_copy.argtypes = [sp, sp, i32, vp, vp, C.POINTER(_abi.TdeSnapshotFrames), C.c_uint32, vp]
+    for s in SNAPSHOT_SYMBOLS:
         getattr(L, s).restype = C.c_int
     _lib = L
     return L

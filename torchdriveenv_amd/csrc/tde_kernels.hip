@@ -30,4 +30,5 @@
 #include "tde_forecast.hip"
 #include "tde_forecast_scene.hip"
 #include "tde_plan_scene.hip"
+#include "tde_snapshot.hip"
 #endif

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "tde_hip.h"
+#include "tde_snapshot.h"
 
 namespace {
 
@@ -509,6 +510,9 @@ class EnvHandle {
     int64_t flags() const { return cfg_.flags; }
     int64_t num_envs() const { return state_.B; }
     int64_t agents_per_env() const { return state_.A; }
+    // (for state_copy below, which launches on two handles' states)
+    const tde_state &state() const { return state_; }
+    const at::Device &device() const { return dev_; }
 
   private:
     // an optional tensor's checked pointer, NULL without it
@@ -545,6 +549,36 @@ class EnvHandle {
     at::Device dev_;
     std::vector<at::Tensor> keep_;         // the state's tensors
 };
+
+// tde_state_copy (include/tde_snapshot.h): env rows src_env[k] of `src`'s state into rows dst_env[k] of `dst`'s (the same handle: a fork).
+// A launch on TWO states, so a function of two handles and not a method of one.  frames: (src_layers, dst_layers, src_obs, dst_obs) uint8
+// tensors, each pair optional, with the ring's n_stack, plane and the two phases.
+void state_copy(const EnvHandle &src, const EnvHandle &dst, const at::Tensor &src_env, const at::Tensor &dst_env,
+                const std::optional<at::Tensor> &src_layers, const std::optional<at::Tensor> &dst_layers,
+                const std::optional<at::Tensor> &src_obs, const std::optional<at::Tensor> &dst_obs, int64_t n_stack, int64_t plane,
+                int64_t src_phase, int64_t dst_phase, int64_t flags)
+{
+    TORCH_CHECK(tde_snapshot_version() == TDE_SNAPSHOT_VERSION, "libtde_hip.so snapshot version ", tde_snapshot_version(), " != header ", TDE_SNAPSHOT_VERSION);
+    const at::Device dev = dst.device();
+    TORCH_CHECK(src.device() == dev, "src is on ", src.device(), ", dst on ", dev);
+    const int64_t n = src_env.numel();
+    const int32_t *ps = ptr<const int32_t>(src_env, at::kInt, n, "src_env", dev), *pd = ptr<const int32_t>(dst_env, at::kInt, n, "dst_env", dev);
+    tde_snapshot_frames fr;
+    std::memset(&fr, 0, sizeof(fr));
+    const bool with_frames = src_layers || dst_layers || src_obs || dst_obs;
+    if (with_frames) {
+        TORCH_CHECK(n_stack >= 1 && n_stack <= TDE_SNAPSHOT_MAX_STACK && plane >= 1 && plane <= (1 << 24), "frames: n_stack / plane out of range");
+        const int64_t sB = src.state().B, dB = dst.state().B, row = n_stack * plane;
+        fr.src_layers = src_layers ? ptr<const uint8_t>(*src_layers, at::kByte, sB * row, "src_layers", dev) : nullptr;
+        fr.dst_layers = dst_layers ? ptr<uint8_t>(*dst_layers, at::kByte, dB * row, "dst_layers", dev) : nullptr;
+        fr.src_obs = src_obs ? ptr<const uint8_t>(*src_obs, at::kByte, sB * 3 * row, "src_obs", dev) : nullptr;
+        fr.dst_obs = dst_obs ? ptr<uint8_t>(*dst_obs, at::kByte, dB * 3 * row, "dst_obs", dev) : nullptr;
+        fr.n_stack = (int32_t)n_stack; fr.plane = (int32_t)plane; fr.src_phase = (int32_t)src_phase; fr.dst_phase = (int32_t)dst_phase;
+    }
+    tde_state to = dst.state();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    check_rc(tde_state_copy(&src.state(), &to, (int32_t)n, ps, pd, with_frames ? &fr : nullptr, (uint32_t)flags, cur_stream(dev)), "tde_state_copy");
+}
 
 // ---- operator level: the SimulatorInterface methods GymEnv calls (include/tde_hip.h, first block), torch tensors in / out ----
 
@@ -643,6 +677,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("waypoint_reward", &waypoint_reward, py::arg("cfg"), py::arg("pre"), py::arg("post"), py::arg("offroad"),
           py::arg("collided"), py::arg("tl"), py::arg("wp_xy"), py::arg("wp_n"), py::arg("scn"), py::arg("steps"),
           py::arg("target_idx"), py::arg("reached"));
+    m.def("state_copy", &state_copy, py::arg("src"), py::arg("dst"), py::arg("src_env"), py::arg("dst_env"), py::arg("src_layers"),
+          py::arg("dst_layers"), py::arg("src_obs"), py::arg("dst_obs"), py::arg("n_stack"), py::arg("plane"), py::arg("src_phase"),
+          py::arg("dst_phase"), py::arg("flags"));
     py::class_<Config>(m, "Config", "tde_config by value, from its bytes").def(py::init<const py::bytes &>(), py::arg("raw"));
     py::class_<World, std::shared_ptr<World>>(m, "World", "tde_world over named device tensors (kept alive)")
         .def(py::init<const py::dict &, const py::dict &, int64_t>(), py::arg("tensors"), py::arg("ints"), py::arg("device_index"));

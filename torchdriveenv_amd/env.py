@@ -1286,6 +1286,46 @@ class BatchedWaypointEnv:
             else:
                 self.state.arrays[k].copy_(v)
 
+    # ---- per-env snapshots, forks and recordings (snapshot.py, include/tde_snapshot.h) ---------------------
+    def snapshot(self, envs):
+        """the rows of the envs `envs` (indices, no duplicates) as they are now -> snapshot.EnvSnapshot: an EnvState of len(envs) rows
+        without caches - the step's outputs included - with the rows of the frame-stack ring and stacked observation (or of the single
+        birdview frame, or of the vector observation) and of the terminal frames, and the indices it was taken from.  One tde_state_copy
+        launch (plus a torch gather for vector observations and terminal frames); the live state, the sample counters of buffers and
+        the observation are untouched.  Every per-env buffer the env holds is in it (snapshot.py lists them); replay and rollout
+        buffers are not."""
+        from . import snapshot as S
+
+        return S.snapshot(self, envs)
+
+    def restore(self, snap, envs=None):
+        """put the rows of `snap` back into the envs `envs` (default: the indices they were taken from) and return the observation
+        buffer, whose rows for those envs are the saved ones - what the last step() / reset() before the snapshot returned for them.
+        (get_obs() of a frame-stacked env pushes a new frame onto every env's stack, as it always has: use the returned buffer.)  The
+        step's caches of the rows are invalidated in the same launch.  The RNG rule: the re-spawn draws are keyed by (seed, global env
+        index, episode counter) and nothing else is keyed by the index, so a row restored into its own index continues bit for bit for
+        ever, and a row put into another index continues bit for bit until that env next re-spawns.  A snapshot taken from an env with
+        other options (observation mode, frame stack, resolution, info / magnitudes / routed near field, terminal_obs) raises
+        ValueError naming what does not fit."""
+        from . import snapshot as S
+
+        return S.restore(self, snap, envs)
+
+    def fork(self, src_env, dst_envs):
+        """copy env `src_env` into the envs `dst_envs` (which must not hold src_env) within the live state, frames included, in one
+        launch -> the observation buffer.  The copies continue bit for bit like the source until they next re-spawn (restore()'s RNG
+        rule); give them different actions to branch."""
+        from . import snapshot as S
+
+        return S.fork(self, src_env, dst_envs)
+
+    def recorder(self, envs, video_length=200):
+        """a snapshot.EpisodeRecorder of the envs `envs`: capture() after each reset() / step() records their state rows (one launch, no
+        rendering), frames() / save() render them later with the scene renderer.  Nothing is allocated before this call."""
+        from . import snapshot as S
+
+        return S.EpisodeRecorder(self, envs, video_length)
+
     def replay_buffer(self, capacity_steps, seed=None, terminal_per_step=None, prioritized=None):
         """a replay.ReplayBuffer of `capacity_steps` time slots bound to this env (index draws seeded by `seed`; None: the env's seed).
         On a terminal_obs env the buffer also keeps up to `terminal_per_step` terminal frames per step (None: max(1, num_envs // 8));
@@ -1447,8 +1487,15 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
 
     def __init__(self, env, copy_obs=True, info_keywords=("offroad", "collision", "traffic_light_violation", "is_success",
                                                            "reached_waypoint_num", "psi_smoothness", "speed_smoothness",
-                                                           "psi_reward", "dist_reward"), obs_buffers=None):
-        """obs_buffers: optional list of host tensors (pinned, or page-locked by the caller with hipHostRegister) of the
+                                                           "psi_reward", "dist_reward"), obs_buffers=None,
+                 record_video_trigger=None, video_length=200, video_folder=None):
+        """record_video_trigger / video_length / video_folder: stable_baselines3's VecVideoRecorder (ref examples/rl_training.py:163-164)
+        built in - a callable step -> bool; when it holds after reset() (step 0) or after a step, the state rows of the next video_length
+        frames are recorded on the device (one launch per step, snapshot.EpisodeRecorder) and then rendered and written to
+        `video_folder` as rl-video-step-{start}-to-step-{start + video_length}.mp4, all envs tiled (snapshot.VecRecording; `recording`).
+        A finished env was re-spawned before the frame is taken, as under SB3's recorder.  None (default): nothing is allocated and
+        nothing changes.
+        obs_buffers: optional list of host tensors (pinned, or page-locked by the caller with hipHostRegister) of the
         observation's shape to use as the ring the device-to-host copies land in - how a shard of ShardedBatchedEnv lets
         its observations arrive directly in its slice of the gathered buffer"""
         import time
@@ -1479,6 +1526,11 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
         self._turn = 0
         self._act_pin = self._act_np = self._act_dev = None
         self._obs2_ring = None
+        self.recording, self._step_id = None, 0
+        if record_video_trigger is not None:
+            from .snapshot import VecRecording
+
+            self.recording = VecRecording(env, record_video_trigger, video_length, video_folder)
 
     # ---- helpers
     def _obs_to_host(self, obs, rows=None):
@@ -1492,6 +1544,8 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
         torch.cuda.current_stream(self.env.torch_device).synchronize()
         self._turn += 1
         self.reset_infos = [{} for _ in range(self.num_envs)]
+        if self.recording is not None:
+            self.recording.after(self._step_id)
         out = buf.numpy()
         return out.copy() if self.copy_obs else out
 
@@ -1595,6 +1649,9 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
             terminal = LazyTerminal(idx, obs_of, ep_r, ep_l, t)
         if self.copy_obs:
             obs_np = obs_np.copy()
+        if self.recording is not None:
+            self._step_id += 1
+            self.recording.after(self._step_id)
         return obs_np, rew, done, LazyInfos(self.num_envs, cols, terminal)
 
     def _sel_staging(self, n, like):
@@ -1610,6 +1667,8 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
         return self.step_wait()
 
     def close(self):
+        if self.recording is not None:
+            self.recording.close()
         self.env.close()
 
     def get_attr(self, attr_name, indices=None):

@@ -1127,3 +1127,77 @@ def sequence_sample(rp, tm, dev, first, count, n, T, out, idx_in=None, seed=0, d
     head, outs = _sample_args(rp, dev, n, out, idx_in, seed, draw, T)
     _ring_call(dev, "tde_sequence_sample", C.byref(rp), None if tm is None else C.byref(tm), int(first), int(count), *head, T, *outs)
     return out
+
+
+# ---- copies of env rows between states (include/tde_snapshot.h) ---------------------------------------------------------------------------
+def snapshot_frames(src_layers, dst_layers, src_obs, dst_obs, n_stack, plane, src_phase=0, dst_phase=0):
+    """the `frames` argument of state_copy: the frame-stack ring of the same rows - layers uint8 [B, n_stack, plane] and the stacked
+    observation uint8 [B, 3 * n_stack, plane] of the source and of the destination (each pair optional: None, None), and the ring slot the
+    next frame goes to on either side (FrameStack.phase)"""
+    return dict(src_layers=src_layers, dst_layers=dst_layers, src_obs=src_obs, dst_obs=dst_obs, n_stack=int(n_stack), plane=int(plane),
+                src_phase=int(src_phase), dst_phase=int(dst_phase))
+
+
+def _row_indices(envs, name, dev):
+    """int32 device tensor [n] of env indices from a sequence or tensor"""
+    t = torch.as_tensor(envs)
+    if t.dtype in (torch.float16, torch.float32, torch.float64, torch.bool, torch.bfloat16):
+        raise ValueError(f"{name} must hold integers")
+    return t.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+
+
+def state_copy(src_state, dst_state, src_env, dst_env, frames=None, outputs=False, check=True, handles=None):
+    """tde_state_copy on the current stream: env row src_env[k] of `src_state` into env row dst_env[k] of `dst_state` (device EnvStates
+    of the same A; the same state for a fork, with dst_env disjoint from src_env) - every per-agent and per-env array both states carry,
+    with outputs=True the step's outputs too; the destination rows of dst_state's caches are invalidated in the same launch and no cache
+    is ever copied (include/tde_snapshot.h lists the groups).  frames: snapshot_frames(...) - the rows' frame-stack ring moves with them.
+    check=True (default) reads the indices back first (one synchronisation) and raises on indices out of range, rows named twice in
+    dst_env, or dst_env overlapping src_env within one state; check=False skips that: a pair out of range is then skipped by the kernel.
+    handles: (src, dst) launch handles of the two states - the extension's EnvHandles (the call then goes through the extension) or
+    ops.CtypesHandles / None (through ctypes): both reach the same entry point."""
+    if src_state.device is None or dst_state.device is None:
+        raise ValueError("state_copy needs device states (there is no CPU path)")
+    dev = torch.device(dst_state.device)
+    if torch.device(src_state.device) != dev:
+        raise ValueError(f"src_state is on {src_state.device}, dst_state on {dst_state.device}")
+    if src_state.A != dst_state.A:
+        raise ValueError(f"src_state has A = {src_state.A}, dst_state A = {dst_state.A}: they must be equal")
+    if src_state["slot_route"] is not None and dst_state["slot_route"] is None:
+        raise ValueError("src_state carries slot_route and dst_state does not: the routes of near-field agents would be lost")
+    se, de = _row_indices(src_env, "src_env", dev), _row_indices(dst_env, "dst_env", dev)
+    if se.numel() != de.numel():
+        raise ValueError(f"src_env holds {se.numel()} indices, dst_env {de.numel()}")
+    n = se.numel()
+    flags = (_abi.SNAPSHOT_OUTPUTS if outputs else 0) | (_abi.SNAPSHOT_CHECK if check else 0)
+    f = None
+    if frames is not None:
+        f = dict(frames)
+        ns, plane = f["n_stack"], f["plane"]
+        if not 1 <= ns <= _abi.SNAPSHOT_MAX_STACK:
+            raise ValueError(f"frames: n_stack must be in [1, {_abi.SNAPSHOT_MAX_STACK}], got {ns}")
+        if plane < 1 or plane % 16:
+            raise ValueError(f"frames: plane must be a positive multiple of 16, got {plane}")
+        for k in ("src_phase", "dst_phase"):
+            if not 0 <= f[k] < ns:
+                raise ValueError(f"frames: {k} must be in [0, {ns}), got {f[k]}")
+        for a, b in (("src_layers", "dst_layers"), ("src_obs", "dst_obs")):
+            if (f[a] is None) != (f[b] is None):
+                raise ValueError(f"frames: {a} and {b} are given together or not at all")
+        sizes = {"src_layers": src_state.B * ns * plane, "dst_layers": dst_state.B * ns * plane,
+                 "src_obs": src_state.B * 3 * ns * plane, "dst_obs": dst_state.B * 3 * ns * plane}
+        ptrs = {k: _chk(f[k], torch.uint8, sizes[k], k, dev, optional=True) for k in sizes}
+    ext = handles is not None and not isinstance(handles[1], CtypesHandle)
+    if ext:
+        from . import _ext
+
+        g = f or dict(src_layers=None, dst_layers=None, src_obs=None, dst_obs=None, n_stack=0, plane=0, src_phase=0, dst_phase=0)
+        _ext.load().state_copy(handles[0], handles[1], se, de, g["src_layers"], g["dst_layers"], g["src_obs"], g["dst_obs"], g["n_stack"],
+                               g["plane"], g["src_phase"], g["dst_phase"], flags)
+        return dst_state
+    fr = None
+    if f is not None:
+        fr = C.byref(_abi.TdeSnapshotFrames(ptrs["src_layers"], ptrs["dst_layers"], ptrs["src_obs"], ptrs["dst_obs"], ns, plane,
+                                            f["src_phase"], f["dst_phase"]))
+    _ring_call(dev, "tde_state_copy", C.byref(src_state.struct), C.byref(dst_state.struct), n, se.data_ptr() if n else None,
+               de.data_ptr() if n else None, fr, flags)
+    return dst_state
