@@ -1,11 +1,10 @@
-"""CPU checks of the n-step sample (include/tde_nstep.h, torchdriveenv_amd/replay.py): the header beside the others, the symbols of the
-built library, every host-side rejection of the entry point, of the ops wrapper and of sample_nstep's arguments (all before any launch:
+"""CPU checks of the n-step sample (include/tde_nstep.h, torchdriveenv_amd/replay.py): the header's constant (the header beside the others, its
+symbols and the loader's refusals: tests/test_abi_families_cpu.py), every host-side rejection of the entry point, of the ops wrapper and of sample_nstep's arguments (all before any launch:
 no GPU needed), the numpy restatement (tests/nstep_ref.py) against a brute-force composition written here, and the case table
 (tests/nstep_cases.py) that tests/test_gpu_nstep.py runs on the GPU, held to the conditions that make it mean something."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import pytest
 from tests import nstep_cases as K
 from tests import nstep_ref as N
 from tests.replay_ref import ENDED
+from tests.test_abi_families_cpu import c_status
 from tests.test_replay_cpu import BAD_STRUCTS, _Host
 from torchdriveenv_amd import _abi
 
@@ -21,48 +21,10 @@ F = np.float32
 
 
 # ---- header, symbols, constants -----------------------------------------------------------------------------------------------------
-def test_header_compiles_beside_the_others_and_alone(tmp_path):
-    c, exe = tmp_path / "ns.c", str(tmp_path / "ns")
-    body = ("int main(void){return (TDE_ABI_VERSION - 14) | (TDE_REPLAY_VERSION - 1) | (TDE_ONPOLICY_VERSION - 1) | (TDE_TERMINAL_VERSION - 1) |"
-            " (TDE_NSTEP_VERSION - 1) | (TDE_NSTEP_MAX - 64) | (sizeof(&tde_nstep_sample) != sizeof(&tde_nstep_version));}\n")
-    for order in (("tde_hip.h", "tde_replay.h", "tde_onpolicy.h", "tde_terminal.h", "tde_nstep.h"), ("tde_nstep.h", "tde_onpolicy.h", "tde_hip.h")):
-        c.write_text("".join(f'#include "{h}"\n' for h in order) + body)
-        subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-        assert subprocess.run([exe]).returncode == 0
-    c.write_text('#include "tde_nstep.h"\nint main(void){tde_replay r; tde_terminal t; r.C = TDE_NSTEP_VERSION; t.M = r.C; return t.M - 1;}\n')
-    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-    assert subprocess.run([exe]).returncode == 0
-
-
-def test_header_lib_and_abi_agree():
-    from torchdriveenv_amd import _lib, build
-
+def test_constants_match_header(tmp_path):
+    assert c_status(tmp_path, ["tde_nstep.h"], "TDE_NSTEP_MAX - 64") == 0
     text = open(os.path.join(ROOT, "include", "tde_nstep.h")).read()
-    declared = re.findall(r"TDE_API\s+int\s+(tde_\w+)\(", text)
-    assert sorted(declared) == sorted(_lib.NSTEP_SYMBOLS) and _lib.NSTEP_SYMBOLS == ["tde_nstep_version", "tde_nstep_sample"]
-    assert int(re.search(r"#define TDE_NSTEP_VERSION (\d+)", text).group(1)) == _abi.TDE_NSTEP_VERSION == 1
     assert int(re.search(r"#define TDE_NSTEP_MAX (\d+)", text).group(1)) == _abi.NSTEP_MAX == N.NSTEP_MAX == 64
-    L = _lib.load()
-    assert all(hasattr(L, s) for s in _lib.NSTEP_SYMBOLS) and L.tde_nstep_version() == 1
-    older = set(_lib.SYMBOLS) | set(_lib.REPLAY_SYMBOLS) | set(_lib.ONPOLICY_SYMBOLS) | set(_lib.TERMINAL_SYMBOLS)
-    assert not set(_lib.NSTEP_SYMBOLS) & older
-    assert [len(getattr(L, s).argtypes) for s in _lib.NSTEP_SYMBOLS] == [0, 19]
-    assert "tde_nstep.hip" in build.UNITS and any(d.endswith("tde_nstep.h") for d in build.DEPS)
-    # the older lists and versions are as they were
-    assert len(_lib.SYMBOLS) == 31 and _abi.TDE_ABI_VERSION == 14 == L.tde_abi_version()
-    assert L.tde_replay_version() == 1 and L.tde_onpolicy_version() == 1 and L.tde_terminal_version() == 1
-    assert (len(_lib.REPLAY_SYMBOLS), len(_lib.ONPOLICY_SYMBOLS), len(_lib.TERMINAL_SYMBOLS)) == (5, 3, 4)
-
-
-def test_a_library_without_the_nstep_symbols_is_a_stale_build(monkeypatch):
-    from torchdriveenv_amd import _lib
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "NSTEP_SYMBOLS", _lib.NSTEP_SYMBOLS + ["tde_nstep_not_there"])
-    with pytest.raises(_lib.TdeError, match=r"lacks symbols \['tde_nstep_not_there'\]: stale build\?"):
-        _lib.load()
-    monkeypatch.undo()
-    _lib.load()
 
 
 # ---- every host-side refusal, before any launch -------------------------------------------------------------------------------------

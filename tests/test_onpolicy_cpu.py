@@ -1,11 +1,8 @@
-"""CPU checks of the on-policy view of the replay ring (include/tde_onpolicy.h, torchdriveenv_amd/onpolicy.py): the header beside the
-others, the symbols of the built library, every host-side rejection of the two entry points, of the ops wrappers and of RolloutBuffer's
+"""CPU checks of the on-policy view of the replay ring (include/tde_onpolicy.h, torchdriveenv_amd/onpolicy.py; the header beside the
+others, its symbols and the loader's refusals: tests/test_abi_families_cpu.py): every host-side rejection of the two entry points, of the ops wrappers and of RolloutBuffer's
 arguments and call order (all before any launch: no GPU needed), and the numpy restatement (tests/onpolicy_ref.py) against
 hand-computed known answers."""
 import ctypes as C
-import itertools
-import os
-import subprocess
 import types
 
 import numpy as np
@@ -15,53 +12,13 @@ from tests import onpolicy_ref as O
 from tests.test_replay_cpu import BAD_STRUCTS, _Host
 from torchdriveenv_amd import _abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CUT = _abi.REPLAY_CUT
-
-
-def test_header_compiles_beside_the_others_in_any_order(tmp_path):
-    c, exe = tmp_path / "op.c", str(tmp_path / "op")
-    for order in itertools.permutations(("tde_hip.h", "tde_replay.h", "tde_onpolicy.h")):
-        c.write_text("".join(f'#include "{h}"\n' for h in order) +
-                     "int main(void){return (TDE_ABI_VERSION - 14) | (TDE_REPLAY_VERSION - 1) | (TDE_ONPOLICY_VERSION - 1) |"
-                     " (sizeof(&tde_gae) != sizeof(&tde_onpolicy_gather)) | (sizeof(&tde_onpolicy_version) != sizeof(&tde_replay_sample));}\n")
-        subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-        assert subprocess.run([exe]).returncode == 0
-    # alone, too: it brings what it needs
-    c.write_text('#include "tde_onpolicy.h"\nint main(void){tde_replay r; r.C = TDE_ONPOLICY_VERSION; return r.C - 1;}\n')
-    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-    assert subprocess.run([exe]).returncode == 0
-    assert _abi.TDE_ONPOLICY_VERSION == 1
 
 
 def _loaded():
     from torchdriveenv_amd import _lib
 
     return _lib, _lib.load()
-
-
-def test_symbols_of_the_built_library():
-    _lib, L = _loaded()
-    assert _lib.ONPOLICY_SYMBOLS == ["tde_onpolicy_version", "tde_gae", "tde_onpolicy_gather"]
-    assert all(hasattr(L, s) for s in _lib.ONPOLICY_SYMBOLS)
-    assert not set(_lib.ONPOLICY_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.REPLAY_SYMBOLS))
-    assert L.tde_onpolicy_version() == 1 == _abi.TDE_ONPOLICY_VERSION
-    assert [len(getattr(L, s).argtypes) for s in _lib.ONPOLICY_SYMBOLS] == [0, 11, 17]
-    # the two older lists and their versions are as they were
-    assert len(_lib.SYMBOLS) == 31 and _abi.TDE_ABI_VERSION == 14 == L.tde_abi_version()
-    assert _lib.REPLAY_SYMBOLS == ["tde_replay_version", "tde_replay_begin", "tde_replay_push", "tde_replay_sample", "tde_replay_pack"]
-    assert L.tde_replay_version() == 1 == _abi.TDE_REPLAY_VERSION
-
-
-def test_a_library_without_the_onpolicy_symbols_is_a_stale_build(monkeypatch):
-    from torchdriveenv_amd import _lib
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "ONPOLICY_SYMBOLS", _lib.ONPOLICY_SYMBOLS + ["tde_onpolicy_not_there"])
-    with pytest.raises(_lib.TdeError, match=r"lacks symbols \['tde_onpolicy_not_there'\]: stale build\?"):
-        _lib.load()
-    monkeypatch.undo()
-    _lib.load()
 
 
 def test_entry_points_reject_bad_arguments_without_a_launch():

@@ -1,12 +1,11 @@
-"""CPU checks of prioritized replay (include/tde_priority.h, torchdriveenv_amd/replay.py): the header beside the others, the symbols of
-the built library, every host-side rejection of the entry points, of the ops wrappers and of the two new methods (all before any launch:
+"""CPU checks of prioritized replay (include/tde_priority.h, torchdriveenv_amd/replay.py): the header's constants and struct (the header beside the
+others, its symbols and the loader's refusals: tests/test_abi_families_cpu.py), every host-side rejection of the entry points, of the ops wrappers and of the two new methods (all before any launch:
 no GPU needed), the Python statement (tests/priority_ref.py) against a brute-force walk and against valid_pairs()' rule, the weights,
 the distribution of the statement's draw, and the case table (tests/priority_cases.py) that tests/test_gpu_priority.py runs on the GPU,
 held to the conditions that make it mean something."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import pytest
 from tests import priority_cases as K
 from tests import priority_ref as P
 from tests import ring_util as U
+from tests.test_abi_families_cpu import c_status
 from tests.test_replay_cpu import BAD_STRUCTS, _Host
 from torchdriveenv_amd import _abi
 
@@ -21,53 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- header, symbols, constants -----------------------------------------------------------------------------------------------------
-def test_header_compiles_beside_the_others_and_alone(tmp_path):
-    c, exe = tmp_path / "pr.c", str(tmp_path / "pr")
-    body = ("int main(void){return (TDE_ABI_VERSION - 14) | (TDE_REPLAY_VERSION - 1) | (TDE_ONPOLICY_VERSION - 1) | (TDE_TERMINAL_VERSION - 1) |"
-            " (TDE_NSTEP_VERSION - 1) | (TDE_PRIORITY_VERSION - 1) | (TDE_PRIORITY_ONE != 65536u) | (TDE_PRIORITY_QMAX != 268435456u) |"
-            " (TDE_PRIORITY_TAG != 0x5052u) | (sizeof(&tde_priority_sample) != sizeof(&tde_priority_version));}\n")
-    for order in (("tde_hip.h", "tde_replay.h", "tde_onpolicy.h", "tde_terminal.h", "tde_nstep.h", "tde_priority.h"),
-                  ("tde_priority.h", "tde_nstep.h", "tde_onpolicy.h", "tde_hip.h")):
-        c.write_text("".join(f'#include "{h}"\n' for h in order) + body)
-        subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-        assert subprocess.run([exe]).returncode == 0
-    c.write_text('#include "tde_priority.h"\nint main(void){tde_replay r; tde_priority p; r.C = TDE_PRIORITY_VERSION; p.leaf = 0; p.sums = 0;'
-                 ' p.qmax = 0; return (r.C - 1) | (p.leaf != 0) | (sizeof(*p.sums) != 8) | (sizeof(*p.leaf) != 4) | (sizeof(*p.qmax) != 4);}\n')
-    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-    assert subprocess.run([exe]).returncode == 0
-
-
-def test_header_lib_and_abi_agree():
-    from torchdriveenv_amd import _lib, build
-
+def test_constants_and_struct_match_header(tmp_path):
+    assert c_status(tmp_path, ["tde_priority.h"], "(TDE_PRIORITY_ONE != 65536u) | (TDE_PRIORITY_QMAX != 268435456u) | (TDE_PRIORITY_TAG != 0x5052u) |"
+                    " (p.leaf != 0) | (sizeof(*p.sums) != 8) | (sizeof(*p.leaf) != 4) | (sizeof(*p.qmax) != 4)",
+                    decls="tde_priority p; p.leaf = 0; p.sums = 0; p.qmax = 0;") == 0
     text = open(os.path.join(ROOT, "include", "tde_priority.h")).read()
-    declared = re.findall(r"TDE_API\s+\w+\s+(tde_\w+)\(", text)
-    want = ["tde_priority_version", "tde_priority_words", "tde_priority_reset", "tde_priority_push", "tde_priority_update", "tde_priority_sample"]
-    assert sorted(declared) == sorted(_lib.PRIORITY_SYMBOLS) and _lib.PRIORITY_SYMBOLS == want
-    assert int(re.search(r"#define TDE_PRIORITY_VERSION (\d+)", text).group(1)) == _abi.TDE_PRIORITY_VERSION == 1
     assert (_abi.PRIORITY_ONE, _abi.PRIORITY_QMAX, _abi.PRIORITY_TAG) == (1 << 16, 1 << 28, 0x5052) == (P.ONE, P.QMAX, P.TAG)
     assert [n for n, _ in _abi.TdePriority._fields_] == re.findall(r"uint\d+_t \*(\w+);", text) == ["leaf", "sums", "qmax"]
-    L = _lib.load()
-    assert all(hasattr(L, s) for s in _lib.PRIORITY_SYMBOLS) and L.tde_priority_version() == 1
-    older = (set(_lib.SYMBOLS) | set(_lib.REPLAY_SYMBOLS) | set(_lib.ONPOLICY_SYMBOLS) | set(_lib.TERMINAL_SYMBOLS) | set(_lib.NSTEP_SYMBOLS))
-    assert not set(_lib.PRIORITY_SYMBOLS) & older
-    assert [len(getattr(L, s).argtypes) for s in _lib.PRIORITY_SYMBOLS] == [0, 2, 3, 6, 8, 10]
-    assert "tde_priority.hip" in build.UNITS and any(d.endswith("tde_priority.h") for d in build.DEPS)
-    # the older lists and versions are as they were
-    assert len(_lib.SYMBOLS) == 31 and _abi.TDE_ABI_VERSION == 14 == L.tde_abi_version()
-    assert L.tde_replay_version() == 1 and L.tde_onpolicy_version() == 1 and L.tde_terminal_version() == 1 and L.tde_nstep_version() == 1
-    assert (len(_lib.REPLAY_SYMBOLS), len(_lib.ONPOLICY_SYMBOLS), len(_lib.TERMINAL_SYMBOLS), len(_lib.NSTEP_SYMBOLS)) == (5, 3, 4, 2)
-
-
-def test_a_library_without_the_priority_symbols_is_a_stale_build(monkeypatch):
-    from torchdriveenv_amd import _lib
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "PRIORITY_SYMBOLS", _lib.PRIORITY_SYMBOLS + ["tde_priority_not_there"])
-    with pytest.raises(_lib.TdeError, match=r"lacks symbols \['tde_priority_not_there'\]: stale build\?"):
-        _lib.load()
-    monkeypatch.undo()
-    _lib.load()
 
 
 def test_words_is_the_inner_nodes_of_a_64_ary_tree():

@@ -1,11 +1,10 @@
-"""CPU checks of the sequence sample (include/tde_sequence.h, torchdriveenv_amd/replay.py): the header beside the others, the symbols of
-the built library, every host-side rejection of the entry point, of the ops wrapper and of sample_sequence's arguments (all before any
+"""CPU checks of the sequence sample (include/tde_sequence.h, torchdriveenv_amd/replay.py): the header's constant (the header beside the others,
+its symbols and the loader's refusals: tests/test_abi_families_cpu.py), every host-side rejection of the entry point, of the ops wrapper and of sample_sequence's arguments (all before any
 launch: no GPU needed), the numpy restatement (tests/sequence_ref.py) against a brute force written here, the draw, and the case tables
 (tests/sequence_cases.py) that tests/test_gpu_sequence.py runs on the GPU, held to the conditions that make them mean something."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ from tests import sequence_cases as K
 from tests import sequence_ref as S
 from tests.replay_ref import ENDED, PAL
 from tests.ring_util import HAS
+from tests.test_abi_families_cpu import c_status
 from tests.test_replay_cpu import BAD_STRUCTS, _Host
 from torchdriveenv_amd import _abi
 
@@ -22,56 +22,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- header, symbols, constants -----------------------------------------------------------------------------------------------------
-def test_header_compiles_alone_and_beside_the_others(tmp_path):
-    c, exe = tmp_path / "sq.c", str(tmp_path / "sq")
-    body = ("int main(void){return (TDE_ABI_VERSION - 14) | (TDE_REPLAY_VERSION - 1) | (TDE_ONPOLICY_VERSION - 1) | (TDE_TERMINAL_VERSION - 1) |"
-            " (TDE_NSTEP_VERSION - 1) | (TDE_PRIORITY_VERSION - 1) | (TDE_SEQUENCE_VERSION - 1) | (TDE_SEQUENCE_MAX - 256) | (TDE_NSTEP_MAX - 64) |"
-            " (sizeof(&tde_sequence_sample) != sizeof(&tde_sequence_version));}\n")
-    for order in (("tde_hip.h", "tde_replay.h", "tde_onpolicy.h", "tde_terminal.h", "tde_nstep.h", "tde_priority.h", "tde_sequence.h"),
-                  ("tde_sequence.h", "tde_priority.h", "tde_nstep.h", "tde_onpolicy.h", "tde_hip.h")):
-        c.write_text("".join(f'#include "{h}"\n' for h in order) + body)
-        subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-        assert subprocess.run([exe]).returncode == 0
-    c.write_text('#include "tde_sequence.h"\nint main(void){tde_replay r; tde_terminal t; r.C = TDE_SEQUENCE_VERSION; t.M = r.C; return t.M - 1;}\n')
-    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-    assert subprocess.run([exe]).returncode == 0
-
-
-def test_header_lib_and_abi_agree():
-    from torchdriveenv_amd import _lib, build
-
+def test_constants_match_header(tmp_path):
+    assert c_status(tmp_path, ["tde_sequence.h", "tde_nstep.h"], "(TDE_SEQUENCE_MAX - 256) | (TDE_NSTEP_MAX - 64)") == 0
     text = open(os.path.join(ROOT, "include", "tde_sequence.h")).read()
-    declared = re.findall(r"TDE_API\s+int\s+(tde_\w+)\(", text)
-    assert sorted(declared) == sorted(_lib.SEQUENCE_SYMBOLS) and _lib.SEQUENCE_SYMBOLS == ["tde_sequence_version", "tde_sequence_sample"]
-    assert int(re.search(r"#define TDE_SEQUENCE_VERSION (\d+)", text).group(1)) == _abi.TDE_SEQUENCE_VERSION == 1
     assert int(re.search(r"#define TDE_SEQUENCE_MAX (\d+)", text).group(1)) == _abi.SEQUENCE_MAX == S.SEQUENCE_MAX == 256
-    assert '#include "tde_terminal.h"' in text
-    L = _lib.load()
-    assert all(hasattr(L, s) for s in _lib.SEQUENCE_SYMBOLS) and L.tde_sequence_version() == 1
-    older = (set(_lib.SYMBOLS) | set(_lib.REPLAY_SYMBOLS) | set(_lib.ONPOLICY_SYMBOLS) | set(_lib.TERMINAL_SYMBOLS) | set(_lib.NSTEP_SYMBOLS)
-             | set(_lib.PRIORITY_SYMBOLS))
-    assert not set(_lib.SEQUENCE_SYMBOLS) & older
-    assert [len(getattr(L, s).argtypes) for s in _lib.SEQUENCE_SYMBOLS] == [0, 16]
-    assert "tde_sequence.hip" in build.UNITS and any(d.endswith("tde_sequence.h") for d in build.DEPS)
-    assert all(os.path.exists(d) for d in build.DEPS)
-    # the older lists and versions are as they were
-    assert len(_lib.SYMBOLS) == 31 and _abi.TDE_ABI_VERSION == 14 == L.tde_abi_version()
-    assert L.tde_replay_version() == 1 and L.tde_onpolicy_version() == 1 and L.tde_terminal_version() == 1
-    assert L.tde_nstep_version() == 1 and L.tde_priority_version() == 1 and _abi.NSTEP_MAX == 64
-    assert (len(_lib.REPLAY_SYMBOLS), len(_lib.ONPOLICY_SYMBOLS), len(_lib.TERMINAL_SYMBOLS), len(_lib.NSTEP_SYMBOLS),
-            len(_lib.PRIORITY_SYMBOLS)) == (5, 3, 4, 2, 6)
-    assert [len(getattr(L, s).argtypes) for s in _lib.NSTEP_SYMBOLS] == [0, 19]
-
-
-def test_a_library_without_the_sequence_symbols_is_a_stale_build(monkeypatch):
-    from torchdriveenv_amd import _lib
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "SEQUENCE_SYMBOLS", _lib.SEQUENCE_SYMBOLS + ["tde_sequence_not_there"])
-    with pytest.raises(_lib.TdeError, match=r"lacks symbols \['tde_sequence_not_there'\]: stale build\?"):
-        _lib.load()
-    monkeypatch.undo()
-    _lib.load()
 
 
 # ---- every host-side refusal, before any launch -------------------------------------------------------------------------------------

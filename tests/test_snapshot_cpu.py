@@ -1,16 +1,16 @@
-"""CPU checks of tde_state_copy (include/tde_snapshot.h, torchdriveenv_amd/snapshot.py): the header beside the others, the symbols of the
-built library, every host-side refusal of the entry point (all before any launch: no GPU needed - the index rules of
+"""CPU checks of tde_state_copy (include/tde_snapshot.h, torchdriveenv_amd/snapshot.py): the header's constants and struct (the header beside
+the others, its symbols and the loader's refusals: tests/test_abi_families_cpu.py), every host-side refusal of the entry point (all before any launch: no GPU needed - the index rules of
 TDE_SNAPSHOT_CHECK included, which a process without a device reads from host memory), the classification of every tde_state member, and
 the numpy restatement (tests/snapshot_ref.py) against a brute force written here."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import snapshot_ref as S
+from tests.test_abi_families_cpu import COMPILERS, c_status
 from torchdriveenv_amd import _abi
 from torchdriveenv_amd.state import EnvState
 
@@ -19,59 +19,13 @@ HEADER = os.path.join(ROOT, "include", "tde_snapshot.h")
 
 
 # ---- header, symbols, constants -----------------------------------------------------------------------------------------------------
-def test_header_compiles_as_c_and_cxx_beside_the_others(tmp_path):
-    body = ("int main(void){tde_snapshot_frames f; f.n_stack = TDE_SNAPSHOT_VERSION; return (TDE_ABI_VERSION - 14) | (TDE_REPLAY_VERSION - 1) |"
-            " (TDE_ONPOLICY_VERSION - 1) | (TDE_TERMINAL_VERSION - 1) | (TDE_NSTEP_VERSION - 1) | (TDE_PRIORITY_VERSION - 1) |"
-            " (TDE_SEQUENCE_VERSION - 1) | (f.n_stack - 1) | (TDE_SNAPSHOT_OUTPUTS - 1) | (TDE_SNAPSHOT_CHECK - 2) | (TDE_SNAPSHOT_MAX_STACK - 8) |"
-            " (sizeof(f) != 48) | (sizeof(&tde_state_copy) != sizeof(&tde_snapshot_version));}\n")
-    orders = (("tde_hip.h", "tde_replay.h", "tde_onpolicy.h", "tde_terminal.h", "tde_nstep.h", "tde_priority.h", "tde_sequence.h", "tde_snapshot.h"),
-              ("tde_snapshot.h", "tde_sequence.h", "tde_priority.h", "tde_nstep.h", "tde_onpolicy.h"))
-    for cc, ext in (("gcc", "c"), ("g++", "cpp")):
-        src, exe = tmp_path / f"sn.{ext}", str(tmp_path / f"sn_{ext}")
-        for order in orders:
-            src.write_text("".join(f'#include "{h}"\n' for h in order) + body)
-            subprocess.run([cc, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
-            assert subprocess.run([exe]).returncode == 0
-        src.write_text('#include "tde_snapshot.h"\nint main(void){tde_state s; s.B = TDE_SNAPSHOT_VERSION; return s.B - 1;}\n')
-        subprocess.run([cc, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
-        assert subprocess.run([exe]).returncode == 0
-
-
-def test_header_lib_and_abi_agree():
-    from torchdriveenv_amd import _lib, build
-
-    text = open(HEADER).read()
-    declared = re.findall(r"TDE_API\s+int\s+(tde_\w+)\(", text)
-    assert sorted(declared) == sorted(_lib.SNAPSHOT_SYMBOLS) and _lib.SNAPSHOT_SYMBOLS == ["tde_snapshot_version", "tde_state_copy"]
-    assert int(re.search(r"#define TDE_SNAPSHOT_VERSION (\d+)", text).group(1)) == _abi.TDE_SNAPSHOT_VERSION == 1
+def test_constants_and_struct_match_header(tmp_path):
+    for cc, ext in COMPILERS:
+        assert c_status(tmp_path, ["tde_snapshot.h"], "(f.n_stack - 1) | (TDE_SNAPSHOT_OUTPUTS - 1) | (TDE_SNAPSHOT_CHECK - 2) |"
+                        " (TDE_SNAPSHOT_MAX_STACK - 8) | (sizeof(f) != 48) | (s.B - 1)", cc, ext,
+                        decls="tde_snapshot_frames f; tde_state s; f.n_stack = TDE_SNAPSHOT_VERSION; s.B = TDE_SNAPSHOT_VERSION;") == 0
     assert (_abi.SNAPSHOT_OUTPUTS, _abi.SNAPSHOT_CHECK, _abi.SNAPSHOT_MAX_STACK) == (S.SNAPSHOT_OUTPUTS, S.SNAPSHOT_CHECK, 8) == (1, 2, 8)
     assert C.sizeof(_abi.TdeSnapshotFrames) == 48
-    L = _lib.load()
-    assert all(hasattr(L, s) for s in _lib.SNAPSHOT_SYMBOLS) and L.tde_snapshot_version() == 1
-    older = (set(_lib.SYMBOLS) | set(_lib.REPLAY_SYMBOLS) | set(_lib.ONPOLICY_SYMBOLS) | set(_lib.TERMINAL_SYMBOLS) | set(_lib.NSTEP_SYMBOLS)
-             | set(_lib.PRIORITY_SYMBOLS) | set(_lib.SEQUENCE_SYMBOLS))
-    assert not set(_lib.SNAPSHOT_SYMBOLS) & older
-    assert [len(getattr(L, s).argtypes) for s in _lib.SNAPSHOT_SYMBOLS] == [0, 8]
-    assert "tde_snapshot.hip" in build.UNITS and any(d.endswith("tde_snapshot.h") for d in build.DEPS)
-    assert all(os.path.exists(d) for d in build.DEPS)
-    assert '#include "tde_snapshot.hip"' in open(os.path.join(ROOT, "torchdriveenv_amd", "csrc", "tde_kernels.hip")).read()
-    # the older lists and versions are as they were
-    assert len(_lib.SYMBOLS) == 31 and _abi.TDE_ABI_VERSION == 14 == L.tde_abi_version()
-    assert L.tde_replay_version() == 1 and L.tde_onpolicy_version() == 1 and L.tde_terminal_version() == 1
-    assert L.tde_nstep_version() == 1 and L.tde_priority_version() == 1 and L.tde_sequence_version() == 1
-    assert (len(_lib.REPLAY_SYMBOLS), len(_lib.ONPOLICY_SYMBOLS), len(_lib.TERMINAL_SYMBOLS), len(_lib.NSTEP_SYMBOLS),
-            len(_lib.PRIORITY_SYMBOLS), len(_lib.SEQUENCE_SYMBOLS)) == (5, 3, 4, 2, 6, 2)
-
-
-def test_a_library_without_the_snapshot_symbols_is_a_stale_build(monkeypatch):
-    from torchdriveenv_amd import _lib
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "SNAPSHOT_SYMBOLS", _lib.SNAPSHOT_SYMBOLS + ["tde_snapshot_not_there"])
-    with pytest.raises(_lib.TdeError, match=r"lacks symbols \['tde_snapshot_not_there'\]: stale build\?"):
-        _lib.load()
-    monkeypatch.undo()
-    _lib.load()
 
 
 # ---- every member of tde_state is classified ----------------------------------------------------------------------------------------

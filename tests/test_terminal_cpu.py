@@ -1,16 +1,16 @@
 """CPU checks of the terminal pool beside the replay ring (include/tde_terminal.h, torchdriveenv_amd/replay.py, onpolicy.py, env.py): the
-numpy restatement (tests/terminal_ref.py) against hand-made cases, the header beside the others, the symbols of the built library, and
-every host-side rejection of the entry points, of the ops wrappers and of the Python arguments (all before any launch: no GPU needed)."""
+numpy restatement (tests/terminal_ref.py) against hand-made cases, the header's constants and struct (the header beside the others, its
+symbols and the loader's refusals: tests/test_abi_families_cpu.py), and every host-side rejection of the entry points, of the ops wrappers and of the Python arguments (all before any launch: no GPU needed)."""
 import ctypes as C
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
 from tests import terminal_ref as T
+from tests.test_abi_families_cpu import c_status
 from tests.test_replay_cpu import BAD_STRUCTS, _Host
 from torchdriveenv_amd import _abi
 
@@ -87,51 +87,13 @@ def test_a_transition_that_is_cut_and_ended_keeps_its_frame():
 
 
 # ---- header, symbols, constants -----------------------------------------------------------------------------------------------------
-def test_header_compiles_beside_the_others_and_alone(tmp_path):
-    c, exe = tmp_path / "tm.c", str(tmp_path / "tm")
-    body = ("int main(void){return (TDE_ABI_VERSION - 14) | (TDE_REPLAY_VERSION - 1) | (TDE_ONPOLICY_VERSION - 1) | (TDE_TERMINAL_VERSION - 1) |"
-            " (TDE_TERMINAL_HAS & (TDE_REPLAY_CUT | 31)) | (sizeof(&tde_terminal_push) != sizeof(&tde_terminal_sample)) |"
-            " (sizeof(&tde_terminal_stash) != sizeof(&tde_terminal_version)) | (sizeof(tde_terminal) != 24);}\n")
-    for order in (("tde_hip.h", "tde_replay.h", "tde_onpolicy.h", "tde_terminal.h"), ("tde_terminal.h", "tde_onpolicy.h", "tde_hip.h")):
-        c.write_text("".join(f'#include "{h}"\n' for h in order) + body)
-        subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-        assert subprocess.run([exe]).returncode == 0
-    c.write_text('#include "tde_terminal.h"\nint main(void){tde_replay r; tde_terminal t; r.C = TDE_TERMINAL_VERSION; t.M = r.C; return t.M - 1;}\n')
-    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe], check=True)
-    assert subprocess.run([exe]).returncode == 0
-
-
-def test_header_lib_and_abi_agree():
-    from torchdriveenv_amd import _lib, build
-
+def test_constants_and_struct_match_header(tmp_path):
+    assert c_status(tmp_path, ["tde_terminal.h"], "(TDE_TERMINAL_HAS & (TDE_REPLAY_CUT | 31)) | (sizeof(tde_terminal) != 24)") == 0
     text = open(os.path.join(ROOT, "include", "tde_terminal.h")).read()
-    declared = re.findall(r"TDE_API\s+int\s+(tde_\w+)\(", text)
-    assert sorted(declared) == sorted(_lib.TERMINAL_SYMBOLS) and len(declared) == 4
-    assert int(re.search(r"#define TDE_TERMINAL_VERSION (\d+)", text).group(1)) == _abi.TDE_TERMINAL_VERSION == 1
     assert int(re.search(r"#define TDE_TERMINAL_HAS (0x[0-9a-fA-F]+)", text).group(1), 16) == _abi.TERMINAL_HAS == 0x40
     assert not _abi.TERMINAL_HAS & (_abi.REPLAY_CUT | 31)               # free beside done_bits (bits 0-4) and the cut bit
     assert [f[0] for f in _abi.TdeTerminal._fields_] == ["M", "pool", "ref"] and C.sizeof(_abi.TdeTerminal) == 24
     assert _abi.TdeTerminal.pool.offset == 8 and _abi.TdeTerminal.ref.offset == 16
-    L = _lib.load()
-    assert all(hasattr(L, s) for s in _lib.TERMINAL_SYMBOLS) and L.tde_terminal_version() == 1
-    assert not set(_lib.TERMINAL_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.REPLAY_SYMBOLS) | set(_lib.ONPOLICY_SYMBOLS))
-    assert [len(getattr(L, s).argtypes) for s in _lib.TERMINAL_SYMBOLS] == [0, 7, 7, 15]
-    assert "tde_terminal.hip" in build.UNITS and any(d.endswith("tde_terminal.h") for d in build.DEPS)
-    # the older lists and versions are as they were
-    assert len(_lib.SYMBOLS) == 31 and _abi.TDE_ABI_VERSION == 14 == L.tde_abi_version()
-    assert L.tde_replay_version() == 1 == _abi.TDE_REPLAY_VERSION and L.tde_onpolicy_version() == 1 == _abi.TDE_ONPOLICY_VERSION
-    assert len(_lib.REPLAY_SYMBOLS) == 5 and len(_lib.ONPOLICY_SYMBOLS) == 3
-
-
-def test_a_library_without_the_terminal_symbols_is_a_stale_build(monkeypatch):
-    from torchdriveenv_amd import _lib
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "TERMINAL_SYMBOLS", _lib.TERMINAL_SYMBOLS + ["tde_terminal_not_there"])
-    with pytest.raises(_lib.TdeError, match=r"lacks symbols \['tde_terminal_not_there'\]: stale build\?"):
-        _lib.load()
-    monkeypatch.undo()
-    _lib.load()
 
 
 # ---- every host-side refusal, before any launch -------------------------------------------------------------------------------------

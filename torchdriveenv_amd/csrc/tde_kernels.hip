@@ -1,6 +1,8 @@
-// tde_kernels.hip — libtde_hip.so as ONE translation unit: every unit of the library included here.  build.py compiles the units
-// side by side instead (about a third of the wall time on 8 cores); this form serves the A/B and resource-probe scripts
-// (scripts/build_variant.sh, scripts/kernel_resources.sh, scripts/probe_kernel.sh), which pass one source file to hipcc.
+// tde_kernels.hip — libtde_hip.so as ONE translation unit: every unit of build.py's UNITS included here (tests/test_abi_families_cpu.py
+// holds the two lists equal).  build.py compiles the units side by side instead (about a third of the wall time on 8 cores); this form
+// serves the A/B and resource-probe scripts (scripts/build_variant.sh, scripts/make_stamped_build.py, scripts/kernel_resources.sh,
+// scripts/probe_kernel.sh), which pass one source file to hipcc.  The units' anonymous namespaces merge here, so a host helper's name
+// must be unique across units.
 #ifndef TDE_KERNEL_PROBE
 #define TDE_TU_API 1
 #endif
@@ -30,5 +32,11 @@
 #include "tde_forecast.hip"
 #include "tde_forecast_scene.hip"
 #include "tde_plan_scene.hip"
+#include "tde_replay.hip"
+#include "tde_onpolicy.hip"
+#include "tde_terminal.hip"
+#include "tde_nstep.hip"
+#include "tde_priority.hip"
+#include "tde_sequence.hip"
 #include "tde_snapshot.hip"
 #endif

@@ -78,7 +78,7 @@ using namespace tde_host;
 
 namespace {
 
-unsigned env_blocks(int B) { return ring_blocks(B, tde::kTermEnvs); }
+unsigned term_blocks(int B) { return ring_blocks(B, tde::kTermEnvs); }
 
 // the ring and the pool beside it; fills the launch's argument block
 int check_terminal(const char *fn, const tde_replay *rp, const tde_terminal *tm, tde::TerminalArgs &a)
@@ -120,7 +120,7 @@ int tde_terminal_stash(int32_t B, int32_t row_bytes, const uint8_t *done_bits, c
     const int64_t al = vec ? 16 : 4;
     if (src_stride % al != 0 || !aligned(src, al) || !aligned(dst, al))
         return bad_in(fn, "src, src_stride and dst must be multiples of 16 (row_bytes not a multiple of 16: 4)");
-    tde::terminal_stash_kernel<<<env_blocks(B), tde::kTermEnvs, 0, (hipStream_t)stream>>>(B, row_bytes, vec, done_bits, src, src_stride, dst);
+    tde::terminal_stash_kernel<<<term_blocks(B), tde::kTermEnvs, 0, (hipStream_t)stream>>>(B, row_bytes, vec, done_bits, src, src_stride, dst);
     return tde_host::launch_status(fn);
 }
 
@@ -133,7 +133,7 @@ int tde_terminal_push(const tde_replay *rp, const tde_terminal *tm, int32_t w, c
     if (rc || (rc = check_slot(fn, rp, w)) != 0) return rc;
     if (!done_bits) return bad_in(fn, "NULL argument");
     if ((rc = check_src(fn, a.row, a.vec, term_src, term_stride, "term_src", "term_stride")) != 0) return rc;
-    tde::terminal_push_kernel<<<env_blocks(rp->B), tde::kTermEnvs, 0, (hipStream_t)stream>>>(a, w, done_bits, term_src, term_stride);
+    tde::terminal_push_kernel<<<term_blocks(rp->B), tde::kTermEnvs, 0, (hipStream_t)stream>>>(a, w, done_bits, term_src, term_stride);
     return tde_host::launch_status(fn);
 }
 
