@@ -83,7 +83,7 @@ def main():
     steps = a.capacity + 8
     for t in range(steps):
         act = low + (high - low) * torch.rand(B, 2, device=dev, generator=gen)
-        store[(t % Ct) * B:(t % Ct + 1) * B].copy_(env._obs)
+        store[(t % Ct) * B:(t % Ct + 1) * B].copy_(env.observer.obs)
         obs, *_ = env.step(act)
         store_done[(t % Ct) * B:(t % Ct + 1) * B].copy_(env.state["done_bits"])
         buf.push(act)

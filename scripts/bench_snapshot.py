@@ -68,7 +68,7 @@ def main():
     low, high = (torch.tensor(v, device=dev) for v in (env.action_space.low, env.action_space.high))
     for t in range(8):
         env.step(low + (high - low) * torch.rand(B, 2, device=dev, generator=gen))
-    src, stack = env.state, env._stack
+    src, stack = env.state, env.observer.stack
     from torchdriveenv_amd.snapshot import _handle_for
     from torchdriveenv_amd.state import EnvState
 

@@ -47,7 +47,7 @@ def main():
     for t in range(a.max_steps + a.capacity // 2):       # the ring ends up holding the step at which every env ran out
         plain.step(acts[t % 16]), term.step(acts[t % 16])
         pbuf.push(acts[t % 16]), tbuf.push(acts[t % 16])
-    assert torch.equal(plain._obs, term._obs) and torch.equal(pbuf.done, tbuf.done)
+    assert torch.equal(plain.observer.obs, term.observer.obs) and torch.equal(pbuf.done, tbuf.done)
     stored = (tbuf.first + torch.arange(tbuf.count, device=dev)) % tbuf.C      # (the open slot holds no step)
     fin, pooled = (tbuf.done[stored] & 3) != 0, int((tbuf.ref[stored] >= 0).sum())
     lines = [f"terminal observations: {B} envs x 16 agents, frame_stack {ns}, capacity_steps {a.capacity}, pool rows per step {tbuf.M}; "
@@ -65,7 +65,7 @@ def main():
                  f"(+{s1[0] - s0[0]:.1f} us)")
     # what the option adds to a step, each part called alone on the state the last step left (its mask: the envs that step finished)
     st = term.state
-    src, off, stride = term._terminal_source(term._obs)
+    src, off, stride = term.observer.newest_frame()
 
     def mask():
         torch.bitwise_or(st["terminated"], st["truncated"], out=term._term_mask)

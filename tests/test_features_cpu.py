@@ -292,3 +292,44 @@ def test_single_agent_wrapper_transforms_mirror_the_reference():
     back = w.transform_in({"a": out["a"], "c": 3.5})
     assert back["a"].shape == (1, 1, 2, 3) and torch.equal(back["a"], t) and back["c"] == 3.5
     assert w.torch_device == torch.device("cpu")           # attribute access falls through to the wrapped env
+
+
+def test_observation_layout_is_the_one_statement_of_shape_dtype_and_modes():
+    """config.observation_layout: what the env's observation_space, the VecEnv's host ring and the sharded env's shared buffer are made
+    from, and where the obs_mode / frame_stack / vector_obs combinations that do not exist are refused - with the messages the env gave"""
+    import torch
+
+    from torchdriveenv_amd.config import VectorObs, observation_layout
+
+    cfg = EnvConfig(seed=1)
+    small = EnvConfig(seed=1, simulator=SimulatorConfig(renderer=RendererConfig(res=48)))
+    assert observation_layout(cfg) == ((3, 64, 64), torch.uint8)
+    assert observation_layout(cfg, "birdview", 1) == ((3, 64, 64), torch.uint8)
+    assert observation_layout(cfg, "birdview", 3) == ((9, 64, 64), torch.uint8)
+    assert observation_layout(small, "birdview", 1) == ((3, 48, 48), torch.uint8)
+    assert observation_layout(small, "birdview", 3) == ((9, 48, 48), torch.uint8)
+    assert observation_layout(cfg, "birdview", 0) == ((3, 64, 64), torch.uint8)             # (the env reads frame_stack < 1 as 1)
+    for fs in (1, 3):
+        assert observation_layout(small, "state", fs) == ((8,), torch.float32)              # (no stack of compact observations)
+    assert observation_layout(cfg, "vector", 1) == ((VectorObs().dim,), torch.float32) == ((10 + 9 * 8 + 3 * 32,), torch.float32)
+    other = VectorObs(k_neighbours=2, n_rays=4)
+    assert observation_layout(small, "vector", 1, other) == ((10 + 9 * 2 + 3 * 4,), torch.float32)
+    assert observation_layout(cfg, "vector", 1, dict(k_neighbours=0, n_rays=0)) == ((10,), torch.float32)
+    with pytest.raises(ValueError, match="obs_mode must be 'birdview', 'state' or 'vector'"):
+        observation_layout(cfg, "rgb", 1)
+    with pytest.raises(ValueError, match="obs_mode='vector' has no frame stack: frame_stack must be 1"):
+        observation_layout(cfg, "vector", 3)
+    for mode in ("birdview", "state"):
+        with pytest.raises(ValueError, match="vector_obs= needs obs_mode='vector'"):
+            observation_layout(cfg, mode, 1, other)
+    with pytest.raises(ValueError, match=r"vector_obs: k_neighbours must be in \[0, 16\] and n_rays in \[0, 64\]"):
+        observation_layout(cfg, "vector", 1, VectorObs(k_neighbours=17))
+    with pytest.raises(TypeError, match="vector_obs must be a VectorObs"):
+        observation_layout(cfg, "vector", 1, 3)
+    # the env refuses the same, with the same words, before it touches a device
+    from torchdriveenv_amd.env import BatchedWaypointEnv
+
+    for kw, msg in ((dict(obs_mode="rgb"), "obs_mode must be"), (dict(obs_mode="vector", frame_stack=3), "has no frame stack"),
+                    (dict(vector_obs=other), "vector_obs= needs obs_mode='vector'")):
+        with pytest.raises(ValueError, match=msg):
+            BatchedWaypointEnv(cfg, None, num_envs=2, **kw)

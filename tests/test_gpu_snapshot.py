@@ -252,7 +252,7 @@ def test_a_fork_continues_like_its_source_until_it_respawns(worlds):
     env.reset()
     for t in range(3):
         env.step(acts[t])
-    before = record(env, env._obs)
+    before = record(env, env.observer.obs)
     obs = env.fork(2, [5, 0])
     after = record(env, obs)
     same_rows(after, before, [1, 2, 3, 4], env.A, "fork leaves the others alone")
@@ -426,7 +426,7 @@ def test_snapshot_and_capture_leave_the_env_untouched(worlds):
     buf = env.replay_buffer(8)
     draws = buf.draws
     before = {k: v.clone() for k, v in env.state.arrays.items() if v is not None}
-    obs0, lay0, phase0 = obs.clone(), env._stack.layers.clone(), env._stack.phase
+    obs0, lay0, phase0 = obs.clone(), env.observer.stack.layers.clone(), env.observer.stack.phase
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated()
     snap = env.snapshot([0, 5, 2])
@@ -435,7 +435,7 @@ def test_snapshot_and_capture_leave_the_env_untouched(worlds):
     assert torch.cuda.memory_allocated() > mem               # they allocate when made - and only then
     for k, v in before.items():                              # every array, the caches included: nothing of the live state moved
         assert torch.equal(v.view(-1).view(torch.uint8), env.state.arrays[k].view(-1).view(torch.uint8)), k
-    assert torch.equal(obs0, env._obs) and torch.equal(lay0, env._stack.layers) and env._stack.phase == phase0 and buf.draws == draws
+    assert torch.equal(obs0, env.observer.obs) and torch.equal(lay0, env.observer.stack.layers) and env.observer.stack.phase == phase0 and buf.draws == draws
     # and the snapshot holds the rows
     for k in _abi.SNAPSHOT_COPIED + _abi.SNAPSHOT_OUTPUT_ARRAYS:
         if before.get(k) is not None:

@@ -109,7 +109,12 @@ def test_ops_wrappers_reject_host_tensors_and_bad_shapes():
 def _fake_env(**over):
     kw = dict(auto_reset=True, state={"done_bits": object()}, num_envs=4, torch_device="cuda:0", obs_mode="birdview", frame_stack=3, _res=64)
     kw.update(over)
-    return types.SimpleNamespace(**kw)
+    from torchdriveenv_amd.config import EnvConfig, RendererConfig, SimulatorConfig
+    from torchdriveenv_amd.observe import make_observer
+
+    env = type("FakeEnv", (types.SimpleNamespace,), {})(config=EnvConfig(simulator=SimulatorConfig(renderer=RendererConfig(res=kw["_res"]))), **kw)
+    env.observer = make_observer(env)                    # (the observers of birdview and state touch no device when they are made)
+    return env
 
 
 def _bare(pos, finished, n_steps=3, B=4):

@@ -248,6 +248,26 @@ def check_vector_obs(vo):
     return vo
 
 
+def observation_layout(cfg: EnvConfig, obs_mode="birdview", frame_stack=1, vector_obs=None):
+    """(shape, torch dtype) of ONE env's observation - the single statement of it, and of which obs_mode / frame_stack / vector_obs
+    combinations exist: (3 * frame_stack, res, res) uint8 for "birdview", (8,) float32 for "state", (VectorObs.dim,) float32 for
+    "vector" (vector_obs None: VectorObs()).  Pure: no device is touched."""
+    import torch
+
+    if obs_mode not in ("birdview", "state", "vector"):
+        raise ValueError("obs_mode must be 'birdview', 'state' or 'vector'")
+    if obs_mode == "vector" and int(frame_stack) > 1:
+        raise ValueError("obs_mode='vector' has no frame stack: frame_stack must be 1")
+    if vector_obs is not None and obs_mode != "vector":
+        raise ValueError("vector_obs= needs obs_mode='vector'")
+    if obs_mode == "birdview":
+        res = int(cfg.simulator.renderer.res)
+        return (3 * max(1, int(frame_stack)), res, res), torch.uint8
+    if obs_mode == "state":
+        return (8,), torch.float32
+    return (check_vector_obs(vector_obs if vector_obs is not None else VectorObs()).dim,), torch.float32
+
+
 PLANNER_PREDICT = ("constant", "route", "queue")
 
 

@@ -17,8 +17,9 @@ import numpy as np
 import torch
 
 from . import _abi, ops
-from .config import (EnvConfig, NearField, Planner, VectorObs, WaypointSuite, check_near_field, check_plan_react, check_plan_refine, check_planner, check_vector_obs,
+from .config import (EnvConfig, NearField, Planner, WaypointSuite, check_near_field, check_plan_react, check_plan_refine, check_planner, observation_layout,
                      render_flags, to_tde_config, validate)
+from .observe import make_observer
 from .state import EnvState
 from .video import VideoRecorder
 from .world import (NearFieldTable, World, assemble_world, build_near_field, check_threshold, corridor_mesh,
@@ -686,13 +687,7 @@ class BatchedWaypointEnv:
             raise ValueError("a NearFieldTable belongs to the World it was built for: pass that World as `data`")
         if binding not in ("ext", "ctypes"):
             raise ValueError("binding must be 'ext' or 'ctypes'")                                              # ref gym_env.py:79-80 and the fields this path rejects
-        if obs_mode not in ("birdview", "state", "vector"):
-            raise ValueError("obs_mode must be 'birdview', 'state' or 'vector'")
-        if obs_mode == "vector" and int(frame_stack) > 1:
-            raise ValueError("obs_mode='vector' has no frame stack: frame_stack must be 1")
-        if vector_obs is not None and obs_mode != "vector":
-            raise ValueError("vector_obs= needs obs_mode='vector'")
-        self.vector_obs = check_vector_obs(vector_obs if vector_obs is not None else VectorObs()) if obs_mode == "vector" else None
+        observation_layout(cfg, obs_mode, frame_stack, vector_obs)  # (raises on an obs_mode / frame_stack / vector_obs that does not exist)
         self.config = cfg
         dev = device or cfg.device or ("cuda" if torch.cuda.is_available() else None)
         if dev is None or not torch.cuda.is_available():
@@ -747,24 +742,20 @@ class BatchedWaypointEnv:
         if near_field is not None:
             self.dnf = near_field.to_device(self.torch_device)
             self.dworld.near_field = self.dnf                        # (ops.env_rollout / env_step_render refuse such a world)
-        # obs_mode "state": tde_env_step writes the compact observation itself (no second launch per step)
-        self.info_magnitudes = bool(info_magnitudes)
-        self.state = EnvState(self.num_envs, self.A, device=self.torch_device, with_info=with_info,
-                              with_obs=(obs_mode == "state"), with_magnitudes=self.info_magnitudes, with_slot_route=self._nf_routed)
         self.obs_mode, self.frame_stack = obs_mode, max(1, int(frame_stack))
         r = cfg.simulator.renderer
         self._res, self._fov = int(r.res), float(r.fov)
         self._rflags = render_flags(cfg)
-        self._obs = self._stack = None
+        self.observer = make_observer(self, vector_obs)              # (observe.py: every observation buffer and what refreshes it)
+        self.vector_obs, self._after_step = self.observer.vector_obs, self.observer.after_step    # (bound once: every step() calls it)
+        self.info_magnitudes = bool(info_magnitudes)
+        self.state = EnvState(self.num_envs, self.A, device=self.torch_device, with_info=with_info,
+                              with_obs=self.observer.state_obs, with_magnitudes=self.info_magnitudes, with_slot_route=self._nf_routed)
         self.action_space = _box(ACTION_LOW, ACTION_HIGH)
-        self.observation_space = (_box(0, 255, (3 * self.frame_stack, self._res, self._res), np.uint8) if obs_mode == "birdview" else
-                                  _box(-np.inf, np.inf, (self.vector_obs.dim if obs_mode == "vector" else 8,), np.float32))
-        self._vobs = self._ray_dir = None
+        shape, dtype = self.observer.layout
+        self.observation_space = _box(0, 255, shape, np.uint8) if dtype is torch.uint8 else _box(-np.inf, np.inf, shape, np.float32)
         self._plan_out = self._plan_diag = self._refine = None
         self._plan_fc = self._plan_lat = None          # planner.predict == "route" / "queue": the forecast buffer, the lattice as one-knot sequences
-        if obs_mode == "vector":
-            self._vobs = torch.zeros((self.num_envs, self.vector_obs.dim), dtype=torch.float32, device=self.torch_device)
-            self._ray_dir = torch.from_numpy(self.vector_obs.ray_directions()).to(self.torch_device)
         self.reward_range = (-float("inf"), float("inf"))           # ref gym_env.py:97
         self._vec = None
         self._mag = self.state["magnitudes"]                         # float32 [B, 4] written by the step (None: indicators)
@@ -778,16 +769,13 @@ class BatchedWaypointEnv:
         else:
             self._h, self._hnf = ops.CtypesHandle(self.tde_cfg, self.dworld, self.state), self.dnf
         # terminal_obs: the newest frame each env showed when it last finished (tde_terminal_stash), and what step() needs around it
-        self.terminal_frames = self._term_mask = self._term_packed = self._term_pack_struct = None
+        self.terminal_frames = self._term_mask = None
         if self.terminal_obs:
-            if obs_mode == "birdview":
-                if (self._res * self._res) % 16 != 0:
-                    raise ValueError(f"terminal_obs=True: H * W = {self._res * self._res} must be a multiple of 16 (the planes move as 16-byte words)")
-                self.terminal_frames = torch.full((self.num_envs, self._res * self._res), _abi.LAYER_BLANK, dtype=torch.uint8,
-                                                  device=self.torch_device)
-            else:
-                self.terminal_frames = torch.zeros((self.num_envs, self.observation_space.shape[0]), dtype=torch.float32,
-                                                   device=self.torch_device)
+            plane = self.observer.plane                              # (0: the observation is float rows)
+            if plane % 16 != 0:
+                raise ValueError(f"terminal_obs=True: H * W = {plane} must be a multiple of 16 (the planes move as 16-byte words)")
+            self.terminal_frames = (torch.full((self.num_envs, plane), _abi.LAYER_BLANK, dtype=torch.uint8, device=self.torch_device) if plane else
+                                    torch.zeros((self.num_envs, shape[0]), dtype=torch.float32, device=self.torch_device))
             self._term_mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.torch_device)
         if self.dnf is None:
             # the world's first-step gap cache for this configuration, now - not inside the first step() (which may be under a stream capture)
@@ -817,29 +805,19 @@ class BatchedWaypointEnv:
         scn = None
         if options is not None and options.get("scenario") is not None:
             scn = ops.check_scenario_ids(options["scenario"], self.num_envs, self.world.n_scn).to(self.torch_device)
-        if scn is None and m is not None and self.obs_mode == "birdview" and self._obs is not None and self.dnf is None:
-            # the SB3-style auto-reset: the re-spawn and the re-spawned views' first observation in ONE C-ABI call
-            if self._stack is not None:
-                self._obs = self._stack.reset_rerender(self.tde_cfg, self.dworld, self.state, m, self._fov)
-            else:
-                self._h.reset_render(m, int(self.tde_cfg.flags), self._obs, self._res, self._res, self._fov, 1, None, 0, self._rflags)
-            return self._obs
+        # the SB3-style auto-reset: the re-spawn and the re-spawned views' first observation in ONE C-ABI call, where there is one
+        obs = self.observer.reset_reobserve(m) if scn is None and m is not None else None
+        if obs is not None:
+            return obs
         if scn is not None:
             self._h.reset_to(scn, m, int(self.tde_cfg.flags))
         else:
             self._h.reset(m, int(self.tde_cfg.flags))
         self._spawn_near_field(m)                                    # (near-field envs: reset -> spawn -> render)
-        if self.obs_mode == "vector":
-            return self._vector_obs(m)                               # (a masked reset rewrites the re-spawned envs' rows only)
-        if self.obs_mode == "state" or m is None or self._obs is None:
-            if self._stack is not None:
-                self._stack.clear()                                  # VecFrameStack clears the stack on reset
-            return self.get_obs()
-        if self._stack is not None:
-            self._obs = self._stack.rerender(self.tde_cfg, self.dworld, self.state, m, self._fov)
-        else:
-            self._render1(self._obs, only=m)
-        return self._obs
+        if m is not None:
+            return self.observer.reobserve(m)
+        self.observer.clear()                                        # VecFrameStack clears the stack on reset
+        return self.observer.observe()
 
     def _spawn_near_field(self, mask=None, done=False):
         """tde_near_field_spawn on the envs in `mask` (all: None), or - done=True - on the envs the last step finished (the
@@ -863,14 +841,6 @@ class BatchedWaypointEnv:
         finally:
             self.tde_cfg.flags = full
 
-    def _flag_views(self):
-        """the state's terminated / truncated bytes seen as bool (no copy), formed once: the buffers never move"""
-        v = self.__dict__.get("_tt_views")
-        st = self.state
-        if v is None or v[0] is not st["terminated"]:
-            v = self._tt_views = (st["terminated"], st["terminated"].view(torch.bool), st["truncated"].view(torch.bool))
-        return v[1], v[2]
-
     def step(self, actions):
         # (the host side of a step is what a closed loop of small kernels waits for: no tensor op that is not needed)
         a = actions
@@ -882,35 +852,16 @@ class BatchedWaypointEnv:
         self._h.step(a, int(self.tde_cfg.flags))
         if self.dnf is not None and self.auto_reset:
             self._spawn_near_field(done=True)                        # the envs the step re-spawned, before they are observed
-        st = self.state
-        if self.obs_mode == "state":
-            obs = st["obs"]
-        elif self.obs_mode == "vector":
-            obs = self._vector_obs()
-        else:
-            fresh = None
-            if self.auto_reset and self.frame_stack > 1:
-                # envs that finished were re-spawned inside the kernel: their frame stack restarts blank.  The render
-                # kernel reads bits 0-1 of the mask, which is exactly the done part of done_bits
-                fresh = st["done_bits"] if st["done_bits"] is not None else (st["terminated"] | st["truncated"])
-            obs = self.get_obs(fresh)
-        # uint8 0/1 flags seen as bool without a copy; info entries are only computed when they are read
-        term, trunc = self._flag_views()
-        return obs, st["reward"], term, trunc, _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
+        return self._result(self._after_step())
 
-    def _terminal_source(self, obs):
-        """(tensor, byte offset, byte stride) of the newest frame of the observation `obs` the env just took: the layer plane of the
-        frame-stack ring, the plane tde_replay_pack makes of a colour observation without one, or the float32 row"""
-        if self.obs_mode != "birdview":
-            return obs, 0, 4 * obs.shape[1]
-        plane = self._res * self._res
-        if self._stack is not None:
-            st = self._stack
-            return st.layers, ((st.phase - 1) % self.frame_stack) * plane, self.frame_stack * plane
-        if self._term_packed is None:
-            self._term_packed = torch.empty((self.num_envs, plane), dtype=torch.uint8, device=self.torch_device)
-            self._term_pack_struct = ops.replay_pack_struct(self.num_envs, plane, self._term_packed)
-        return ops.replay_pack(self._term_pack_struct, self.torch_device, obs, self._term_packed), 0, plane
+    def _result(self, obs):
+        """what a step returns with the observation `obs`: the state's terminated / truncated bytes seen as bool (no copy; the views are
+        formed once: the buffers never move); info entries are only computed when they are read"""
+        v = self.__dict__.get("_tt_views")
+        st = self.state
+        if v is None or v[0] is not st["terminated"]:
+            v = self._tt_views = (st["terminated"], st["terminated"].view(torch.bool), st["truncated"].view(torch.bool))
+        return obs, st["reward"], v[1], v[2], _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
 
     def _step_terminal(self, a):
         """step() of a terminal_obs env: the step without the in-kernel re-spawn (the kernel form WaypointVecEnv.step_wait uses) ->
@@ -919,45 +870,24 @@ class BatchedWaypointEnv:
         st = self.state
         with self._without_autoreset():
             self._h.step(a, int(self.tde_cfg.flags))
-            obs = st["obs"] if self.obs_mode == "state" else self._vector_obs() if self.obs_mode == "vector" else self.get_obs()
-        src, off, stride = self._terminal_source(obs)
-        ops.terminal_stash(self.torch_device, st["done_bits"], src, off, stride, self.terminal_frames)
-        obs = self.reset(mask=torch.bitwise_or(st["terminated"], st["truncated"], out=self._term_mask))
-        term, trunc = self._flag_views()
-        return obs, st["reward"], term, trunc, _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
+            self._after_step()
+        ops.terminal_stash(self.torch_device, st["done_bits"], *self.observer.newest_frame(), self.terminal_frames)
+        return self._result(self.reset(mask=torch.bitwise_or(st["terminated"], st["truncated"], out=self._term_mask)))
 
     def _step_then_post_step(self, a):
         """the round-4 form of a step with magnitudes, kept for A/B runs and as a second witness of the fused path
         (tests/test_gpu_magnitudes.py): step without in-kernel re-spawn -> tde_env_post_step (the magnitudes of the infractions the
         step flagged + the re-spawn of the envs it finished, one launch) -> the observation.  Same results as step(), one launch
         more."""
-        st = self.state
         if self._mag is None:
             raise RuntimeError("needs info_magnitudes=True")
-        full = int(self.tde_cfg.flags)
-        flags = full & ~_abi.F_AUTORESET
-        post = flags | (full & _abi.F_AUTORESET)            # (WaypointVecEnv.step_wait clears the flag: it re-spawns the envs itself)
-        self.tde_cfg.flags = flags
-        try:
-            self._h.step(a, flags)
-            self._h.post_step(self._mag, post)
-        finally:
-            self.tde_cfg.flags = full
-        if full & _abi.F_AUTORESET:
+        full = int(self.tde_cfg.flags)                      # (WaypointVecEnv.step_wait clears F_AUTORESET: it re-spawns the envs itself)
+        with self._without_autoreset():
+            self._h.step(a, int(self.tde_cfg.flags))
+            self._h.post_step(self._mag, full)
+        if self.auto_reset:
             self._spawn_near_field(done=True)
-        term, trunc = self._flag_views()
-        info = _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
-        if self.obs_mode == "state":
-            obs = st["obs"]                                           # written by the step, refreshed by the re-spawn
-        elif self.obs_mode == "vector":
-            obs = self._vector_obs()
-        else:
-            # the finished envs were re-spawned: their frame stacks restart blank (bits 0-1 of done_bits = the step's done flags)
-            fresh = None
-            if (full & _abi.F_AUTORESET) and self.frame_stack > 1:
-                fresh = st["done_bits"] if st["done_bits"] is not None else (st["terminated"] | st["truncated"])
-            obs = self.get_obs(fresh)
-        return obs, st["reward"], term, trunc, info
+        return self._result(self._after_step())
 
     def rollout(self, actions):
         """K open-loop steps from a resident [K,B,2] action tensor -> (reward [K,B], done bits [K,B]).  (The Monitor-style
@@ -979,29 +909,7 @@ class BatchedWaypointEnv:
         return reward, done
 
     def get_obs(self, fresh=None):
-        if self.obs_mode == "vector":
-            return self._vector_obs()
-        if self.obs_mode == "state":
-            # x, y, psi, v, target offset (forward, left) in the ego frame, target-exists flag, environment_steps
-            self._h.state_obs(self.state["obs"])
-            return self.state["obs"]
-        if self.frame_stack > 1:
-            if self._stack is None:
-                self._stack = ops.FrameStack(self.num_envs, self.frame_stack, self._res, self._res, self.torch_device,
-                                             flags=self._rflags, handle=self._h)
-            self._obs = self._stack.render(self.tde_cfg, self.dworld, self.state, self._fov, fresh=fresh)
-            return self._obs
-        if self._obs is None:
-            self._obs = torch.zeros((self.num_envs, 3, self._res, self._res), dtype=torch.uint8, device=self.torch_device)
-        self._render1(self._obs)
-        return self._obs
-
-    def _vector_obs(self, only=None):
-        """tde_vector_obs into the env's [B, D] buffer (the rows of `only`, uint8 [B], or all) -> the buffer"""
-        vo = self.vector_obs
-        self._h.vector_obs(self._vobs, self._ray_dir, int(vo.k_neighbours), int(vo.n_rays), float(vo.neighbour_radius),
-                           float(vo.ray_range), float(vo.ray_step), only, int(self.tde_cfg.flags))
-        return self._vobs
+        return self.observer.observe(fresh)
 
     def plan_actions(self, out=None, only=None, diag=False):
         """the sampling planner's action for every ego on the state as it is (tde_plan_action with self.planner) -> float32 [B, 2] on
@@ -1222,24 +1130,15 @@ class BatchedWaypointEnv:
                 a = self.plan_actions() if isinstance(policy, str) else policy(obs)
                 obs = self.step(a)[0]
                 self._h.eval_advance(ev.plan, ev.round, ev.active, ev.acc, ev.results, flags)
-                if self.dnf is not None or self.obs_mode != "state":
-                    # the envs the advance re-spawned: finished at this step and still evaluating
+                if self.dnf is not None or not self.observer.state_obs:
+                    # the envs the advance re-spawned: finished at this step and still evaluating (it rewrites a state observation's rows itself)
                     torch.bitwise_or(st["terminated"], st["truncated"], out=respawned).bitwise_and_(ev.active)
                     self._spawn_near_field(respawned)
-                    if self.obs_mode == "vector":
-                        obs = self._vector_obs(respawned)
-                    elif self.obs_mode == "birdview":
-                        if self._stack is not None:
-                            obs = self._obs = self._stack.rerender(self.tde_cfg, self.dworld, st, respawned, self._fov)
-                        else:
-                            self._render1(self._obs, only=respawned)
+                    if not self.observer.state_obs:
+                        obs = self.observer.reobserve(respawned)
         if bool(ev.active.any()):
             raise RuntimeError("evaluate(): envs still active after ceil(jobs / B) * max_steps steps")
         return EvalResult.from_records(ev.records().reshape(-1)[:len(jobs)], jobs)
-
-    def _render1(self, out, only=None):
-        """single-frame raster of every (or the masked) view into `out`"""
-        self._h.render(out, self._res, self._res, self._fov, 1, None, 0, self._rflags, None, only)
 
     def get_info(self):
         """info schema of the reference (ref gym_env.py:419-437), one entry per env; a mapping whose tensors are formed
@@ -1265,8 +1164,9 @@ class BatchedWaypointEnv:
     def state_dict(self):
         """snapshot of every mutable buffer (checkpoint / parity replays), the frame-stack ring included"""
         sd = {k: v.clone() for k, v in self.state.arrays.items() if v is not None}
-        if self._stack is not None:
-            sd["_frame_stack"] = self._stack.state_dict()
+        ring = self.observer.state_dict()
+        if ring is not None:
+            sd["_frame_stack"] = ring
         if self.terminal_frames is not None:
             sd["_terminal_frames"] = self.terminal_frames.clone()
         return sd
@@ -1274,11 +1174,7 @@ class BatchedWaypointEnv:
     def load_state_dict(self, sd):
         for k, v in sd.items():
             if k == "_frame_stack":
-                if self._stack is None:
-                    self._stack = ops.FrameStack(self.num_envs, self.frame_stack, self._res, self._res, self.torch_device,
-                                                 flags=self._rflags, handle=self._h)
-                self._stack.load_state_dict(v)
-                self._obs = self._stack.obs
+                self.observer.load_state_dict(v)
             elif k == "_terminal_frames":
                 if self.terminal_frames is None:
                     raise ValueError("the state holds terminal frames, this env was built without terminal_obs=True")
@@ -1296,7 +1192,7 @@ class BatchedWaypointEnv:
         buffers are not."""
         from . import snapshot as S
 
-        return S.snapshot(self, envs)
+        return S.EnvSnapshot(self, envs)
 
     def restore(self, snap, envs=None):
         """put the rows of `snap` back into the envs `envs` (default: the indices they were taken from) and return the observation
@@ -1514,8 +1410,8 @@ class WaypointVecEnv(_SB3VecEnv if _SB3VecEnv is not None else object):
                                    if env.state["info"] is not None or k not in LazyInfos.INFO_COLS + ("reached_waypoint_num",))
         self._t_start = time.time()
         self._pending = None
-        shape = (env.num_envs,) + tuple(env.observation_space.shape)
-        odt = torch.uint8 if env.obs_mode == "birdview" else torch.float32
+        shape, odt = env.observer.layout
+        shape = (env.num_envs,) + shape
         if obs_buffers is not None:
             for b in obs_buffers:
                 if tuple(b.shape) != shape or b.dtype != odt or b.is_cuda or not b.is_contiguous():

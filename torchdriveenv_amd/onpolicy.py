@@ -60,9 +60,8 @@ class RolloutBuffer:
         T = int(n_steps)
         if T < 1:
             raise ValueError(f"n_steps must be >= 1, got {n_steps}")
-        n_stack = env.frame_stack if env.obs_mode == "birdview" else 1
         self.seed = int(getattr(env, "seed_value", 0) if seed is None else seed)
-        self.ring = ReplayBuffer(env, capacity_steps=T + n_stack, seed=self.seed, terminal_per_step=terminal_per_step)
+        self.ring = ReplayBuffer(env, capacity_steps=T + env.observer.n_stack, seed=self.seed, terminal_per_step=terminal_per_step)
         self.env, self.B, self.n_steps, self.dev = env, env.num_envs, T, torch.device(env.torch_device)
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
         self.values, self.log_probs, self.advantages, self.returns = (torch.zeros((T, self.B), dtype=torch.float32, device=self.dev)
@@ -159,8 +158,7 @@ class RolloutBuffer:
         out = self._out.get(n)
         if out is None:
             r = self.ring
-            shape, dt = ((n, 3 * r.n_stack, r.H, r.W), torch.uint8) if r.planes else ((n, r.D), torch.float32)
-            out = self._out[n] = {"observations": torch.empty(shape, dtype=dt, device=self.dev),
+            out = self._out[n] = {"observations": torch.empty((n,) + r.obs_shape, dtype=r.obs_dtype, device=self.dev),
                                   "actions": torch.empty((n, 2), dtype=torch.float32, device=self.dev),
                                   **{k: torch.empty(n, dtype=torch.float32, device=self.dev)
                                      for k in ("old_values", "old_log_prob", "advantages", "returns")}}

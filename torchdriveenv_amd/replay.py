@@ -179,22 +179,18 @@ class ReplayBuffer:
             raise ValueError("ReplayBuffer needs an env with with_info=True: it reads the step's done_bits")
         self.env, self.B, self.C, self.seed = env, env.num_envs, C_, int(seed)
         self.dev = env.torch_device
-        self.planes = env.obs_mode == "birdview"
-        self.n_stack = env.frame_stack if self.planes else 1
+        ob = env.observer
+        self.n_stack, self.plane, (self.obs_shape, self.obs_dtype) = ob.n_stack, ob.plane, ob.layout
+        self.planes, self.D = self.plane > 0, 0 if ob.plane else int(ob.layout[0][0])
         if C_ < self.n_stack + 1 or C_ < 2:
             raise ValueError(f"capacity_steps must be >= frame_stack + 1 = {max(2, self.n_stack + 1)} (a stack and its successor), got {C_}")
         if self.planes:
-            self.H = self.W = env._res
-            self.plane, self.D = self.H * self.W, 0
             if self.plane % 16 != 0:
                 raise ValueError(f"H * W = {self.plane} must be a multiple of 16 (the planes move as 16-byte words)")
             if self.plane > _abi.REPLAY_MAX_PLANE:
                 raise ValueError(f"H * W = {self.plane} exceeds {_abi.REPLAY_MAX_PLANE}")
             self.frames = torch.full((C_, self.B, self.plane), _abi.LAYER_BLANK, dtype=torch.uint8, device=self.dev)
-            # an env without a frame stack renders colours only: its observation goes back to a layer plane through here
-            self._packed = torch.empty((self.B, self.plane), dtype=torch.uint8, device=self.dev) if self.n_stack == 1 else None
         else:
-            self.plane, self.D = 0, int(env.observation_space.shape[0])
             self.frames = torch.zeros((C_, self.B, self.D), dtype=torch.float32, device=self.dev)
         self.action = torch.zeros((C_, self.B, 2), dtype=torch.float32, device=self.dev)
         self.reward = torch.zeros((C_, self.B), dtype=torch.float32, device=self.dev)
@@ -229,21 +225,6 @@ class ReplayBuffer:
         """bytes the ring holds per stored transition"""
         return (self.plane if self.planes else 4 * self.D) + 8 + 4 + 1 + 1
 
-    def _source(self):
-        """(tensor, byte offset, byte stride) of the newest frame of every env's current observation"""
-        env = self.env
-        if not self.planes:
-            src = env._vobs if env.obs_mode == "vector" else env.state["obs"]
-            return src, 0, 4 * self.D
-        if self.n_stack == 1:
-            if env._obs is None:
-                raise ValueError("the env has no observation yet: call env.reset() first")
-            return ops.replay_pack(self.struct, self.dev, env._obs, self._packed), 0, self.plane
-        st = env._stack
-        if st is None:
-            raise ValueError("the env has no observation yet: call env.reset() first")
-        return st.layers, ((st.phase - 1) % self.n_stack) * self.plane, self.n_stack * self.plane
-
     def begin(self, mask=None):
         """after env.reset() (mask None) or env.reset(mask=m): the open slot takes the re-spawned envs' first frame with age 0; on a
         buffer that already runs, the envs' last stored step is cut (REPLAY_CUT: its successor is not its next observation)"""
@@ -253,8 +234,7 @@ class ReplayBuffer:
                 raise ValueError(f"mask must have {self.B} elements")
         elif self._begun:
             mask = torch.ones(self.B, dtype=torch.uint8, device=self.dev)
-        src, off, stride = self._source()
-        ops.replay_begin(self.struct, self.dev, self.w, src, off, stride, mask)
+        ops.replay_begin(self.struct, self.dev, self.w, *self.env.observer.newest_frame(), mask)
         if self.pstruct is not None and not self._begun:
             ops.priority_reset(self.pstruct, self.struct, self.dev)
         self._begun = True
@@ -269,8 +249,7 @@ class ReplayBuffer:
                 and a.shape[1] == 2 and a.is_contiguous()):
             a = torch.as_tensor(actions, dtype=torch.float32, device=self.dev).reshape(self.B, 2).contiguous()
         st = self.env.state
-        src, off, stride = self._source()
-        ops.replay_push(self.struct, self.dev, self.w, a, st["reward"], st["done_bits"], src, off, stride)
+        ops.replay_push(self.struct, self.dev, self.w, a, st["reward"], st["done_bits"], *self.env.observer.newest_frame())
         if self.tstruct is not None:
             ops.terminal_push(self.struct, self.tstruct, self.dev, self.w, st["done_bits"], self.env.terminal_frames)
         self.w = (self.w + 1) % self.C
@@ -292,10 +271,7 @@ class ReplayBuffer:
 
     def _alloc(self, n):
         """a fresh set of the output tensors of a sample of `n` transitions"""
-        if self.planes:
-            shape, dt = (n, 3 * self.n_stack, self.H, self.W), torch.uint8
-        else:
-            shape, dt = (n, self.D), torch.float32
+        shape, dt = (n,) + self.obs_shape, self.obs_dtype
         return {"observations": torch.empty(shape, dtype=dt, device=self.dev),
                 "next_observations": torch.empty(shape, dtype=dt, device=self.dev),
                 "actions": torch.empty((n, 2), dtype=torch.float32, device=self.dev),
@@ -312,8 +288,7 @@ class ReplayBuffer:
                 "steps": torch.empty(n, dtype=torch.uint8, device=self.dev)}
 
     def _alloc_sequence(self, n, T):
-        obs = ((n, T + 1, 3 * self.n_stack, self.H, self.W), torch.uint8) if self.planes else ((n, T + 1, self.D), torch.float32)
-        return {"observations": torch.empty(obs[0], dtype=obs[1], device=self.dev),
+        return {"observations": torch.empty((n, T + 1) + self.obs_shape, dtype=self.obs_dtype, device=self.dev),
                 "actions": torch.empty((n, T, 2), dtype=torch.float32, device=self.dev),
                 "rewards": torch.empty((n, T), dtype=torch.float32, device=self.dev),
                 "dones": torch.empty((n, T), dtype=torch.uint8, device=self.dev),

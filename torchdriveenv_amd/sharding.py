@@ -137,16 +137,8 @@ class ShardedBatchedEnv:
             env_kw = dict(env_kw, near_field=near_field)
         self.devices = list(devices) if devices is not None else [r % ndev for r in range(self.n_shards)]
         self.num_envs = int(total_envs)
-        obs_mode = env_kw.get("obs_mode", "birdview")
-        fs = max(1, int(env_kw.get("frame_stack", 1)))
-        r = cfg.simulator.renderer
-        if obs_mode == "vector":
-            from .config import VectorObs, check_vector_obs
-            vo = env_kw.get("vector_obs")
-            oshape = (check_vector_obs(vo if vo is not None else VectorObs()).dim,)
-        else:
-            oshape = (3 * fs, int(r.res), int(r.res)) if obs_mode == "birdview" else (8,)
-        odt = torch.uint8 if obs_mode == "birdview" else torch.float32
+        from .config import observation_layout
+        oshape, odt = observation_layout(cfg, env_kw.get("obs_mode", "birdview"), env_kw.get("frame_stack", 1), env_kw.get("vector_obs"))
         self._shm = {"obs": torch.zeros((self.num_envs,) + oshape, dtype=odt).share_memory_(),
                      "reward": torch.zeros(self.num_envs, dtype=torch.float32).share_memory_(),
                      "done": torch.zeros(self.num_envs, dtype=torch.bool).share_memory_(),

@@ -36,12 +36,11 @@ def _as_rows(envs, B, what="envs"):
     return rows
 
 
-def _like_state(state, n, device):
-    """an EnvState of n rows with the optional arrays `state` carries, and no caches"""
+def _like(state):
+    """EnvState's keywords for a state with the optional arrays `state` carries, and no caches"""
     a = state.arrays
-    return EnvState(n, state.A, device=device, with_info=a["info"] is not None, with_obs=a["obs"] is not None,
-                    with_episode=a["ep_return"] is not None, with_cache=False, with_magnitudes=a["magnitudes"] is not None,
-                    with_slot_route=a["slot_route"] is not None)
+    return dict(with_info=a["info"] is not None, with_obs=a["obs"] is not None, with_episode=a["ep_return"] is not None, with_cache=False,
+                with_magnitudes=a["magnitudes"] is not None, with_slot_route=a["slot_route"] is not None)
 
 
 def _handle_for(venv, state):
@@ -51,17 +50,6 @@ def _handle_for(venv, state):
 
         return _ext.env_handle(venv.tde_cfg, venv.dworld, state)
     return ops.CtypesHandle(venv.tde_cfg, venv.dworld, state)
-
-
-def _env_frames(venv):
-    """(layers, obs, n_stack, plane, phase) of the env's birdview buffers: the frame-stack ring, or the single frame of an env without one
-    (layers None), or all None before the first observation / in the other observation modes"""
-    if venv.obs_mode != "birdview" or venv._obs is None:
-        return None, None, 0, 0, 0
-    plane = venv._res * venv._res
-    if venv._stack is not None:
-        return venv._stack.layers, venv._stack.obs, venv.frame_stack, plane, venv._stack.phase
-    return None, venv._obs, 1, plane, 0
 
 
 class EnvSnapshot(EnvState):
@@ -80,17 +68,14 @@ class EnvSnapshot(EnvState):
         rows = _as_rows(envs, venv.num_envs)
         src = venv.state
         dev = venv.torch_device
-        a = src.arrays
-        EnvState.__init__(self, len(rows), src.A, device=dev, with_info=a["info"] is not None, with_obs=a["obs"] is not None,
-                          with_episode=a["ep_return"] is not None, with_cache=False, with_magnitudes=a["magnitudes"] is not None,
-                          with_slot_route=a["slot_route"] is not None)
+        EnvState.__init__(self, len(rows), src.A, device=dev, **_like(src))
         self.envs = rows
         self.envs_t = torch.tensor(rows, dtype=torch.int32, device=dev)
         self._own = torch.arange(len(rows), dtype=torch.int32, device=dev)
         self._handle = _handle_for(venv, self)
         self.layers = self.obs = self.vector = self.terminal_frames = None
         self.n_stack = self.plane = 0
-        layers, obs, ns, plane, phase = _env_frames(venv)
+        layers, obs, ns, plane, phase = venv.observer.frames()
         frames = None
         if obs is not None:
             self.n_stack, self.plane = ns, plane
@@ -99,15 +84,8 @@ class EnvSnapshot(EnvState):
             self.obs = torch.empty((len(rows),) + tuple(obs.shape[1:]), dtype=torch.uint8, device=dev)
             frames = ops.snapshot_frames(layers, self.layers, obs, self.obs, ns, plane, phase, 0)
         ops.state_copy(src, self, self.envs_t, self._own, frames=frames, outputs=True, check=False, handles=(venv._h, self._handle))
-        if venv.obs_mode == "vector":
-            self.vector = venv._vobs.index_select(0, self.envs_t.long())
-        if venv.terminal_frames is not None:
-            self.terminal_frames = venv.terminal_frames.index_select(0, self.envs_t.long())
-
-
-def snapshot(venv, envs):
-    """venv.snapshot(envs)"""
-    return EnvSnapshot(venv, envs)
+        self.vector, self.terminal_frames = (None if t is None else t.index_select(0, self.envs_t.long())
+                                             for t in (venv.observer.rows, venv.terminal_frames))
 
 
 def restore(venv, snap, envs=None):
@@ -126,36 +104,26 @@ def restore(venv, snap, envs=None):
         if n not in _abi.SNAPSHOT_INVALIDATED and (arr is None) != (dst.arrays[n] is None):
             raise ValueError(f"the snapshot {'lacks' if arr is None else 'carries'} the state array {n!r} and this env does not: it was "
                              "taken from an env built with other options")
-    if (snap.vector is None) != (venv.obs_mode != "vector") or (snap.terminal_frames is None) != (venv.terminal_frames is None):
+    if (snap.vector is None) != (venv.observer.rows is None) or (snap.terminal_frames is None) != (venv.terminal_frames is None):
         raise ValueError("the snapshot was taken from an env with another obs_mode or terminal_obs setting")
-    layers, obs, ns, plane, phase = _env_frames(venv)
+    layers, obs, ns, plane, phase = venv.observer.frames()
     frames = None
     if snap.obs is not None:
-        if obs is None and venv.obs_mode == "birdview":
+        if obs is None and venv.observer.plane:
             venv.get_obs()                                       # the env has not been observed yet: its buffers come into being
-            layers, obs, ns, plane, phase = _env_frames(venv)
+            layers, obs, ns, plane, phase = venv.observer.frames()
         if obs is None or (ns, plane) != (snap.n_stack, snap.plane) or (layers is None) != (snap.layers is None):
             raise ValueError("the snapshot's frames (frame_stack, resolution) do not fit this env's")
         frames = ops.snapshot_frames(snap.layers, layers, snap.obs, obs, ns, plane, 0, phase)
     elif obs is not None:
         raise ValueError("the snapshot was taken before the env's first observation and holds no frames, this env has been observed: "
-                         "its frame buffers ('_obs' / the frame stack) would keep the overwritten envs' frames")
+                         "its frame buffers (the observer's frame / frame stack) would keep the overwritten envs' frames")
     rows_t = snap.envs_t if envs is None else torch.tensor(rows, dtype=torch.int32, device=venv.torch_device)
     ops.state_copy(snap, dst, snap._own, rows_t, frames=frames, outputs=True, check=False, handles=(snap._handle, venv._h))
-    if snap.vector is not None:
-        venv._vobs.index_copy_(0, rows_t.long(), snap.vector)
-    if snap.terminal_frames is not None:
-        venv.terminal_frames.index_copy_(0, rows_t.long(), snap.terminal_frames)
-    return _current_obs(venv)
-
-
-def _current_obs(venv):
-    """the observation buffer the env's last step / reset returned (None before the first one)"""
-    if venv.obs_mode == "vector":
-        return venv._vobs
-    if venv.obs_mode == "state":
-        return venv.state["obs"]
-    return venv._obs
+    for live, saved in ((venv.observer.rows, snap.vector), (venv.terminal_frames, snap.terminal_frames)):
+        if saved is not None:
+            live.index_copy_(0, rows_t.long(), saved)
+    return venv.observer.current()
 
 
 def fork(venv, src_env, dst_envs):
@@ -168,14 +136,13 @@ def fork(venv, src_env, dst_envs):
         raise ValueError(f"dst_envs holds src_env ({s[0]}): a fork writes other envs")
     dev = venv.torch_device
     se, de = torch.full((len(d),), s[0], dtype=torch.int32, device=dev), torch.tensor(d, dtype=torch.int32, device=dev)
-    layers, obs, ns, plane, phase = _env_frames(venv)
+    layers, obs, ns, plane, phase = venv.observer.frames()
     frames = ops.snapshot_frames(layers, layers, obs, obs, ns, plane, phase, phase) if obs is not None else None
     ops.state_copy(venv.state, venv.state, se, de, frames=frames, outputs=True, check=False, handles=(venv._h, venv._h))
-    if venv.obs_mode == "vector":
-        venv._vobs[de.long()] = venv._vobs[s[0]]
-    if venv.terminal_frames is not None:
-        venv.terminal_frames[de.long()] = venv.terminal_frames[s[0]]
-    return _current_obs(venv)
+    for live in (venv.observer.rows, venv.terminal_frames):
+        if live is not None:
+            live[de.long()] = live[s[0]]
+    return venv.observer.current()
 
 
 class EpisodeRecorder:
@@ -198,7 +165,7 @@ class EpisodeRecorder:
         if self.video_length < 1:
             raise ValueError("video_length must be >= 1")
         n, dev = len(self.envs), venv.torch_device
-        self.trace = _like_state(venv.state, n * self.video_length, dev)
+        self.trace = EnvState(n * self.video_length, venv.state.A, device=dev, **_like(venv.state))
         self._handle = _handle_for(venv, self.trace)
         self._src = torch.tensor(self.envs, dtype=torch.int32, device=dev)
         self._slots = torch.arange(n * self.video_length, dtype=torch.int32, device=dev).reshape(self.video_length, n)
