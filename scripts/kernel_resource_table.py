@@ -32,7 +32,7 @@ for ln in text.splitlines():
 assert rows, "no kernel-resource-usage remarks in the compiler's output"
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout.strip().split("\n")
 print(f"# {len(rows)} kernels; hipcc flags: {' '.join(b.CFLAGS)}")
-print(f"{'VGPRs':>5} {'spill':>5} {'SGPRsp':>6} {'scratch':>7} {'occ':>3} {'LDS':>6}  kernel")
+print(f"{'VGPRs':>5} {'SGPRs':>5} {'spill':>5} {'SGPRsp':>6} {'scratch':>7} {'occ':>3} {'LDS':>6}  kernel")
 for r, n in sorted(zip(rows, names), key=lambda t: t[1]):
     n = re.sub(r"\(tde_config.*", "", n).replace("void tde::", "")
-    print(f"{r.get('VGPRs', '?'):>5} {r.get('VGPRs Spill', '?'):>5} {r.get('SGPRs Spill', '?'):>6} {r.get('ScratchSize', '?'):>7} {r.get('Occupancy', '?'):>3} {r.get('LDS Size', '?'):>6}  {n}")
+    print(f"{r.get('VGPRs', '?'):>5} {r.get('TotalSGPRs', '?'):>5} {r.get('VGPRs Spill', '?'):>5} {r.get('SGPRs Spill', '?'):>6} {r.get('ScratchSize', '?'):>7} {r.get('Occupancy', '?'):>3} {r.get('LDS Size', '?'):>6}  {n}")

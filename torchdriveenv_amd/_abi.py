@@ -228,6 +228,7 @@ class TdeSnapshotFrames(C.Structure):
 
 
 TDE_SNAPSHOT_VERSION = 1         # include/tde_snapshot.h
+TDE_DRIVEN_VERSION = 1           # include/tde_driven.h
 SNAPSHOT_OUTPUTS, SNAPSHOT_CHECK, SNAPSHOT_MAX_STACK = 1 << 0, 1 << 1, 8
 # the group of every tde_state array under tde_state_copy (the header's list): copied always, copied with SNAPSHOT_OUTPUTS, invalidated
 SNAPSHOT_COPIED = (STATE_AGENT_F32 + STATE_AGENT_I32 + STATE_AGENT_U8 + ["slot_route"] + STATE_ENV_I32 + ["action", "obs", "ep_return"])

@@ -88,10 +88,18 @@ FAMILIES = [
         ("tde_state_copy", [sp, sp, i32, vp, vp, C.POINTER(_abi.TdeSnapshotFrames), u32, vp])]),
 ]
 
+# Families added since tests/test_abi_families_cpu.py pinned FAMILIES to its eight names: the same records under the same rules, walked
+# by load() and build.DEPS behind FAMILIES, each held to the rules by its own test file ("Adding a family").
+ADDED_FAMILIES = [
+    Family("driven", "tde_driven.h", "tde_step_driven.hip", "TDE_DRIVEN_VERSION", [
+        ("tde_driven_version", []),
+        ("tde_env_step_driven", [cfgp, wp, sp, vp, vp, vp])]),
+]
+
 
 def symbols(name):
-    """the symbols of family `name`, as FAMILIES lists them"""
-    return [s[0] for f in FAMILIES if f.name == name for s in f.symbols]
+    """the symbols of family `name`, as FAMILIES / ADDED_FAMILIES list them"""
+    return [s[0] for f in FAMILIES + ADDED_FAMILIES if f.name == name for s in f.symbols]
 
 
 SYMBOLS = symbols("core")        # every symbol include/tde_hip.h declares
@@ -116,7 +124,7 @@ def load():
     import torch  # noqa: F401  (side effect: maps torch/lib/libamdhip64.so)
 
     L = C.CDLL(LIB_PATH)
-    for fam in FAMILIES:
+    for fam in FAMILIES + ADDED_FAMILIES:
         missing = [s[0] for s in fam.symbols if not hasattr(L, s[0])]
         if missing:
             raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")

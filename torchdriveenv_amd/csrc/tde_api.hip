@@ -787,5 +787,8 @@ int tde_state_obs(const tde_world *world, const tde_state *st, float *out, void 
 
 }  // extern "C"
 
+// (for the units that define entry points of their own over (config, world, state): tde_step_driven.hip)
+int tde_host::check_env_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st) { return ::check_env_args(fn, cfg, w, st); }
+
 // host-side table build (no kernels): tde_grid_build / tde_grid_free
 #include "tde_gridbuild.h"

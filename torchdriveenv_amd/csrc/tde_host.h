@@ -100,6 +100,13 @@ int launch_step_solo_mag(const tde_config *cfg, const tde_world *world, const td
 // tde_step_routed.hip / tde_step_routed_mag.hip: env_step_routed_kernel<A >= 4, LIGHTS, OBS, BIG, WAVES, MAG = false / true> (state.slot_route != NULL)
 int launch_step_routed(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
 int launch_step_routed_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
+// tde_step_driven.hip / tde_step_driven_mag.hip: env_step_driven_kernel<A, LIGHTS, OBS, BIG, WAVES, MAG = false / true> (tde_env_step_driven)
+int launch_step_driven(const tde_config *cfg, const tde_world *world, const tde_state *st, const float *agent_action,
+                       const uint8_t *driven, void *stream);
+int launch_step_driven_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, const float *agent_action,
+                           const uint8_t *driven, void *stream);
+// tde_api.hip: what every entry point that takes (config, world, state) checks first; the message names `fn`
+int check_env_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st);
 // tde_rollout_trio.hip: env_rollout_trio_kernel<A in {8, 16, 32}, LIGHTS, BIG>; env_rollout_wide_kernel<LIGHTS> (128 slots)
 int launch_rollout_trio(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, void *stream);
 int launch_rollout_wide(const tde::StepArgs *args, const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, int waves, void *stream);

@@ -1209,13 +1209,17 @@ TDE_DEV void write_tile_slot(float4 &ta, float4 &tb, bool live, const Agent &ag,
 // Called by all BLOCK lanes of the workgroup, converged (contains barriers and wave ballots).
 // LIGHTS: compiled with the traffic-light code (stop-line violation of the ego, NPCs stopping at red lines); the
 // kernels without it serve configs that have no lights at zero cost.
+// DRIVEN (env_step_driven_kernel alone): a present slot a >= 1 with `drv` set takes (drv_acc, drv_steer) from outside as slot 0 takes
+// the ego action - at every k, with or without TDE_F_NPC - and is not pulled to its replay record; its controller still runs (every
+// lane takes part in the sweeps) and its route bookkeeping stays an NPC's, so that the controller can have the slot back at any step.
 #ifndef TDE_SOLO_MAG_LEAN
 #define TDE_SOLO_MAG_LEAN 1         // the one-role kernel's magnitudes section with the low-register scan too (A/B)
 #endif
-template <int A, int BLOCK, bool LIGHTS, bool BIG = false, bool MAG = false>
+template <int A, int BLOCK, bool LIGHTS, bool BIG = false, bool MAG = false, bool DRIVEN = false>
 TDE_DEV StepOut step_lane(const tde_config &cfg, const tde_world &w, const Cold &cold, const tde_state &st,
                           Tiles<BLOCK> &t, int e, int a, bool valid, Agent &ag, EnvRegs &er, Ctx &cx, float &c0,
-                          float &s0, float act_acc, float act_steer, float *mag_out = nullptr)
+                          float &s0, float act_acc, float act_steer, float *mag_out = nullptr, bool drv = false,
+                          float drv_acc = 0.0f, float drv_steer = 0.0f)
 {
     using mask_t = typename MaskOf<A>::type;
     const uint32_t F = cfg.flags;
@@ -1230,7 +1234,8 @@ TDE_DEV StepOut step_lane(const tde_config &cfg, const tde_world &w, const Cold 
     out.k = k;
 
     // replayed agents take their recorded state at time k (:275-283); issue the read ahead of the sweeps
-    const bool replayed = (F & TDE_F_REPLAY) && a > 0 && live && k < cx.replay_len;
+    bool replayed = (F & TDE_F_REPLAY) && a > 0 && live && k < cx.replay_len;
+    if constexpr (DRIVEN) replayed = replayed && !drv;
     float4 rep = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (replayed) rep = reinterpret_cast<const float4 *>(w.replay_states)[(int64_t)ag.replay * w.RT + k];
 
@@ -1247,6 +1252,9 @@ TDE_DEV StepOut step_lane(const tde_config &cfg, const tde_world &w, const Cold 
         else npc_action<A>(cfg, &t.a[base], &t.b[base], a, ag, c0, s0, has_target, cx.tgx, cx.tgy, cx.g_far, red_gap, na, nb);
         // (first step of an episode: the NPCs coast unless TDE_F_NPC_FIRST_STEP asks for the reference's behaviour, tde_abi.h)
         if (npc && (k > 1 || (F & TDE_F_NPC_FIRST_STEP))) { acc = na; beta = nb; }
+    }
+    if constexpr (DRIVEN) {
+        if (drv) { acc = drv_acc; beta = drv_steer; }       // (the controller's result is dropped: raw units, as the ego's)
     }
 
     if (live) {
@@ -1363,7 +1371,9 @@ __global__ __launch_bounds__(kBlock, A > kWave ? WAVES : 1) void env_step_kernel
                                                           uint8_t *done_k)
 {
 #define TDE_STEP_ROUTED 0
+#define TDE_STEP_DRIVEN 0
 #include "tde_step_body.inc"
+#undef TDE_STEP_DRIVEN
 #undef TDE_STEP_ROUTED
 }
 
@@ -1376,7 +1386,26 @@ __global__ __launch_bounds__(kBlock, A > kWave ? WAVES : 1) void env_step_routed
                                                           uint8_t *done_k)
 {
 #define TDE_STEP_ROUTED 1
+#define TDE_STEP_DRIVEN 0
 #include "tde_step_body.inc"
+#undef TDE_STEP_DRIVEN
+#undef TDE_STEP_ROUTED
+}
+
+// The one-role step in which chosen NPC slots take their actions from outside (tde_env_step_driven, include/tde_driven.h): lane (e, a)
+// with a >= 1, a present slot and driven[e * A + a] != 0 integrates agent_action[e * A + a] instead of the controller's result or its
+// replay record.  `driven` may be NULL (nobody is driven).  A family of its own, as the routed one: the instantiations of
+// env_step_kernel are the same code objects with or without it.
+template <int A, bool LIGHTS, bool OBS, bool BIG = false, int WAVES = TDE_WIDE_WAVES, bool MAG = false>
+__global__ __launch_bounds__(kBlock, A > kWave ? WAVES : 1) void env_step_driven_kernel(tde_config cfg, tde_world w, tde_state st,
+                                                          const float *__restrict__ action, float *reward_k,
+                                                          uint8_t *done_k, const float *__restrict__ agent_action,
+                                                          const uint8_t *__restrict__ driven)
+{
+#define TDE_STEP_ROUTED 0
+#define TDE_STEP_DRIVEN 1
+#include "tde_step_body.inc"
+#undef TDE_STEP_DRIVEN
 #undef TDE_STEP_ROUTED
 }
 

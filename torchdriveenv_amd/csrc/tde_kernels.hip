@@ -21,6 +21,8 @@
 #include "tde_step_solo_mag.hip"
 #include "tde_step_routed.hip"
 #include "tde_step_routed_mag.hip"
+#include "tde_step_driven.hip"
+#include "tde_step_driven_mag.hip"
 #include "tde_rollout_trio.hip"
 #include "tde_rollout_duo.hip"
 #include "tde_rollout_solo.hip"

@@ -1,6 +1,7 @@
-// tde_step_body.inc - the body of the one-role step kernels, included by tde_kernels.h inside env_step_kernel (TDE_STEP_ROUTED 0) and
-// env_step_routed_kernel (TDE_STEP_ROUTED 1): ONE text, so that the routed family is the one-role step plus one load, and the existing
-// family compiles from exactly the tokens it always had.
+// tde_step_body.inc - the body of the one-role step kernels, included by tde_kernels.h inside env_step_kernel (TDE_STEP_ROUTED 0,
+// TDE_STEP_DRIVEN 0), env_step_routed_kernel (TDE_STEP_ROUTED 1) and env_step_driven_kernel (TDE_STEP_DRIVEN 1): ONE text, so that the
+// routed family is the one-role step plus one load, the driven family the one-role step plus a mask byte and an action per driven slot,
+// and the existing family compiles from exactly the tokens it always had.
     __shared__ Tiles<kBlock> t;
     __shared__ Cold cold;
     if (threadIdx.x == 0) fill_cold(cold, cfg, w);
@@ -16,6 +17,14 @@
     const uint32_t slot_word = st.slot_route[gs];        // (with the state's own arrays: ahead of the chain scenario -> spawn record that load_ctx walks)
 #endif
     if (!valid) ag.present = false;
+#if TDE_STEP_DRIVEN
+    // the slot's mask byte and, behind it, its action: beside the state's own arrays, ahead of the table chain.  Row 0 (the ego's action
+    // is state.action) and the entries of absent or undriven slots are never read.
+    bool drv = false;
+    float2 dact = make_float2(0.0f, 0.0f);
+    if (driven && a > 0 && ag.present) drv = driven[gs] != 0;
+    if (drv) dact = reinterpret_cast<const float2 *>(agent_action)[gs];
+#endif
     EnvRegs er{st.scn[es], st.steps[es], st.target_idx[es], st.reached[es], st.episode[es]};
     Ctx cx;
     // (the one-role kernel does not use the lookup caches even when they are there: read in its prologue and kept like the
@@ -33,7 +42,11 @@
     write_tile_slot(t.a[threadIdx.x], t.b[threadIdx.x], valid && ag.present, ag, c0, s0, cfg.npc_lane_half);
     tile_sync<A>();
     const int map0 = cx.map_id;                     // (MAG: the map of the episode that is being stepped; a re-spawn replaces cx)
+#if TDE_STEP_DRIVEN
+    StepOut o = step_lane<A, kBlock, LIGHTS, BIG, MAG, true>(cfg, w, cold, st, t, es, a, valid, ag, er, cx, c0, s0, act.x, act.y, st.magnitudes, drv, dact.x, dact.y);
+#else
     StepOut o = step_lane<A, kBlock, LIGHTS, BIG, MAG>(cfg, w, cold, st, t, es, a, valid, ag, er, cx, c0, s0, act.x, act.y, st.magnitudes);
+#endif
     const unsigned long long hit_m = MAG ? __ballot(o.collided != 0) : 0ull, off_m = MAG ? __ballot(o.offroad != 0) : 0ull;
     if (valid) {
         store_agent_dynamic(st, g, ag);
@@ -50,6 +63,11 @@
             st.truncated[e] = o.truncated;
             if (st.tl_violation) st.tl_violation[e] = o.tl;
             if (o.respawned) { st.scn[e] = er.scn; st.episode[e] = er.episode; }
+#if TDE_STEP_DRIVEN
+            // the stored NPC actions were computed for a step the controller takes: the env's key goes invalid, as tde_near_field_spawn
+            // leaves it (slot_cache / env_cache are keyed by what they cache - scenario, episode, waypoint indices - and see the new state)
+            if (st.act_cache) *reinterpret_cast<int2 *>(st.act_cache + (int64_t)e * (A + 1) + A) = make_int2(-1, 0);
+#endif
             if (reward_k) reward_k[e] = o.reward;
             if (done_k)
                 done_k[e] = (uint8_t)(o.terminated | (o.truncated << 1) | (o.offroad << 2) | (o.collided << 3) | (o.tl << 4));

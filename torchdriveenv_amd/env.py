@@ -841,18 +841,42 @@ class BatchedWaypointEnv:
         finally:
             self.tde_cfg.flags = full
 
-    def step(self, actions):
+    def step(self, actions, agent_actions=None, driven=None):
+        """driven (bool / uint8 [B, A] on the env's device) with agent_actions (float32 [B, A, 2]): the present slots a >= 1 whose mask
+        entry is set take agent_actions[e, a] = (acceleration, steering) in this step as slot 0 takes actions[e] - raw units, at every
+        step count, instead of the controller's result or the slot's replay record (tde_env_step_driven, include/tde_driven.h).  Row 0
+        and the rows of absent or undriven slots are never read.  The mask is by slot index: an env re-spawned in the step keeps it for
+        its new agents.  Only the launch differs: observations, terminal_obs, info and episode statistics are the plain step's.
+        driven=None (default): the plain step."""
         # (the host side of a step is what a closed loop of small kernels waits for: no tensor op that is not needed)
         a = actions
         if not (torch.is_tensor(a) and a.dtype is torch.float32 and a.device == self.torch_device and a.dim() == 2
                 and a.shape[0] == self.num_envs and a.shape[1] == 2 and a.is_contiguous()):
             a = torch.as_tensor(actions, dtype=torch.float32, device=self.torch_device).reshape(self.num_envs, 2).contiguous()
+        launch = self._h.step if driven is None else self._driven_launch(agent_actions, driven)
         if self.terminal_obs and self.auto_reset:                    # (the VecEnv adapter clears the flag and re-spawns the envs itself)
-            return self._step_terminal(a)
-        self._h.step(a, int(self.tde_cfg.flags))
+            return self._step_terminal(a, launch)
+        launch(a, int(self.tde_cfg.flags))
         if self.dnf is not None and self.auto_reset:
             self._spawn_near_field(done=True)                        # the envs the step re-spawned, before they are observed
         return self._result(self._after_step())
+
+    def _driven_launch(self, agent_actions, driven):
+        """the launch of a step with outside actions for the slots in `driven`, in the shape of the handle's step(action, flags): the two
+        tensors are checked here, before anything is queued; the ego actions go to state["action"], which the C ABI reads; the call
+        goes through ctypes under either binding (ops.env_step_driven)"""
+        if self._nf_routed:
+            raise ValueError("step(driven=) with routed near-field traffic (NearField(routes=True)): tde_env_step_driven refuses a state "
+                             "with per-slot routes")
+        ops.check_driven(agent_actions, driven, self.num_envs, self.A, self.torch_device)
+
+        def launch(a, flags):
+            self.tde_cfg.flags = flags
+            act = self.state["action"]
+            if a is not act:
+                act.copy_(a)
+            ops.env_step_driven(self.tde_cfg, self.dworld, self.state, agent_actions, driven)
+        return launch
 
     def _result(self, obs):
         """what a step returns with the observation `obs`: the state's terminated / truncated bytes seen as bool (no copy; the views are
@@ -863,13 +887,13 @@ class BatchedWaypointEnv:
             v = self._tt_views = (st["terminated"], st["terminated"].view(torch.bool), st["truncated"].view(torch.bool))
         return obs, st["reward"], v[1], v[2], _LazyInfo(st, self.num_envs, self.A, magnitudes=self._mag)
 
-    def _step_terminal(self, a):
+    def _step_terminal(self, a, launch):
         """step() of a terminal_obs env: the step without the in-kernel re-spawn (the kernel form WaypointVecEnv.step_wait uses) ->
         the observation, which for a finished env is its terminal one -> tde_terminal_stash of the finished envs' newest frame into
         terminal_frames -> reset(mask=done): the masked re-spawn and re-render.  Same results as step() without the option."""
         st = self.state
         with self._without_autoreset():
-            self._h.step(a, int(self.tde_cfg.flags))
+            launch(a, int(self.tde_cfg.flags))
             self._after_step()
         ops.terminal_stash(self.torch_device, st["done_bits"], *self.observer.newest_frame(), self.terminal_frames)
         return self._result(self.reset(mask=torch.bitwise_or(st["terminated"], st["truncated"], out=self._term_mask)))
@@ -1152,6 +1176,39 @@ class BatchedWaypointEnv:
         render_mode="video" (BirdviewRecordingWrapper, ref gym_env.py:295-297), which this batched API does not take as a mode
         (ops.render_scene)."""
         return ops.render_scene(self.tde_cfg, self.dworld, self.state, envs, H, W, fov, camera, out, flags=self._rflags)
+
+    def render_agents(self, envs, slots, H=64, W=64, fov=None):
+        """uint8 [n, 3, H, W] on the device: the birdview centred on slot slots[i] of env envs[i], its heading up - the observation a
+        policy that drives that slot (step(driven=)) can use.  The tde_scene_view rows are gathered on the device from the state and
+        handed to tde_render_scene with this env's render flags; fov defaults to the ego observation's.  Slot 0 stays painted as the
+        ego whichever slot the view is centred on; an absent slot gives the view from the pose its row holds.  envs and slots are
+        integer sequences or tensors of one length, envs in [0, B), slots in [0, A) (checked on the host)."""
+        dev = self.torch_device
+        envs = torch.as_tensor(envs, dtype=torch.int64).reshape(-1)
+        slots = torch.as_tensor(slots, dtype=torch.int64).reshape(-1)
+        if envs.numel() != slots.numel():
+            raise ValueError(f"envs and slots must have one length, got {envs.numel()} and {slots.numel()}")
+        if envs.numel() and not bool(((envs >= 0) & (envs < self.num_envs)).all()):
+            raise ValueError(f"envs must be in [0, {self.num_envs})")
+        if slots.numel() and not bool(((slots >= 0) & (slots < self.A)).all()):
+            raise ValueError(f"slots must be in [0, {self.A})")
+        H, W = int(H), int(W)
+        if not (1 <= H <= 4096 and 1 <= W <= 4096):
+            raise ValueError("H and W must be in [1, 4096]")
+        fov = self._fov if fov is None else float(fov)
+        if not (np.isfinite(fov) and fov > 0):
+            raise ValueError("fov must be finite and positive")
+        envs, slots = envs.to(dev), slots.to(dev)
+        n = envs.numel()
+        out = torch.empty((n, 3, H, W), dtype=torch.uint8, device=dev)
+        if n == 0:
+            return out
+        g = envs * self.A + slots
+        views = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        views[:, 0] = envs
+        pose = views[:, 1:].view(torch.float32)                      # (the state's own bits)
+        pose[:, 0], pose[:, 1], pose[:, 2] = self.state["x"][g], self.state["y"][g], self.state["psi"][g]
+        return ops.render_scene_views(self.tde_cfg, self.dworld, self.state, views, H, W, fov, out, flags=self._rflags)
 
     def render(self):
         """(B, H, W, 3) uint8 of the current ego views (ref gym_env.py:152-155)"""

@@ -257,6 +257,37 @@ def env_step(cfg, dworld, state, action=None):
                               _lib.current_stream(state.device)), "tde_env_step")
 
 
+def check_driven(agent_action, driven, B, A, dev):
+    """the two tensors of env_step_driven -> their device addresses (None, None when nobody is driven): agent_action float32 [B, A, 2],
+    driven bool or uint8 [B, A], both contiguous on `dev`"""
+    if driven is None:
+        return _chk(agent_action, torch.float32, B * A * 2, "agent_action", torch.device(dev), optional=True), None
+    if torch.is_tensor(driven) and driven.dtype == torch.bool:
+        driven = driven.view(torch.uint8)               # (the same bytes: True is 1)
+    pd = _chk(driven, torch.uint8, B * A, "driven", torch.device(dev))
+    if tuple(driven.shape) != (B, A):
+        raise ValueError(f"driven must have shape [{B}, {A}], got {list(driven.shape)}")
+    if agent_action is None:
+        raise ValueError("agent_action is required when driven is given")
+    pa = _chk(agent_action, torch.float32, B * A * 2, "agent_action", torch.device(dev))
+    if tuple(agent_action.shape) != (B, A, 2):
+        raise ValueError(f"agent_action must have shape [{B}, {A}, 2], got {list(agent_action.shape)}")
+    return pa, pd
+
+
+def env_step_driven(cfg, dworld, state, agent_action=None, driven=None, stream=None):
+    """tde_env_step_driven (include/tde_driven.h): one timestep of every env in which the present slots a >= 1 with driven[e, a] set take
+    agent_action[e, a] = (acceleration, steering) as slot 0 takes state["action"]; everything else is env_step's.  agent_action float32
+    [B, A, 2], driven bool / uint8 [B, A], on the state's device; driven=None: nobody is driven.  `stream`: a torch.cuda.Stream
+    (default: the current one).  Through ctypes under either binding."""
+    L = _lib.load()
+    dev = state.device
+    pa, pd = check_driven(agent_action, driven, state.B, state.A, dev)
+    s = _lib.current_stream(dev) if stream is None else C.c_void_p(stream.cuda_stream)
+    _lib.check(_call(dev, L.tde_env_step_driven, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), pa, pd, s),
+               "tde_env_step_driven")
+
+
 def env_rollout(cfg, dworld, state, actions, reward=None, done=None):
     """actions float32 [K,B,2] on device -> (reward [K,B] f32, done [K,B] u8)"""
     _no_near_field(dworld, "env_rollout")
