@@ -168,9 +168,10 @@ typedef struct tde_scenario {
  * an episode of scenario s apart from the ego - min(leader gap over the scenario's other NPCs, gap to a red stop line) at the spawn
  * state, which depends on the scenario's tables and the controller's constants only, not on the episode.  `key` = the launch's
  * controller hash | 1 (what tde_act_cache's key carries: config.flags & (NPC | REPLAY | TRAFFIC_LIGHTS), the npc_* constants, the
- * identity of the world's tables); an entry with another key (zero-initialised memory) is recomputed and rewritten by the lane
- * that meets it, as ONE 8-byte store.  With a valid entry the first step of a re-spawned env costs the role-split kernels one
- * exact test against the ego's row instead of the controller's sweep over the env's slots; same minimum, same bits. */
+ * identity of the world's tables); tde_first_gaps writes the entries, each as ONE 8-byte store, and no step or rollout kernel
+ * writes them: a lane that meets an entry with another key (zero-initialised memory) leaves it and runs the whole controller.
+ * With a valid entry the first step of a re-spawned env costs the role-split kernels (the two-role one-step kernel for 128 slots
+ * among them) one exact test against the ego's row instead of the controller's sweep over the env's slots; same minimum, same bits. */
 typedef struct tde_first_gap {
     float gap;
     uint32_t key;
@@ -229,7 +230,7 @@ typedef struct tde_world {
                                    episode that starts at fraction f of the segment reads entry floor(f * NH).  Unused (may be a
                                    one-element dummy) when NH == 0: tde_scenario.start_heading then */
     tde_first_gap *first_gap;   /* (ABI 11) [S][A] the first-step gap cache (see tde_first_gap): the ONE table of the world the
-                                   kernels WRITE - scratch that belongs to the world's device copy, zero-initialised by its owner;
+                                   library WRITES (tde_first_gaps alone) - scratch that belongs to the world's device copy, zero-initialised by its owner;
                                    NULL: no cache (every first step runs the controller's sweep).  The CPU checker ignores it */
     int32_t n_maps, n_scn, NW, A;
     int32_t n_routes, RW, n_replay, RT;

@@ -192,7 +192,8 @@ TDE_API int tde_env_post_step(const tde_config *config, const tde_world *world, 
  * without it (or with entries of another configuration) they run the whole controller: same results either way.
  * tde_env_step / tde_env_rollout call this themselves, on their stream, the first time they meet a (world, configuration) pair (a
  * small per-process memo of the pairs already served): a caller only needs it to choose WHEN the launch happens (e.g. outside a
- * stream capture).  One launch of n_scn * A lanes; up to 64 agent slots per env (the 128-slot kernels do not use the cache: no-op). */
+ * stream capture).  One launch of n_scn * A lanes; up to 128 agent slots per env (at 128 slots the two-role one-step kernel reads
+ * the cache; the 128-slot rollout kernel does not).  This launch alone writes the cache: no step or rollout kernel does. */
 TDE_API int tde_first_gaps(const tde_config *config, const tde_world *world, void *stream);
 
 /* Near-field traffic at reset (the stand-in for iai_conditional_initialize, gym_env.py:232-238, iai.py:6-60): fills the free slots of

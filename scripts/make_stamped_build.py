@@ -91,8 +91,8 @@ def patch_duo(s):
     k = sub(k, "            act = act_next;\n        }\n", "            act = act_next;\n        }\n        if (lane == 0) for (int i = 0; i < 12; ++i) atomicAdd(&g_stamps[i], stp.acc[i]);\n")
     k = sub(k, "        lds_barrier();\n        for (int i = 0; i < ro.K; ++i) {\n            const int p = i & 1;\n            lds_barrier();                                   // A\n            lds_barrier();                                   // B: rows of step i are in buffer p\n",
             "        lds_barrier();\n        Stamps stp; stp.start();\n        for (int i = 0; i < ro.K; ++i) {\n            const int p = i & 1;\n            lds_barrier();                                   // A\n            stp.mark(0);\n            lds_barrier();                                   // B: rows of step i are in buffer p\n            stp.mark(1);\n")
-    k = sub(k, "            bool off = false;\n            if (F & TDE_F_OFFROAD) off = offroad_resolve<false, BIG || TDE_ROLLOUT_CLS2>(w, corners, thr2, cx.m.rec_base);\n",
-            "            stp.mark(2);\n            bool off = false;\n            if (F & TDE_F_OFFROAD) off = offroad_resolve<false, BIG || TDE_ROLLOUT_CLS2>(w, corners, thr2, cx.m.rec_base);\n            stp.mark(3);\n")
+    k = sub(k, "            bool off = false;\n            if (F & TDE_F_OFFROAD) off = offroad_resolve<false, BIG>(w, corners, thr2, cx.m.rec_base);\n",
+            "            stp.mark(2);\n            bool off = false;\n            if (F & TDE_F_OFFROAD) off = offroad_resolve<false, BIG>(w, corners, thr2, cx.m.rec_base);\n            stp.mark(3);\n")
     k = sub(k, "            if (lane == 0) sh.done = any;\n", "            stp.mark(4);\n            if (lane == 0) sh.done = any;\n")
     k = sub(k, "                o.respawned = true;\n            }\n        }\n",
             "                o.respawned = true;\n            }\n            stp.mark(5);\n        }\n        if (lane == 0) for (int i = 0; i < 12; ++i) atomicAdd(&g_stamps[12 + i], stp.acc[i]);\n")
@@ -167,15 +167,15 @@ def patch_step3(s):
     k = sub(k, "        if (respawned || switched || rebuilt || need_tg2) store_slot_cache(st, g, ag, er, cx, cfg.flags, respawned);\n",
             "        if (respawned || switched || rebuilt || need_tg2) store_slot_cache(st, g, ag, er, cx, cfg.flags, respawned);\n        tde_mark(&stl, 5);\n        tde_flush(0, 7);\n        if (lane == 0) { g_wg[blockIdx.x & 4095][23] = __builtin_amdgcn_s_memrealtime(); g_wg[blockIdx.x & 4095][7] = dn ? 1ull : 0ull; }\n")
     # judge C
-    k = sub(k, "        lds_barrier();                                       // B\n        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_C2);",
-            "        tde_mark(&stl, 8);\n        lds_barrier();                                       // B\n        tde_mark(&stl, 9);\n        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_C2);")
+    k = sub(k, "        lds_barrier();                                       // B\n        __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_C2);",
+            "        tde_mark(&stl, 8);\n        lds_barrier();                                       // B\n        tde_mark(&stl, 9);\n        __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_C2);")
     k = sub(k, "        RewardOut rw{};\n        const int ti0 = er.target_idx;\n        bool reach = false;\n",
             "        tde_mark(&stl, 12);\n        RewardOut rw{};\n        const int ti0 = er.target_idx;\n        bool reach = false;\n")
     k = sub(k, "        lds_barrier();                                       // A: off / tl masks and the ego's psi term are in\n",
             "        tde_mark(&stl, 10);\n        lds_barrier();                                       // A: off / tl masks and the ego's psi term are in\n        tde_mark(&stl, 11);\n")
     # judge O
-    k = sub(k, "        }\n        lds_barrier();                                       // B\n        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_O2);\n",
-            "        }\n        tde_mark(&stl, 16);\n        lds_barrier();                                       // B\n        tde_mark(&stl, 17);\n        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_O2);\n")
+    k = sub(k, "        }\n        lds_barrier();                                       // B\n        __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_O2);\n",
+            "        }\n        tde_mark(&stl, 16);\n        lds_barrier();                                       // B\n        tde_mark(&stl, 17);\n        __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_O2);\n")
     k = sub(k, "        if (lane == 0) { sh.off_mask = om; sh.tl_mask = tm; }\n",
             "        if (lane == 0) { sh.off_mask = om; sh.tl_mask = tm; }\n        tde_mark(&stl, 18);\n")
     # (round 5: the magnitudes section - slot 21 = from barrier A to its end; slot 20 now includes the pre-A touches)
@@ -211,8 +211,7 @@ def patch_wide(s):
     k = sub(k, "        if (st.slot_cache) { sc0 = reinterpret_cast<const int4 *>(st.slot_cache + g)[0]; sc1 = reinterpret_cast<const int4 *>(st.slot_cache + g)[1]; }\n",
             "        if (st.slot_cache) { sc0 = reinterpret_cast<const int4 *>(st.slot_cache + g)[0]; sc1 = reinterpret_cast<const int4 *>(st.slot_cache + g)[1]; }\n        tde_mark(sp, 17);\n")
     # drive
-    k = sub(k, "        TDE_WIDE_COLD_BARRIER();                             // cold is published\n        Ctx cx;\n        bool rebuilt;\n",
-            "        TDE_WIDE_COLD_BARRIER();                             // cold is published\n        tde_mark(sp, 0);\n        Ctx cx;\n        bool rebuilt;\n")
+    k = sub(k, "        Ctx cx;\n        bool rebuilt;\n", "        tde_mark(sp, 0);\n        Ctx cx;\n        bool rebuilt;\n")
     k = sub(k, "        lds_barrier();                                       // E: does a drive wavefront lack stored actions?\n",
             "        tde_mark(sp, 1);\n        lds_barrier();                                       // E: does a drive wavefront lack stored actions?\n        tde_mark(sp, 2);\n")
     k = sub(k, "        lds_barrier();                                       // B: rows of this step are in buffer 0\n        __builtin_amdgcn_s_setprio(NW == 8 ? 2 : TDE_WIDE_PRIO_D2);",

@@ -290,7 +290,7 @@ static int env_step_launch(const tde_config *cfg, const tde_world *world, const 
     if (st->B <= 0) return 0;
     if (!st->action) return bad("tde_env_step: state.action is NULL");
     if (st->slot_route && st->A < 4) return bad("tde_env_step: state.slot_route needs at least 4 agent slots per env");
-    if ((cfg->flags & TDE_F_OFFROAD) && TDE_STEP_CLS2 && !world->cell_cls2) return bad("tde_env_step: world.cell_cls2 is NULL (ABI 7 class map)");
+    if ((cfg->flags & TDE_F_OFFROAD) && !world->cell_cls2) return bad("tde_env_step: world.cell_cls2 is NULL (ABI 7 class map)");
     const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
     // With the lookup caches present (and a group shape the three-role kernels are built for) the step runs as three
     // wavefronts per 64 agent slots; tde_kernel_override forces one form (A/B runs).
@@ -326,7 +326,7 @@ static int env_step_launch(const tde_config *cfg, const tde_world *world, const 
             if (rc) return rc;
             // eight wavefronts per env while the batch leaves the CUs issue slots to spare (half a residency round), four above;
             // tde_kernel_override(0, 2) = the four-wavefront form at any batch size
-            const int waves = (force != 2 && TDE_WIDE_STEP_WAVES8 && st->B <= 2 * cu_count()) ? 8 : 4;
+            const int waves = (force != 2 && st->B <= 2 * cu_count()) ? 8 : 4;
             return tde_host::launch_step_wide(args, cfg, st, waves, stream);
         }
     }
@@ -392,16 +392,11 @@ int tde_env_rollout(const tde_config *cfg, const tde_world *world, const tde_sta
         // per env) 6.2 / 8.9 / 18.0 / 34.7, one role 10.6 / 11.4 / 23.3 / 38.9 (profiles/r04_z_wide2_waves.txt; round 6: 7.3 at 1024 envs).
         // tde_kernel_override(1, 0) forces the one-role kernel.
         if (g_force_rollout == 1) return tde_host::launch_rollout_solo(cfg, world, st, &r128, stream);
-        const tde::StepArgs *args = nullptr;
-#if TDE_WIDE_ROLLOUT_BLOCK       // (A/B: the arguments from a block in device memory, as the one-step kernel's)
-        args = step_args(cfg, world, st, 0u, stream);
-        if (!args) return tde_host::launch_rollout_solo(cfg, world, st, &r128, stream);
-#endif
         // eight wavefronts per env while the batch leaves the CUs issue slots to spare (half a residency round), four above - us per
         // step, four / eight: 1 env 5.05 / 3.49, 64 envs 5.22 / 3.69, 256 envs 5.35 / 3.81, 512 envs 5.42 / 4.01, 256 envs with lights
         // 6.61 / 5.01 (profiles/r06_z_wide_128.txt); tde_kernel_override(2, 0) = the four-wavefront form at any batch size
-        const int waves = (g_force_rollout != 2 && TDE_WIDE_ROLLOUT_WAVES8 && st->B <= 2 * cu_count()) ? 8 : 4;
-        return tde_host::launch_rollout_wide(args, cfg, world, st, &r128, waves, stream);
+        const int waves = (g_force_rollout != 2 && st->B <= 2 * cu_count()) ? 8 : 4;
+        return tde_host::launch_rollout_wide(cfg, world, st, &r128, waves, stream);
     }
     // Which persistent kernel: one, two or three wavefronts per group of 64 agent slots (tde_kernel_override(1 | 2 | 3, 0)
     // forces one; a forced trio still needs 8, 16 or 32 agents per env).  Interleaved same-process A/B, 40 launches each, median

@@ -305,17 +305,10 @@ TDE_DEV uint32_t cell_class_lookup(const tde_world &w, const tde_map &m, float p
     return ((word >> ((ix & 15u) << 1)) & 3u) | (((uint32_t)m.cell_base + ((iy << m.row_shift) + ix)) << 2);
 }
 
-#ifndef TDE_STEP_CLS2
-#define TDE_STEP_CLS2 1
-#endif
-// the same choice for the judges of the two- and three-role rollout kernels (A/B on the town map, profiles/r04_*)
-#ifndef TDE_ROLLOUT_CLS2
-#define TDE_ROLLOUT_CLS2 0
-#endif
-
 // CLS2 (the one-step kernels, whose state is not register-resident and whose every launch therefore pays the HBM / fabric
 // traffic of its lookups): the corners' classes come from the class map and only a corner in a MIXED cell fetches its cell word
-// (offroad_resolve).  k.w* = class | cell index << 2 then.
+// (offroad_resolve).  k.w* = class | cell index << 2 then.  (The class map was tried in the rollout kernels' judges on small
+// grids too: slower, profiles/r03_g_ab_rollout_cls2.txt; they take it on a large grid only - BIG.)
 template <bool CLS2 = false>
 TDE_DEV void offroad_issue(const tde_world &w, const tde_map &m, bool live, float x, float y, float c, float s, float hl,
                            float hw, Corners &k)

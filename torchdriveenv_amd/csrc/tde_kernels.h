@@ -29,8 +29,8 @@
 // TDE_EXP_*: builds for TIMING experiments that skip part of the work and therefore compute WRONG results (what a section costs:
 // profiles/r05_magnitudes_floor.md, r04_k_ab_step_no_respawn.txt).  They only compile with -DTDE_EXPERIMENT_BUILD, which no product build
 // sets (build.py never passes it; scripts/build_variant.sh passes whatever it is given): a stray -DTDE_EXP_... in a product build is an
-// error, not a silently wrong library.  (Switches that keep the results - TDE_FIRST_GAP, TDE_COLLIDE_DPP, TDE_STEP_CLS2, the issue
-// priorities ... - are A/B switches and need no fence.)
+// error, not a silently wrong library.  (Switches that keep the results - TDE_SWEEP_BLOCK, TDE_RED_GAP_LINES, the issue
+// priorities ... - are tuning knobs and need no fence.)
 #if (defined(TDE_EXP_NO_COLL_MAG) || defined(TDE_EXP_NO_OFF_MAG) || defined(TDE_EXP_EXTRA_LOAD) || defined(TDE_EXP_NO_D_RESPAWN) || \
      defined(TDE_EXP_NO_C_RESPAWN) || (defined(TDE_EXP_MAG_FRAME) && TDE_EXP_MAG_FRAME != 0)) && !defined(TDE_EXPERIMENT_BUILD)
 #error "TDE_EXP_* switches build a library that computes WRONG results (timing experiments): add -DTDE_EXPERIMENT_BUILD to say you mean it"
@@ -146,13 +146,10 @@ TDE_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::
 // wavefronts of a 256-thread workgroup are independent chains, and a __syncthreads() (s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier)
 // made each of them wait for the slowest at every phase AND for its own grid-index loads that were meant to stay in flight
 // across the collision sweep.  128 slots per env: the env's two wavefronts meet at an LDS-only barrier.
-#ifndef TDE_TILE_SYNC_WG
-#define TDE_TILE_SYNC_WG 0          // 1: the old __syncthreads() (A/B)
-#endif
+// (The __syncthreads() was tried against this: slower, profiles/r04_z_ab_step_tile_sync.txt.)
 template <int A> TDE_DEV void tile_sync()
 {
-    if constexpr (TDE_TILE_SYNC_WG) __syncthreads();
-    else if constexpr (A > kWave) lds_barrier();
+    if constexpr (A > kWave) lds_barrier();
     else { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); }
 }
 
@@ -782,9 +779,8 @@ TDE_DEV void npc_action(const tde_config &cfg, const float4 *ra, const float4 *r
 // entries a re-spawned env's first action is min(G1, exact test against the ego's row) -> npc_act_of_gap: one trip of the exact loop
 // instead of the sweep over the env's rows and the stop-line loop (a minimum over the same values in another order: the same bits as
 // npc_action); with an entry missing (tde_first_gaps not called for this configuration) the kernels run the whole controller.
-#ifndef TDE_FIRST_GAP
-#define TDE_FIRST_GAP 1             // 0: the kernels ignore the first-step gap cache (A/B; same results)
-#endif
+// (Ignoring the cache - the whole controller on every first step - was tried: slower wherever the kernels read it,
+// profiles/r06_first_step_matrix.txt.)
 constexpr uint32_t kGapForm = 0x5bd1e995u;      // act-cache key domain of "first-step gaps forwarded by the re-spawning launch" (step kernel)
 TDE_DEV uint32_t first_gap_key(uint32_t act_hash) { return act_hash | 1u; }     // (never 0: zero-initialised entries are invalid)
 
@@ -797,7 +793,7 @@ TDE_DEV bool npc_first_step(const tde_config &cfg, uint2 ent, uint32_t key, cons
 {
     using mask_t = typename MaskOf<A>::type;
     const bool use = fresh_npc && has_target;                 // the lanes whose action depends on a gap
-    if (!TDE_FIRST_GAP || __ballot(use && ent.y != key)) return false;
+    if (__ballot(use && ent.y != key)) return false;
     const float g_ego = npc_gap_exact<A>(cfg, ra, rb, a, use ? bit_of_row<A>(0) : (mask_t)0, ag, cp, sp);
     float xa, xb;
     npc_act_of_gap(cfg, ag, cp, sp, has_target, tgx, tgy, fminf(__uint_as_float(ent.x), g_ego), 1e30f, xa, xb);
@@ -899,9 +895,6 @@ TDE_DEV bool collide_rows_wide(const float4 *ra, const float4 *rb, int a, bool l
 // finds the step's stamp in `flag[partner]` (LDS) once the other judge wavefront has published its own (TDE_WIDE_SYM_JOIN below).
 // The lane's rows start at a different address per lane but at compile-time offsets from it: `ra` has 192 rows, rows 128..191
 // mirror rows 0..63 (write_rows_wide).  64 x 7 VALU instead of 128 x 7 per judge wavefront and step, half the exact tests.
-#ifndef TDE_WIDE_SYM
-#define TDE_WIDE_SYM 1              // 0: every slot sweeps all 128 rows (A/B)
-#endif
 TDE_DEV bool collide_rows_wide_sym(const float4 *ra, const float4 *rb, int a, bool live, float x, float y, float c, float s, float hl,
                                    float hw, float ri, int *flag, int stamp)
 {
@@ -953,9 +946,6 @@ TDE_DEV bool collide_rows_wide_sym(const float4 *ra, const float4 *rb, int a, bo
 // instead of 16 x 7, and no LDS read (16 ds_read_b128 = 64 LDS-array cycles per wavefront and step).
 // Candidate mask: bit 15 - o for offsets o = 1..8, bit o - 9 for o = 9..15 (the order the verdicts become available).
 // The exact tests read the candidate's rows from LDS as before.  All 64 lanes must be active.
-#ifndef TDE_COLLIDE_DPP
-#define TDE_COLLIDE_DPP 1
-#endif
 template <int N> TDE_DEV float dpp_row_ror(float v)
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, true));
@@ -1063,9 +1053,6 @@ TDE_DEV uint32_t red_mask_cached(const tde_world &w, const tde_map &m, int k, Re
     return rc.red;
 }
 
-#ifndef TDE_RED_GAP_WIDE
-#define TDE_RED_GAP_WIDE 1          // 0: the stop-line loops a line at a time (A/B)
-#endif
 #ifndef TDE_RED_GAP_LINES
 #define TDE_RED_GAP_LINES 4         // stop lines fetched and tested side by side per trip of the wide loops (2 x 4 registers each)
 #endif
@@ -1075,12 +1062,11 @@ constexpr int kLinesPerTrip = TDE_RED_GAP_LINES;
 #endif
 // compute_traffic_lights_violations() > 0 for the ego box (gym_env.py:144,415,429): it overlaps a stop line whose light
 // is red.  Mirrors tde_tl_violation of the oracle.
-// `line(i, a, b)` fetches stop line i of the map: (x, y, cos, sin) and (hl, hw, light, -)
+// `line.cached(i, a, b)` (i < L::kCached) / `line.global(i, a, b)` fetch stop line i of the map: (x, y, cos, sin) and (hl, hw, light, -)
 template <typename L>
 TDE_DEV bool tl_violation_of(const L &line, int n_stop, uint32_t red, float x, float y, float c, float s, float hl, float hw)
 {
     bool v = false;
-#if TDE_RED_GAP_WIDE
     if (red) {
         // four lines per trip like red_line_gap_of: the reach tests side by side, the four-axis test for the lines in reach (rare)
         for (int k0 = 0; k0 < n_stop; k0 += kLinesPerTrip) {
@@ -1101,21 +1087,6 @@ TDE_DEV bool tl_violation_of(const L &line, int n_stop, uint32_t red, float x, f
 #pragma unroll
             for (int u = 0; u < kLinesPerTrip; ++u)
                 if (near[u]) v = v || obb_overlap(x, y, c, s, hl, hw, a[u].x, a[u].y, a[u].z, a[u].w, b[u].x, b[u].y);
-        }
-    }
-    return v;
-#endif
-    if (red) {
-        for (int i = 0; i < n_stop; ++i) {
-            float4 a, b;
-            line(i, a, b);
-            if ((red >> __float_as_int(b.z)) & 1u) {
-                // circumradius reject first, as in collide_rows (overlapping boxes have centres closer than the sum of their
-                // padded circumradii, in exact and in fp32 arithmetic): the ego is rarely within reach of a stop line, and
-                // the four-axis test is 40 instructions that the contended judge wavefront then never issues
-                const float dx = a.x - x, dy = a.y - y, rr = ((hl + hw) + (b.x + b.y)) * kReach;
-                if (dx * dx + dy * dy < rr * rr) v = v || obb_overlap(x, y, c, s, hl, hw, a.x, a.y, a.z, a.w, b.x, b.y);
-            }
         }
     }
     return v;
@@ -1147,7 +1118,6 @@ TDE_DEV float red_line_gap_of(const tde_config &cfg, const L &line, int n_stop, 
 {
     static_assert(L::kCached % kLinesPerTrip == 0, "a trip lies inside or outside the LDS cache");
     float gap = 1e30f;
-#if TDE_RED_GAP_WIDE
     // four lines per trip, all fetched first, the four tests side by side and branch-free (a minimum over the same values in
     // another order: same bits): on the driver's chain a line at a time was four dependent LDS round trips with a branch each
     for (int k0 = 0; k0 < n_stop; k0 += kLinesPerTrip) {
@@ -1172,19 +1142,6 @@ TDE_DEV float red_line_gap_of(const tde_config &cfg, const L &line, int n_stop, 
             gap = on ? fminf(gap, g + cfg.npc_gap_s0 - 1.0f) : gap;
         }
     }
-#else
-    for (int k = 0; k < n_stop; ++k) {
-        float4 a, b;
-        line(k, a, b);
-        if (!((red >> __float_as_int(b.z)) & 1u)) continue;
-        const float ex = a.x - ag.x, ey = a.y - ag.y;
-        const float fj = ex * cp + ey * sp;
-        const float lj = ey * cp - ex * sp;
-        const float hd = cp * a.z + sp * a.w;
-        const float g = fj - 0.5f * ag.len;
-        if (g > 0.0f && fabsf(lj) < b.y && hd > 0.5f) gap = fminf(gap, g + cfg.npc_gap_s0 - 1.0f);
-    }
-#endif
     return gap;
 }
 
@@ -1212,9 +1169,6 @@ TDE_DEV void write_tile_slot(float4 &ta, float4 &tb, bool live, const Agent &ag,
 // DRIVEN (env_step_driven_kernel alone): a present slot a >= 1 with `drv` set takes (drv_acc, drv_steer) from outside as slot 0 takes
 // the ego action - at every k, with or without TDE_F_NPC - and is not pulled to its replay record; its controller still runs (every
 // lane takes part in the sweeps) and its route bookkeeping stays an NPC's, so that the controller can have the slot back at any step.
-#ifndef TDE_SOLO_MAG_LEAN
-#define TDE_SOLO_MAG_LEAN 1         // the one-role kernel's magnitudes section with the low-register scan too (A/B)
-#endif
 template <int A, int BLOCK, bool LIGHTS, bool BIG = false, bool MAG = false, bool DRIVEN = false>
 TDE_DEV StepOut step_lane(const tde_config &cfg, const tde_world &w, const Cold &cold, const tde_state &st,
                           Tiles<BLOCK> &t, int e, int a, bool valid, Agent &ag, EnvRegs &er, Ctx &cx, float &c0,
@@ -1275,7 +1229,7 @@ TDE_DEV StepOut step_lane(const tde_config &cfg, const tde_world &w, const Cold 
     // of HBM / fabric traffic per step at 8192 x 16, same time); at 32 slots per env the extra round trip of the MIXED corners
     // costs 0.55 us of the launch's tail (15.85 -> 16.43 us, profiles/r03_f_step_cls2_ab.txt) and the cell words stay.
     // (BIG - a large grid, tde_world.hints: the cell words of a town are 66 MB per km^2 and the class map wins at any A)
-    constexpr bool kStepCls2 = (BLOCK == kBlock) && TDE_STEP_CLS2 && (A <= 16 || BIG);
+    constexpr bool kStepCls2 = (BLOCK == kBlock) && (A <= 16 || BIG);
     Corners corners;                                // cell words of the four corners: loads stay in flight during
     if (F & TDE_F_OFFROAD)                          // the collision sweep
         offroad_issue<kStepCls2>(w, cx.m, live, ag.x, ag.y, c0, s0, hl, hw, corners);
@@ -1564,11 +1518,6 @@ struct CachedLines {
     const DuoShared &sh;
     const tde_stopline *base;
     int envw;
-    TDE_DEV void operator()(int i, float4 &a, float4 &b) const
-    {
-        if (A >= 8 && i < kStopCache) { a = sh.stop[envw][i][0]; b = sh.stop[envw][i][1]; }
-        else { a = reinterpret_cast<const float4 *>(base + i)[0]; b = reinterpret_cast<const float4 *>(base + i)[1]; }
-    }
     static constexpr int kCached = A >= 8 ? kStopCache : 0;
     static_assert(kStopCache % kLinesPerTrip == 0, "red_line_gap_of walks the lines kLinesPerTrip at a time: a trip lies inside or outside the LDS cache");
     TDE_DEV void cached(int i, float4 &a, float4 &b) const { a = sh.stop[envw][i][0]; b = sh.stop[envw][i][1]; }
@@ -1585,7 +1534,6 @@ struct CacheOnlyLines {
     static constexpr int kCached = 1 << 20;
     TDE_DEV void cached(int i, float4 &a, float4 &b) const { a = sh.stop[envw][i][0]; b = sh.stop[envw][i][1]; }
     TDE_DEV void global(int i, float4 &a, float4 &b) const { cached(i, a, b); }
-    TDE_DEV void operator()(int i, float4 &a, float4 &b) const { cached(i, a, b); }
 };
 
 TDE_DEV void write_rows(DuoShared &sh, int buf, int lane, bool live, const Agent &ag, float c, float s, float lane_half)
@@ -1608,7 +1556,7 @@ __global__ __launch_bounds__(2 * kWave) __attribute__((amdgpu_waves_per_eu(4, 4)
     // The first-step gap cache pays where the controller's second pass walks stop lines (interleaved A/B at 8192 x 16, us per step,
     // cache / whole controller: with lights 3.92 / 4.13; without 2.935 / 2.905 - there the cheap path's code costs the loop more than
     // the re-spawned envs' second sweep does: profiles/r06_first_step_matrix.txt)
-    constexpr bool kGapCache = TDE_FIRST_GAP != 0 && LIGHTS;
+    constexpr bool kGapCache = LIGHTS;
     const bool first_acts = (F & TDE_F_NPC_FIRST_STEP) != 0;   // the NPC controller acts on an episode's first step too
     const int64_t g = (int64_t)blockIdx.x * kWave + lane;
     const int e = (int)(g / A), a = (int)(g % A);
@@ -1778,10 +1726,10 @@ __global__ __launch_bounds__(2 * kWave) __attribute__((amdgpu_waves_per_eu(4, 4)
             const bool live = rc.z != 0.0f;
             const float x = ra.x, y = ra.y, c0 = rb.x, s0 = rb.y, hl = rb.z, hw = rb.w;
             Corners corners;
-            if (F & TDE_F_OFFROAD) offroad_issue<BIG || TDE_ROLLOUT_CLS2>(w, cx.m, live, x, y, c0, s0, hl, hw, corners);
+            if (F & TDE_F_OFFROAD) offroad_issue<BIG>(w, cx.m, live, x, y, c0, s0, hl, hw, corners);
             const bool hit = collide_rows<A>(&sh.a[p][base], &sh.b[p][base], a, live, x, y, c0, s0, hl, hw, ra.z);
             bool off = false;
-            if (F & TDE_F_OFFROAD) off = offroad_resolve<false, BIG || TDE_ROLLOUT_CLS2>(w, corners, thr2, cx.m.rec_base);
+            if (F & TDE_F_OFFROAD) off = offroad_resolve<false, BIG>(w, corners, thr2, cx.m.rec_base);
             bool tl = false;
             if (LIGHTS && (F & TDE_F_TRAFFIC_LIGHTS) && a == 0 && valid)
                 tl = tl_violation_of(CachedLines<A>{sh, w.stoplines + cx.m.stop_base, lane / A}, cx.m.n_stop, red_mask_cached(w, cx.m, k, redc), x, y, c0, s0, hl, hw);
@@ -1832,11 +1780,8 @@ __global__ __launch_bounds__(2 * kWave) __attribute__((amdgpu_waves_per_eu(4, 4)
 // (tde_api.hip: step_args); the action pointer - the one field a closed loop changes from call to call - stays a by-value argument.
 // (The three-role kernels keep by-value arguments: at 6 wavefronts per SIMD the block's extra hop costs them 0.2 - 0.4 us, same file.)
 // `cold`: the block of rarely read arguments the other kernels park in LDS at their start (tde_device.h: Cold), here filled by the HOST with
-// the block: no fill on a lane, no barrier that publishes it (TDE_WIDE_COLD_IN_BLOCK=0: the LDS form, for the A/B).
+// the block: no fill on a lane, no barrier that publishes it.
 struct StepArgs { tde_config cfg; tde_world w; tde_state st; uint32_t act_hash; uint32_t pad; Cold cold; };
-#ifndef TDE_WIDE_COLD_IN_BLOCK
-#define TDE_WIDE_COLD_IN_BLOCK 1
-#endif
 
 // ------------------------------------------------------------------------------------------------------------------
 // The two-role rollout for 128 agent slots per env (the reference's ~100-agent scenes): ONE env per workgroup of four
@@ -1867,7 +1812,6 @@ struct WideLines {
     static constexpr int kCached = kStopCache;
     TDE_DEV void cached(int i, float4 &a, float4 &b) const { a = sh.stop[i][0]; b = sh.stop[i][1]; }
     TDE_DEV void global(int i, float4 &a, float4 &b) const { a = reinterpret_cast<const float4 *>(base + i)[0]; b = reinterpret_cast<const float4 *>(base + i)[1]; }
-    TDE_DEV void operator()(int i, float4 &a, float4 &b) const { if (i < kStopCache) cached(i, a, b); else global(i, a, b); }
 };
 TDE_DEV void fill_stop_cache_wide(WideShared &sh, const tde_world &w, const tde_map &m, int a)
 {
@@ -1882,7 +1826,7 @@ TDE_DEV void write_rows_wide(WideShared &sh, int buf, int a, bool live, const Ag
     float4 ta, tb;
     write_tile_slot(ta, tb, live, ag, c, s, lane_half);
     sh.a[buf][a] = ta; sh.b[buf][a] = tb;
-    if (TDE_WIDE_SYM && a < 64) sh.a[buf][a + 128] = ta;
+    if (a < 64) sh.a[buf][a + 128] = ta;
     sh.c[buf][a] = make_float4(ag.psi, ag.v, live ? 1.0f : 0.0f, 0.0f);
 }
 // the two judge wavefronts of an env exchange their credits: publish() once a wavefront's exact tests are done, joined() where the
@@ -1899,42 +1843,24 @@ TDE_DEV bool wide_sym_joined(WideShared &sh, int half, int a, int stamp)
 }
 
 // The role of a wavefront in the 128-slot two-role kernels: its index in the workgroup -> drive 0, drive 1, judge 0, judge 1.
-// (TDE_WIDE_ROTATE=1 rotates the roles by the workgroup index, in case the hardware placed a workgroup's wavefronts on the CU's
-//  SIMDs in order - every drive wavefront on SIMDs 0 / 1: it does not; same times, profiles/r06_z_wide_128.txt)
-#ifndef TDE_WIDE_ROTATE
-#define TDE_WIDE_ROTATE 0
-#endif
+// (Rotating the roles by the workgroup index - in case the hardware placed a workgroup's wavefronts on the CU's SIMDs in order, every
+//  drive wavefront on SIMDs 0 / 1 - was tried: it does not; same times, profiles/r06_z_wide_128.txt)
 TDE_DEV int wide_role_wave()
 {
-    const int w0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    return TDE_WIDE_ROTATE ? ((w0 + (int)(blockIdx.x & 3u)) & 3) : w0;
+    return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
 #ifndef TDE_WIDE2_WAVES
 #define TDE_WIDE2_WAVES 4
 #endif
-#ifndef TDE_WIDE_ROLLOUT_WAVES8
-#define TDE_WIDE_ROLLOUT_WAVES8 1     // 0: the library never launches the eight-wavefront rollout form (A/B)
-#endif
-#ifndef TDE_WIDE_ROLLOUT_BLOCK
-#define TDE_WIDE_ROLLOUT_BLOCK 0         // 1: the persistent kernel's arguments from the block too (A/B: 16 instead of 34 spilled VGPRs, and SLOWER -
-                                         // 1024 envs 5.25 -> 6.13 us per step: scalar loads inside the step loop; profiles/r06_z_wide_128.txt)
-#endif
 // NW = 8 (batches up to half a residency round): the eight-wavefront form of env_step_wide_kernel in the persistent loop - two sweep
 // helpers take rows 64-127 of the controller sweep of the drivers' slots (first pass only: a re-spawn's second pass is the drivers' own),
 // two offroad helpers take offroad and the ego's stop-line test; stamps instead of flags (the step number + 1).
+// (The arguments from a StepArgs block, as the one-step kernel takes them, were tried: 16 instead of 34 spilled VGPRs and slower -
+//  1024 envs 5.25 -> 6.13 us per step: scalar loads inside the step loop; profiles/r06_z_wide_128.txt)
 template <bool LIGHTS, int NW = 4>
-#if TDE_WIDE_ROLLOUT_BLOCK
-__global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(TDE_WIDE2_WAVES, TDE_WIDE2_WAVES))) void env_rollout_wide_kernel(const StepArgs *__restrict__ args,
-                                                                     tde_rollout ro)
-{
-    const tde_config &cfg = args->cfg;
-    const tde_world &w = args->w;
-    const tde_state &st = args->st;
-#else
 __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(TDE_WIDE2_WAVES, TDE_WIDE2_WAVES))) void env_rollout_wide_kernel(tde_config cfg, tde_world w, tde_state st,
                                                                      tde_rollout ro)
 {
-#endif
     constexpr int A = 128;
     __shared__ WideShared sh;
     __shared__ Cold cold;
@@ -2069,17 +1995,11 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(TDE_
             const float x = ra.x, y = ra.y, c0 = rb.x, s0 = rb.y, hl = rb.z, hw = rb.w;
             Corners corners;
             if (NW != 8 && (F & TDE_F_OFFROAD)) offroad_issue<false>(w, cx.m, live, x, y, c0, s0, hl, hw, corners);
-#if TDE_WIDE_SYM
             bool hit = collide_rows_wide_sym(&sh.a[p][0], &sh.b[p][0], a, live, x, y, c0, s0, hl, hw, ra.z, sh.coll, i + 1);
             wide_sym_publish(sh, wv & 1, lane, i + 1);
-#else
-            const bool hit = collide_rows_wide<A>(&sh.a[p][0], &sh.b[p][0], a, live, x, y, c0, s0, hl, hw, ra.z);
-#endif
             bool off = false;
             if (NW != 8 && (F & TDE_F_OFFROAD)) off = offroad_resolve<false, false>(w, corners, thr2, cx.m.rec_base);
-#if TDE_WIDE_SYM
             hit |= wide_sym_joined(sh, wv & 1, a, i + 1);
-#endif
             bool tl = false;
             if constexpr (NW == 8) {                         // (the offroad helper's flags for this half of the slots at this step)
                 while (*reinterpret_cast<volatile int *>(&sh.off_seq[wv & 1]) != i + 1) __builtin_amdgcn_s_sleep(1);
@@ -2245,9 +2165,7 @@ template <int N> TDE_DEV void dummy_valu(float seed)
 // (windowed reward, DPP collision prefilter) judge O's chain - four dependent cell-word loads per slot - is the longer one
 // of the two: (2, 0, 1) 2.93 us per step against (2, 1, 0) 3.00, (3, 0, 2) 2.93, (2, 0, 2) 2.99, (1, 0, 1) 2.99
 // (profiles/r02_d_ab_diet_steps.txt, tail)
-#ifndef TDE_STEP_PRIO_SWITCH    // one-step three-role kernel: priorities follow the critical path (driver -> judges -> driver)
-#define TDE_STEP_PRIO_SWITCH 1
-#endif
+// one-step three-role kernel: priorities follow the critical path (driver -> judges -> driver)
 #ifndef TDE_STEP_PRIO_D2        // ... behind barrier B: driver (next step's controller), judge C, judge O
 #define TDE_STEP_PRIO_D2 0
 #define TDE_STEP_PRIO_C2 3
@@ -2262,13 +2180,6 @@ template <int N> TDE_DEV void dummy_valu(float seed)
 #define TDE_PRIO_C 0
 #define TDE_PRIO_O 1
 #endif
-// TDE_ROLLOUT_CONST_ARGS (A/B builds only: one set of arguments per process, no two rollouts in flight): the four argument structs
-// in a __constant__ block instead of ~650 bytes of kernel arguments - the experiment of VERDICT r4 item 6 (do the SGPR spills and the
-// LDS copy of the cold arguments go away?); profiles/r05_c_ab_rollout_const_args.txt
-#ifndef TDE_ROLLOUT_CONST_ARGS
-#define TDE_ROLLOUT_CONST_ARGS 0
-#endif
-struct RolloutArgs { tde_config cfg; tde_world w; tde_state st; tde_rollout ro; uint32_t act_hash; };
 // a ballot with the OR of each env's A lane bits on the env's first (ego) lane bit; the other bits hold partial ORs
 // (wave-uniform: scalar shifts by constant amounts)
 template <int A> TDE_DEV unsigned long long fold_env_to_ego(unsigned long long m)
@@ -2277,21 +2188,12 @@ template <int A> TDE_DEV unsigned long long fold_env_to_ego(unsigned long long m
     for (int s = 1; s < A; s <<= 1) m |= m >> s;
     return m;
 }
-#if TDE_ROLLOUT_CONST_ARGS
-__constant__ RolloutArgs g_rollout_args;
-#endif
+// (The four argument structs in a __constant__ block instead of ~650 bytes of kernel arguments were tried: SGPR spills 32 -> 17,
+//  2.881 -> 2.896 us per step, profiles/r05_c_ab_rollout_const_args.txt)
 template <int A, bool LIGHTS, bool BIG>
 __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6))) void env_rollout_trio_kernel(
-#if TDE_ROLLOUT_CONST_ARGS
-    int unused_)
-{
-    const tde_config &cfg = g_rollout_args.cfg; const tde_world &w = g_rollout_args.w; const tde_state &st = g_rollout_args.st;
-    const tde_rollout &ro = g_rollout_args.ro;
-    const uint32_t act_hash = g_rollout_args.act_hash;
-#else
     tde_config cfg, tde_world w, tde_state st, tde_rollout ro, uint32_t act_hash)
 {
-#endif
     __shared__ DuoShared sh;
     __shared__ Cold cold;
     const int lane = threadIdx.x & (kWave - 1);
@@ -2315,7 +2217,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6)
     // The first-step gap cache pays where the controller's second pass walks stop lines (interleaved A/B at 8192 x 16, us per step,
     // cache / whole controller: with lights 3.92 / 4.13; without 2.935 / 2.905 - there the cheap path's code costs the loop more than
     // the re-spawned envs' second sweep does: profiles/r06_first_step_matrix.txt)
-    constexpr bool kGapCache = TDE_FIRST_GAP != 0 && LIGHTS;
+    constexpr bool kGapCache = LIGHTS;
     const bool first_acts = (F & TDE_F_NPC_FIRST_STEP) != 0;   // the NPC controller acts on an episode's first step too
     const int64_t g = (int64_t)blockIdx.x * kWave + lane;
     const int e = (int)(g / A), a = (int)(g % A);
@@ -2607,7 +2509,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6)
                 m = fold_env_to_ego<A>(__ballot(pair));
             } else {
                 // the last step: every slot's flag (st.collided below)
-                if constexpr (A == 16 && TDE_COLLIDE_DPP)
+                if constexpr (A == 16)
                     hit = collide_rows_dpp16(&sh.a[p][base], &sh.b[p][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
                 else
                     hit = collide_rows<A>(&sh.a[p][base], &sh.b[p][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
@@ -2687,12 +2589,12 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(6, 6)
                     bool corner = false;
                     if (a < 4 && sh.c[p][base].z != 0.0f) {
                         const float4 ea = sh.a[p][base], eb = sh.b[p][base];
-                        corner = corner_offroad<BIG || TDE_ROLLOUT_CLS2>(w, cx.m, a, ea.x, ea.y, eb.x, eb.y, eb.z, eb.w, thr2);
+                        corner = corner_offroad<BIG>(w, cx.m, a, ea.x, ea.y, eb.x, eb.y, eb.z, eb.w, thr2);
                     }
                     om = fold_env_to_ego<A>(__ballot(corner));
                 } else {
                     // the last step: every slot's flag (st.offroad below)
-                    off = box_offroad<false, BIG || TDE_ROLLOUT_CLS2>(w, cx.m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, thr2);
+                    off = box_offroad<false, BIG>(w, cx.m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, thr2);
                     om = __ballot(off);
                 }
             }
@@ -2829,9 +2731,6 @@ TDE_DEV int act_key_steps(uint32_t cfg_hash, int steps) { return (int)(cfg_hash 
 #ifndef TDE_WIDE4_SWEEP_BLOCK
 #define TDE_WIDE4_SWEEP_BLOCK 4
 #endif
-#ifndef TDE_WIDE_STEP_WAVES8
-#define TDE_WIDE_STEP_WAVES8 1       // 0: the library never launches the eight-wavefront form (A/B)
-#endif
 struct WideStepShared : WideShared {
     int early[2];                        // a drive wavefront has a slot without a stored action
     float poly[32];                      // MAG: box_iou_wave's vertex lists
@@ -2853,24 +2752,13 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
     const uint32_t act_hash = args->act_hash;
     constexpr int A = 128;
     __shared__ WideStepShared sh;
-#if TDE_WIDE_COLD_IN_BLOCK
-    const Cold &cold = args->cold;
-#define TDE_WIDE_COLD_BARRIER() ((void)0)
-#else
-    __shared__ Cold cold;
-#define TDE_WIDE_COLD_BARRIER() lds_barrier()
-#endif
+    const Cold &cold = args->cold;                          // (filled by the host with the block: StepArgs)
     const int lane = threadIdx.x & (kWave - 1);
     const int wv = wide_role_wave();
     const int role = wv >> 1;                               // 0 = drive, 1 = judge; NW = 8: 2 = sweep helper, 3 = offroad helper
     const int a = ((wv & 1) << 6) | lane;                   // the lane's slot
-    // (the cold block is filled by a JUDGE lane - the drivers' loads are the launch's first instructions - and published by an
-    //  LDS-only barrier that every role reaches with its loads in flight)
     // (every flag word in LDS is initialised by the wavefront that later sets it - program order - and read by the others behind a
     //  barrier that follows the initialisation: no barrier of its own)
-#if !TDE_WIDE_COLD_IN_BLOCK
-    if (wv == (NW == 8 ? 4 : 2) && lane == 0) fill_cold(cold, cfg, w);
-#endif
     const uint32_t F = cfg.flags;
     const bool first_acts = (F & TDE_F_NPC_FIRST_STEP) != 0;
     const bool lights = LIGHTS && (F & TDE_F_TRAFFIC_LIGHTS);
@@ -2891,7 +2779,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
         // stale entry falls back to the chain scenario -> spawn record -> route table and is rewritten (load_ctx_cached)
         int4 sc0 = make_int4(0, 0, 0, 0), sc1 = sc0;
         if (st.slot_cache) { sc0 = reinterpret_cast<const int4 *>(st.slot_cache + g)[0]; sc1 = reinterpret_cast<const int4 *>(st.slot_cache + g)[1]; }
-        TDE_WIDE_COLD_BARRIER();                             // cold is published
         Ctx cx;
         bool rebuilt;
         load_ctx_cached<A>(cfg, cold, st, g, a, true, sc0, sc1, ag, er, cx, false, rebuilt);
@@ -2935,7 +2822,7 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
             // slowest workgroup): min(the scenario's first-step gap, the exact test against the ego's row) instead of the 128-row
             // sweep and the stop-line loop (npc_first_step; the ego's row is in the first half).  k is the env's: uniform.
             bool have = false;
-            if (TDE_FIRST_GAP && first_acts && k == 1 && w.first_gap) {
+            if (first_acts && k == 1 && w.first_gap) {
                 uint2 fe = make_uint2(0u, 0u);
                 if (npc) fe = *reinterpret_cast<const uint2 *>(w.first_gap + ((int64_t)er.scn * A + a));
                 have = npc_first_step<64>(cfg, fe, first_gap_key(act_hash), &sh.a[1][0], &sh.b[1][0], a, ag, c0, s0, npc, has_target, cx.tgx, cx.tgy, na, nb);
@@ -3006,7 +2893,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
         EnvRegs er{st.scn[e], st.steps[e], st.target_idx[e], st.reached[e], st.episode[e]};
         double ep_ret = 0.0;
         if (a == 0 && st.ep_return) ep_ret = st.ep_return[e];
-        TDE_WIDE_COLD_BARRIER();                             // cold is published
         Ctx cx;
         cx.tgx = cx.tgy = 0.0f; cx.route_n = 0; cx.replay_len = 0; cx.wtx = cx.wty = 0.0; cx.n_wp = 0; cx.g_far = 0.0f;
         {
@@ -3030,17 +2916,11 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
         const float x = ra.x, y = ra.y, c0 = rb.x, s0 = rb.y, hl = rb.z, hw = rb.w;
         Corners corners;
         if (NW != 8 && (F & TDE_F_OFFROAD)) offroad_issue<false>(w, cx.m, live, x, y, c0, s0, hl, hw, corners);
-#if TDE_WIDE_SYM
         bool hit = collide_rows_wide_sym(&sh.a[0][0], &sh.b[0][0], a, live, x, y, c0, s0, hl, hw, ra.z, sh.coll, 1);
         wide_sym_publish(sh, wv & 1, lane, 1);
-#else
-        const bool hit = collide_rows_wide<A>(&sh.a[0][0], &sh.b[0][0], a, live, x, y, c0, s0, hl, hw, ra.z);
-#endif
         bool off = false;
         if (NW != 8 && (F & TDE_F_OFFROAD)) off = offroad_resolve<true, false>(w, corners, thr2, cx.m.rec_base);
-#if TDE_WIDE_SYM
         hit |= wide_sym_joined(sh, wv & 1, a, 1);
-#endif
         bool tl = false;
         if constexpr (NW == 8) {                             // (the offroad helper's flags for this half of the slots)
             while (*reinterpret_cast<volatile int *>(&sh.off_seq[wv & 1]) != 1) __builtin_amdgcn_s_sleep(1);
@@ -3133,7 +3013,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
         // ================================ sweep helper (NW = 8) ================================
         __builtin_amdgcn_s_setprio(2);
         if (lane == 0) sh.help_seq[wv & 1] = 0;
-        TDE_WIDE_COLD_BARRIER();                             // cold
         lds_barrier();                                       // E
         if (sh.early[0] | sh.early[1]) lds_barrier();        // E2
         lds_barrier();                                       // B: rows of this step are in buffer 0, the drivers' ctl words beside them
@@ -3153,7 +3032,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
         __builtin_amdgcn_s_setprio(1);
         if (lane == 0) sh.off_seq[wv & 1] = 0;
         const int scn = st.scn[e], k = st.steps[e] + 1;
-        TDE_WIDE_COLD_BARRIER();                             // cold
         tde_map m{};
         if (F & (TDE_F_OFFROAD | TDE_F_TRAFFIC_LIGHTS)) m = cold.maps[reinterpret_cast<const int4 *>(cold.scn)[scn].x];
         const float thr2 = thr2_of(cfg);
@@ -3176,7 +3054,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4
         lds_barrier();                                       // A
     }
 }
-#undef TDE_WIDE_COLD_BARRIER
 
 
 // MAG: also writes tde_state.magnitudes (judge O, behind barrier A); a template flag because the code, taken or not, costs the
@@ -3307,7 +3184,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
             const bool stored = !npc || (k == 1 && !first_acts) || (akey.x == er.episode && akey.y == act_key_steps(act_hash, er.steps));
             // first step with TDE_F_NPC_FIRST_STEP: the launch that re-spawned the env forwarded its slots' entries of the world's
             // first-step gap cache in place of actions (key domain kGapForm; npc_first_step)
-            const bool gap_ok = TDE_FIRST_GAP && first_acts && k == 1 && akey.x == er.episode && akey.y == act_key_steps(act_hash ^ kGapForm, er.steps) &&
+            const bool gap_ok = first_acts && k == 1 && akey.x == er.episode && akey.y == act_key_steps(act_hash ^ kGapForm, er.steps) &&
                                 (!has_target || __float_as_uint(ac.y) == first_gap_key(act_hash));
             if (__ballot(!stored)) {
                 sincos_f32(ag.psi, s0, c0);
@@ -3345,7 +3222,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
         lds_barrier();                                       // B: rows of this step are in buffer 0
         // behind B the critical path is the judges' (stamps: C 4.8 k, O 4.1 k cycles against 3.2 k for the controller below):
         // the driver steps back until their masks are in
-        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_D2);
+        __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_D2);
         if (switched && need_tg2) load_route_target(cold, ag, cx);               // (the look-ahead entry was not there yet: rare)
         if (switched || need_tg2) load_next_target(cold, ag, cx.route_n, cx.tgx2, cx.tgy2);   // (only stored: the entry after the current one)
         // the controller of the NEXT step runs here, beside the judges of this one: it needs the state after this step
@@ -3356,7 +3233,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
         if ((F & TDE_F_NPC) && st.act_cache) controller(0, false, na2, nb2);
         constexpr bool kDrawAhead = A >= 8;                  // (judge C has drawn the next episode's random words: sh.draw)
         lds_barrier();                                       // A: the judges' masks are published
-        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(3);                 // the launch's tail: re-spawn and stores
+        __builtin_amdgcn_s_setprio(3);                 // the launch's tail: re-spawn and stores
         unsigned long long term_m, trunc_m;
         const unsigned long long dn = done_of(k, term_m, trunc_m);
         bool respawned = false;
@@ -3371,7 +3248,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
                 // Requested AHEAD of the spawn record's loads (the new scenario is known from the parked draw): behind them it was a
                 // second memory round trip on the tail every launch waits for
                 uint2 fe = make_uint2(0u, 0u);
-                const bool fwd_lane = TDE_FIRST_GAP && kDrawAhead && first_acts && (F & TDE_F_NPC) && a > 0 && w.first_gap && st.act_cache;
+                const bool fwd_lane = kDrawAhead && first_acts && (F & TDE_F_NPC) && a > 0 && w.first_gap && st.act_cache;
                 if (fwd_lane)
                     fe = *reinterpret_cast<const uint2 *>(w.first_gap + ((int64_t)(int)(((uint64_t)sh.draw[lane / A][0].x * (uint64_t)cold.n_scn) >> 32) * A + a));
                 respawn_lane<A, kDrawAhead>(cfg, cold, e, a, ag, er, cx, false, sh.draw[lane / A][0], sh.draw[lane / A][1],
@@ -3393,7 +3270,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
             float2 *ap = reinterpret_cast<float2 *>(st.act_cache) + (int64_t)e * (A + 1);
             ap[a] = make_float2(na2, nb2);
             if (a == 0) {   // (re-spawn is per env: the ego lane's flag is the env's)
-                const bool fwd = TDE_FIRST_GAP && kDrawAhead && respawned && first_acts && (F & TDE_F_NPC) && w.first_gap;     // the slots hold forwarded gaps
+                const bool fwd = kDrawAhead && respawned && first_acts && (F & TDE_F_NPC) && w.first_gap;     // the slots hold forwarded gaps
                 reinterpret_cast<int2 *>(ap)[A] = make_int2(((F & TDE_F_NPC) && (!respawned || fwd)) ? er.episode : -1,
                                                             act_key_steps(fwd ? act_hash ^ kGapForm : act_hash, er.steps));
             }
@@ -3436,12 +3313,12 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
         if (respawns && a < 2)
             sh.draw[lane / A][a] = philox(cold.seed, cold.env_base + (uint32_t)es, (uint32_t)er.episode, (uint32_t)a, 0x7DEu);
         lds_barrier();                                       // B
-        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_C2);    // the longest chain behind B
+        __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_C2);    // the longest chain behind B
         er.steps += 1;
         const int k = er.steps;
         const float4 ra = sh.a[0][lane], rb = sh.b[0][lane], rc = sh.c[0][lane];
         bool hit;
-        if constexpr (A == 16 && TDE_COLLIDE_DPP)
+        if constexpr (A == 16)
             hit = collide_rows_dpp16(&sh.a[0][base], &sh.b[0][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
         else
             hit = collide_rows<A>(&sh.a[0][base], &sh.b[0][base], a, rc.z != 0.0f, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, ra.z);
@@ -3596,7 +3473,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
             if (a == 0) sh.lights[lane / A] = make_int4((int)red_k, (int)red_n, m.stop_base, m.n_stop);
         }
         lds_barrier();                                       // B
-        if (TDE_STEP_PRIO_SWITCH) __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_O2);
+        __builtin_amdgcn_s_setprio(TDE_STEP_PRIO_O2);
         const float4 ra = sh.a[0][lane], rb = sh.b[0][lane], rc = sh.c[0][lane];
         const bool live = rc.z != 0.0f;
         bool off = false, tl = false;
@@ -3607,7 +3484,7 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
         uint32_t tw0 = 0u, tw1 = 0u, tw2 = 0u, tw3 = 0u;
         if (F & TDE_F_OFFROAD) {
             if constexpr (MAG) {
-                offroad_issue<TDE_STEP_CLS2 != 0>(w, m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, kc);
+                offroad_issue<true>(w, m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, kc);
                 // (only for an ego with a corner outside the FULL cells - one that CAN be off the road: the others' words would be
                 //  four more loads per env that this wavefront has to wait for ahead of barrier A, and every workgroup has egos)
                 // (tried, profiles/r05_magnitudes_floor.md: EVERY ego's words, issued beside the class look-ups: +0.16 us; the words kept
@@ -3616,9 +3493,9 @@ __global__ __launch_bounds__(3 * kWave) __attribute__((amdgpu_waves_per_eu(trio_
                     tw0 = near_tile_word(w, m, kc.px0, kc.py0); tw1 = near_tile_word(w, m, kc.px1, kc.py1);
                     tw2 = near_tile_word(w, m, kc.px2, kc.py2); tw3 = near_tile_word(w, m, kc.px3, kc.py3);
                 }
-                off = offroad_resolve<true, TDE_STEP_CLS2 != 0>(w, kc, thr2, m.rec_base);
+                off = offroad_resolve<true, true>(w, kc, thr2, m.rec_base);
             } else {
-                off = box_offroad<true, TDE_STEP_CLS2 != 0>(w, m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, thr2);
+                off = box_offroad<true, true>(w, m, live, ra.x, ra.y, rb.x, rb.y, rb.z, rb.w, thr2);
             }
         }
         if (LIGHTS && (F & TDE_F_TRAFFIC_LIGHTS) && a == 0 && valid) {

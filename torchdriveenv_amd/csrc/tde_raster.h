@@ -77,8 +77,7 @@ struct RasterJob {
     // image
     int H, W, ns, phase, flags;
     float res, inv_res, thr2;
-    int K8, K4;                                  // clearance units that make an 8x8 / 4x4 block of pixel centres uniform (in
-                                                 // TDE_COARSE_UNITs; TDE_CLEARANCE_UNITs in the TDE_RASTER_COARSE=0 tuning build)
+    int K8, K4;                                  // clearance units (TDE_COARSE_UNITs) that make an 8x8 / 4x4 block of pixel centres uniform
     uint8_t *out;                                // this view's [3 * ns][H][W]
     uint8_t *ring;                               // this view's [ns][H * W] layer planes, or nullptr
     bool fresh;
@@ -86,15 +85,14 @@ struct RasterJob {
 
 // Round 4: the block pyramid reads the COARSE table (tde_world.cell_coarse: one byte per 4 x 4 cells, 16 x 8 tiles per 128-byte
 // line) instead of the clearance field of the cell words: its 320 look-ups per view touched ~320 cache lines of a table of
-// 66 MB per km^2, now ~20 lines of a table of 1 MB per km^2.  TDE_RASTER_COARSE=0 keeps the cell-word form (A/B builds).
-#ifndef TDE_RASTER_COARSE
-#define TDE_RASTER_COARSE 1
-#endif
+// 66 MB per km^2, now ~20 lines of a table of 1 MB per km^2.  (The cell-word form was tried against it: slower,
+// profiles/r04_raster_floor.md.)
 
-// clearance (in units of `unit` metres, rounded up) at which an n x n block of pixel centres is uniform: the centres lie
+// clearance (in TDE_COARSE_UNITs, rounded up) at which an n x n block of pixel centres is uniform: the centres lie
 // within half a diagonal of the block's centre; 1 % + 2 cm cover the fp32 evaluation of both
-inline int raster_block_clearance(int n, float res, float unit = TDE_RASTER_COARSE ? TDE_COARSE_UNIT : TDE_CLEARANCE_UNIT)
+inline int raster_block_clearance(int n, float res)
 {
+    const float unit = TDE_COARSE_UNIT;
     const float r = 0.5f * (float)(n - 1) * 1.41421356f * res * 1.01f + 0.02f;
     int k = (int)(r / unit);
     while ((float)k * unit < r) ++k;
@@ -173,16 +171,12 @@ TDE_DEV uint32_t raster_lookup(const RasterJob &J, const RasterView &V, float u,
 // class | clearance << 2 of the coarse tile under pixel (u, v) (tde_abi.h: tde_world.cell_coarse); the pyramid's look-up
 TDE_DEV uint32_t raster_coarse(const RasterJob &J, const RasterView &V, float u, float v)
 {
-#if TDE_RASTER_COARSE
     const float fx = __builtin_amdgcn_fmed3f(__builtin_fmaf(v, V.cbx, __builtin_fmaf(u, V.cax, V.c0x)), 0.0f, V.nxm1);
     const float fy = __builtin_amdgcn_fmed3f(__builtin_fmaf(v, V.cby, __builtin_fmaf(u, V.cay, V.c0y)), 0.0f, V.nym1);
     const uint32_t cx = (uint32_t)(int)fx >> 2, cy = (uint32_t)(int)fy >> 2;
     static_assert(TDE_COARSE_CELLS == 4, "coarse tiles of 4 x 4 cells");
     const uint32_t line = (uint32_t)J.m.coarse_base + ((cy >> 3) << (J.m.row_shift - 6)) + (cx >> 4);
     return J.cell_coarse[(line << 7) | (((cy & 7u) << 4) | (cx & 15u))];
-#else
-    return raster_lookup(J, V, u, v) & 1023u;
-#endif
 }
 
 // class of the sub-cell of a MIXED cell that holds the clamped cell coordinates (fx, fy): two bits of the cell's word in
@@ -362,7 +356,7 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
 
     // the first 64 candidates of every kind of object (stop lines, waypoints, agent slots) are fetched together (one memory round
     // trip instead of three).  (Issued earlier - ahead of the last MIXED-pixel resolution - their ten registers spill: 21 VGPR
-    // spills under the 64-VGPR cap of eight views per SIMD.)
+    // spills under the 64-VGPR cap of eight views per SIMD.  Ahead of the pyramid was tried too: slower, profiles/r04_raster_floor.md.)
     float4 la0 = make_float4(0.0f, 0.0f, 1.0f, 0.0f), lb0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     double2 wp0 = make_double2(0.0, 0.0);
     typename std::remove_reference<AgentSrc>::type::Raw raw0{};
@@ -374,10 +368,6 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
         if (J.ti + lane < J.n_wp) wp0 = reinterpret_cast<const double2 *>(J.wp)[J.ti + lane];
         if (lane < J.A) raw0 = agent.fetch(lane);
     };
-#ifndef TDE_RASTER_EARLY_OBJECTS
-#define TDE_RASTER_EARLY_OBJECTS 0     // 1: the object records' loads ahead of the pyramid (A/B: profiles/r04_raster_floor.md)
-#endif
-    if (TDE_RASTER_EARLY_OBJECTS) fetch_objects();
     // ---- base layer, 8x8 -> 4x4 -> 2x2 blocks -> pixels; lane b owns 8x8 block b ---------------------------------------
     {
         const int nbw = Wp >> 3, nblk = (Hp >> 3) * nbw, nb4w = Wp >> 2;      // nblk <= 64
@@ -389,25 +379,15 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
         {
             // the block's own look-up and those of its four 4x4 sub-blocks are issued TOGETHER (the sub-blocks' are wasted
             // when the 8x8 block turns out uniform - about half of them - but a dependent round trip is what a view pays for)
-#ifndef TDE_RASTER_SPEC_L1
-#define TDE_RASTER_SPEC_L1 1
-#endif
             uint32_t wd = 0u, w4[4] = {0u, 0u, 0u, 0u};
             if (have) {
                 wd = raster_coarse(J, V, u8, v8);
-                if (TDE_RASTER_SPEC_L1) {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-                        w4[s] = raster_coarse(J, V, u8 + ((s >> 1) ? -2.0f : 2.0f), v8 + ((s & 1) ? -2.0f : 2.0f));
-                }
-            }
-            const uint32_t cls = wd & 3u;
-            const bool uni = cls != TDE_CELL_MIXED && (int)(wd >> 2) >= J.K8;
-            if (!TDE_RASTER_SPEC_L1 && have && !uni) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
                     w4[s] = raster_coarse(J, V, u8 + ((s >> 1) ? -2.0f : 2.0f), v8 + ((s & 1) ? -2.0f : 2.0f));
             }
+            const uint32_t cls = wd & 3u;
+            const bool uni = cls != TDE_CELL_MIXED && (int)(wd >> 2) >= J.K8;
             if (have && uni) {
                 const uint2 val = cls == TDE_CELL_FULL ? make_uint2(0x01010101u, 0x01010101u) : make_uint2(0u, 0u);
 #pragma unroll
@@ -539,7 +519,7 @@ TDE_DEV void raster_view(RasterScratch &S, const RasterJob &J, AgentSrc &&agent,
             raster_paint_box(p8, V, Wp, Pb, Qb, Xb, lane);
         }
     };
-    if (!TDE_RASTER_EARLY_OBJECTS) fetch_objects();
+    fetch_objects();
     if (J.lights) {
         for (int q0 = 0; q0 < J.m.n_stop; q0 += 64) {
             const int q = q0 + lane;

@@ -116,7 +116,8 @@
         // +15 % per step at 65 536 envs x 16, where this kernel runs)
         const unsigned long long ego = __ballot(a == 0 && valid);
         const int w0 = (int)(threadIdx.x & ~63u);
-        ego_magnitudes_of_wave<A, TDE_SOLO_MAG_LEAN != 0>(cfg, w, [&](int src) { return cold.maps[__builtin_amdgcn_readlane(map0, src)]; }, ego,
-                                                           hit_m, off_m, &t.a[w0], &t.b[w0], (int)(threadIdx.x & 63u), t.poly[threadIdx.x >> 6],
-                                                           (a == 0 && valid) ? reinterpret_cast<float4 *>(st.magnitudes) + e : nullptr);
+        // (LEAN = true: the low-register scan of the role-split kernels here too)
+        ego_magnitudes_of_wave<A, true>(cfg, w, [&](int src) { return cold.maps[__builtin_amdgcn_readlane(map0, src)]; }, ego,
+                                        hit_m, off_m, &t.a[w0], &t.b[w0], (int)(threadIdx.x & 63u), t.poly[threadIdx.x >> 6],
+                                        (a == 0 && valid) ? reinterpret_cast<float4 *>(st.magnitudes) + e : nullptr);
     }

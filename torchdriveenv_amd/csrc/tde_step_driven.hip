@@ -44,7 +44,7 @@ int tde_env_step_driven(const tde_config *cfg, const tde_world *world, const tde
         return bad("tde_env_step_driven: state.slot_route is set: routes of near-field agents and outside actions do not combine yet (step such a state with tde_env_step)");
     if (st->B <= 0) return 0;
     if (!st->action) return bad("tde_env_step_driven: state.action is NULL");
-    if ((cfg->flags & TDE_F_OFFROAD) && TDE_STEP_CLS2 && !world->cell_cls2) return bad("tde_env_step_driven: world.cell_cls2 is NULL (ABI 7 class map)");
+    if ((cfg->flags & TDE_F_OFFROAD) && !world->cell_cls2) return bad("tde_env_step_driven: world.cell_cls2 is NULL (ABI 7 class map)");
     return st->magnitudes ? tde_host::launch_step_driven_mag(cfg, world, st, agent_action, driven, stream)
                           : tde_host::launch_step_driven(cfg, world, st, agent_action, driven, stream);
 }
