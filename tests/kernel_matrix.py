@@ -3,7 +3,7 @@ is meant to launch.  A plain helper module: tests/test_kernel_matrix.py checks t
 same set, tests/test_gpu_kernel_matrix.py runs every case against the oracle, scripts/kernel_coverage.py checks from a rocprofv3
 trace of that run that every label was really launched.
 
-A case's label is written by hand from the launchers (csrc/tde_api.hip, tde_step_*.hip, tde_rollout_*.hip); it is NOT derived from
+A case's label is written by hand from the launchers (csrc/tde_api.hip, tde_launch.h, tde_step_*.hip, tde_rollout_*.hip); it is NOT derived from
 a restatement of the dispatch: the trace is what confirms it."""
 import re
 import subprocess

@@ -16,7 +16,7 @@ UNITS = ["tde_step_solo_mag.hip", "tde_step_routed_mag.hip", "tde_step_driven_ma
          "tde_rollout_duo.hip", "tde_rollout_solo.hip", "tde_render_scene.hip", "tde_near_field.hip", "tde_vector_obs.hip", "tde_planner.hip",
          "tde_plan_set.hip", "tde_forecast.hip", "tde_forecast_scene.hip", "tde_plan_scene.hip", "tde_api.hip", "tde_replay.hip", "tde_onpolicy.hip", "tde_terminal.hip", "tde_nstep.hip", "tde_priority.hip", "tde_sequence.hip", "tde_snapshot.hip"]
 SRC = [os.path.join(_CSRC, u) for u in UNITS]
-HEADERS = ["tde_kernels.h", "tde_host.h", "tde_ring.h", "tde_device.h", "tde_raster.h", "tde_gridbuild.h", "tde_magnitudes.h", "tde_magnitudes_kernels.h", "tde_eval_kernels.h", "tde_step_body.inc"]
+HEADERS = ["tde_kernels.h", "tde_host.h", "tde_launch.h", "tde_ring.h", "tde_device.h", "tde_raster.h", "tde_gridbuild.h", "tde_magnitudes.h", "tde_magnitudes_kernels.h", "tde_eval_kernels.h", "tde_step_body.inc"]
 DEPS = SRC + [os.path.join(_CSRC, h) for h in HEADERS] + [os.path.join(_PKG, "..", "include", h)
                                                           for h in ["tde_abi.h"] + [f.header for f in FAMILIES + ADDED_FAMILIES]]
 OUT = os.path.join(_PKG, "libtde_hip.so")

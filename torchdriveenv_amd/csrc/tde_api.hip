@@ -286,12 +286,9 @@ static const tde::StepArgs *step_args(const tde_config *cfg, const tde_world *wo
 static int env_step_launch(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream, int64_t load_slots)
 {
     int rc = check_env_args("tde_env_step", cfg, world, st);
-    if (rc) return rc;
-    if (st->B <= 0) return 0;
-    if (!st->action) return bad("tde_env_step: state.action is NULL");
+    bool run = false;
+    if (rc || (rc = tde_host::check_step_batch("tde_env_step", cfg, world, st, &run)) || !run) return rc;
     if (st->slot_route && st->A < 4) return bad("tde_env_step: state.slot_route needs at least 4 agent slots per env");
-    if ((cfg->flags & TDE_F_OFFROAD) && !world->cell_cls2) return bad("tde_env_step: world.cell_cls2 is NULL (ABI 7 class map)");
-    const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
     // With the lookup caches present (and a group shape the three-role kernels are built for) the step runs as three
     // wavefronts per 64 agent slots; tde_kernel_override forces one form (A/B runs).
     // Which one wins is a matter of load (bench.py --mode step --step-kernel solo|trio, us per step at 16 agents per env,
@@ -304,7 +301,7 @@ static int env_step_launch(const tde_config *cfg, const tde_world *world, const 
     // 131 072 agent slots, one role above (configs[4]: 8192 x 32).  tde_kernel_override(0, 1 | 3) forces one.
     // per-slot routes: always the routed one-role form (no tde_kernel_override, no lookup caches: the spawner that wrote the array has
     // invalidated their entries, which keeps them right for a caller who drops the array later)
-    if (st->slot_route) return st->magnitudes ? tde_host::launch_step_routed_mag(cfg, world, st, stream) : tde_host::launch_step_routed(cfg, world, st, stream);
+    if (st->slot_route) return tde_host::step_routed(cfg, world, st, stream);
     const int force = g_force_step;
     // (slot entries pack route / replay ids into 20 bits and their lengths into 12: tde_abi.h)
     const int32_t id_max = (1 << TDE_CACHE_ID_BITS) - 1, len_max = 1 << (32 - TDE_CACHE_ID_BITS);
@@ -336,8 +333,8 @@ static int env_step_launch(const tde_config *cfg, const tde_world *world, const 
         return tde_host::launch_step_trio(cfg, world, st, tde_host::act_cfg_hash(*cfg, *world), stream);
     }
     // the one-role kernel (its forms - the class map on large grids, four wavefronts per SIMD for big 128-slot batches - are chosen
-    // by the launcher); with / without tde_state.magnitudes are two translation units
-    return st->magnitudes ? tde_host::launch_step_solo_mag(cfg, world, st, stream) : tde_host::launch_step_solo(cfg, world, st, stream);
+    // by the launcher: launch_step_one_role, tde_launch.h)
+    return tde_host::step_solo(cfg, world, st, stream);
 }
 
 int tde_env_step(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream)
@@ -784,6 +781,18 @@ int tde_state_obs(const tde_world *world, const tde_state *st, float *out, void 
 
 // (for the units that define entry points of their own over (config, world, state): tde_step_driven.hip)
 int tde_host::check_env_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st) { return ::check_env_args(fn, cfg, w, st); }
+
+// the rules tde_env_step and tde_env_step_driven share once check_env_args has passed: an empty batch is a no-op, one with envs
+// needs its actions and, to judge offroad, the class map
+int tde_host::check_step_batch(const char *fn, const tde_config *cfg, const tde_world *world, const tde_state *st, bool *run)
+{
+    *run = false;
+    if (st->B <= 0) return 0;
+    if (!st->action) return bad_in(fn, "state.action is NULL");
+    if ((cfg->flags & TDE_F_OFFROAD) && !world->cell_cls2) return bad_in(fn, "world.cell_cls2 is NULL (ABI 7 class map)");
+    *run = true;
+    return 0;
+}
 
 // host-side table build (no kernels): tde_grid_build / tde_grid_free
 #include "tde_gridbuild.h"

@@ -12,6 +12,7 @@
 // The device functions are the step's own; tests/forecast_scene_ref.py restates the rule in numpy.
 #include "tde_kernels.h"
 #include "tde_host.h"
+#include "tde_launch.h"
 
 namespace tde {
 
@@ -94,10 +95,9 @@ int launch_forecast_scene(const tde_config *cfg, const tde_world *world, const t
 {
     const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
     const unsigned nb = (unsigned)(((int64_t)st->B * st->A + tde::kBlock - 1) / tde::kBlock);
-#define TDE_LAUNCH_FORM(AA, L) \
-    tde::forecast_scene_kernel<AA, L><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, T, ego_action, only, reinterpret_cast<float4 *>(out))
-    TDE_DISPATCH_A128(st->A, if (lights) TDE_LAUNCH_FORM(kA, true); else TDE_LAUNCH_FORM(kA, false));
-#undef TDE_LAUNCH_FORM
+    TDE_DISPATCH_A128(st->A, with_flags({lights}, [&](auto l) {
+        tde::forecast_scene_kernel<kA, l.value><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, T, ego_action, only, reinterpret_cast<float4 *>(out));
+    }));
     return launch_status("tde_forecast_scene");
 }
 

@@ -1,5 +1,5 @@
 // tde_host.h — what the translation units of libtde_hip.so share on the HOST side: the error slot of tde_last_error, the
-// dispatch-by-slot-count macros and the launchers each kernel family's unit exports to the C-ABI entry points in tde_api.hip.
+// dispatch-by-slot-count macros (the step and rollout units use tde_launch.h instead) and the launchers each kernel family's unit exports to the C-ABI entry points in tde_api.hip.
 // Everything here has hidden visibility (the library is built with -fvisibility=hidden; only TDE_API symbols are exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -89,24 +89,39 @@ inline uint32_t act_cfg_hash(const tde_config &cfg, const tde_world &w)
 // side).  All return 0 or a hipError_t value with the message in the error slot. -------------------------------------------------
 // tde_step_trio.hip: env_step_trio_kernel<A in {8, 16, 32}, LIGHTS, OBS, MAG>
 int launch_step_trio(const tde_config *cfg, const tde_world *world, const tde_state *st, uint32_t act_hash, void *stream);
-// tde_step_wide.hip: env_step_wide_kernel<LIGHTS, OBS, MAG> (128 agent slots per env, two roles)
+// tde_step_wide.hip: env_step_wide_kernel<LIGHTS, OBS, MAG, NW = 4> (128 agent slots per env, two roles)
 // (`args` = the launch's argument block in device memory, tde_api.hip: step_args; `st` = the caller's struct - shape, optional outputs, action)
 int launch_step_wide(const tde::StepArgs *args, const tde_config *cfg, const tde_state *st, int waves, void *stream);
 // tde_step_wide8.hip: the same kernel's eight-wavefront instantiations (launch_step_wide hands waves == 8 over)
 int launch_step_wide8(const tde::StepArgs *args, const tde_config *cfg, const tde_state *st, void *stream);
-// tde_step_solo.hip / tde_step_solo_mag.hip: env_step_kernel<A, LIGHTS, OBS, BIG, WAVES, MAG = false / true>
+// The one-role step families.  Each is two translation units, without / with tde_state.magnitudes (MAG = false / true; the split is for
+// compile time), and every unit's launcher is launch_step_one_role (tde_launch.h: the choice of form is stated there).  Callers go
+// through step_solo / step_routed / step_driven below, which pick the unit.
+// tde_step_solo.hip / tde_step_solo_mag.hip: env_step_kernel<A, LIGHTS, OBS, BIG, WAVES, MAG>
 int launch_step_solo(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
 int launch_step_solo_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
-// tde_step_routed.hip / tde_step_routed_mag.hip: env_step_routed_kernel<A >= 4, LIGHTS, OBS, BIG, WAVES, MAG = false / true> (state.slot_route != NULL)
+// tde_step_routed.hip / tde_step_routed_mag.hip: env_step_routed_kernel<A >= 4, LIGHTS, OBS, BIG, WAVES, MAG> (state.slot_route != NULL)
 int launch_step_routed(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
 int launch_step_routed_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream);
-// tde_step_driven.hip / tde_step_driven_mag.hip: env_step_driven_kernel<A, LIGHTS, OBS, BIG, WAVES, MAG = false / true> (tde_env_step_driven)
-int launch_step_driven(const tde_config *cfg, const tde_world *world, const tde_state *st, const float *agent_action,
-                       const uint8_t *driven, void *stream);
-int launch_step_driven_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, const float *agent_action,
-                           const uint8_t *driven, void *stream);
+// tde_step_driven.hip / tde_step_driven_mag.hip: env_step_driven_kernel<A, LIGHTS, OBS, BIG, WAVES, MAG> (tde_env_step_driven)
+int launch_step_driven(const tde_config *cfg, const tde_world *world, const tde_state *st, const float *agent_action, const uint8_t *driven, void *stream);
+int launch_step_driven_mag(const tde_config *cfg, const tde_world *world, const tde_state *st, const float *agent_action, const uint8_t *driven, void *stream);
+inline int step_solo(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream)
+{
+    return st->magnitudes ? launch_step_solo_mag(cfg, world, st, stream) : launch_step_solo(cfg, world, st, stream);
+}
+inline int step_routed(const tde_config *cfg, const tde_world *world, const tde_state *st, void *stream)
+{
+    return st->magnitudes ? launch_step_routed_mag(cfg, world, st, stream) : launch_step_routed(cfg, world, st, stream);
+}
+inline int step_driven(const tde_config *cfg, const tde_world *world, const tde_state *st, const float *agent_action, const uint8_t *driven, void *stream)
+{
+    return st->magnitudes ? launch_step_driven_mag(cfg, world, st, agent_action, driven, stream) : launch_step_driven(cfg, world, st, agent_action, driven, stream);
+}
 // tde_api.hip: what every entry point that takes (config, world, state) checks first; the message names `fn`
 int check_env_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st);
+// tde_api.hip: what tde_env_step and tde_env_step_driven ask of the batch after that.  *run = false with 0 returned: no envs, nothing to do
+int check_step_batch(const char *fn, const tde_config *cfg, const tde_world *world, const tde_state *st, bool *run);
 // tde_rollout_trio.hip: env_rollout_trio_kernel<A in {8, 16, 32}, LIGHTS, BIG>; env_rollout_wide_kernel<LIGHTS> (128 slots)
 int launch_rollout_trio(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, void *stream);
 int launch_rollout_wide(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_rollout *ro, int waves, void *stream);

@@ -16,6 +16,7 @@
 // The device functions are the step's own; tests/plan_scene_ref.py restates the rule by composition in numpy.
 #include "tde_kernels.h"
 #include "tde_host.h"
+#include "tde_launch.h"
 
 namespace tde {
 
@@ -265,10 +266,9 @@ int launch_score_plans_scene(const tde_config *cfg, const tde_world *world, cons
 {
     const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
     const unsigned nb = (unsigned)(((int64_t)st->B * ps->N * st->A + tde::kBlock - 1) / tde::kBlock);
-#define TDE_LAUNCH_FORM(AA, L) \
-    tde::score_plans_scene_kernel<AA, L><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *pl, *ps, only, cost, fail_step)
-    TDE_DISPATCH_A128(st->A, if (lights) TDE_LAUNCH_FORM(kA, true); else TDE_LAUNCH_FORM(kA, false));
-#undef TDE_LAUNCH_FORM
+    TDE_DISPATCH_A128(st->A, with_flags({lights}, [&](auto l) {
+        tde::score_plans_scene_kernel<kA, l.value><<<nb, tde::kBlock, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *pl, *ps, only, cost, fail_step);
+    }));
     int rc = launch_status("tde_score_plans_scene");
     if (rc || (!action && !diag)) return rc;
     const unsigned nw = (unsigned)((st->B + tde::kPvWaves - 1) / tde::kPvWaves);

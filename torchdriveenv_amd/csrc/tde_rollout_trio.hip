@@ -2,6 +2,7 @@
 // and the two-role kernel for 128 slots (env_rollout_wide_kernel), with their launchers.
 #include "tde_kernels.h"
 #include "tde_host.h"
+#include "tde_launch.h"
 
 namespace tde_host {
 
@@ -11,14 +12,12 @@ int launch_rollout_trio(const tde_config *cfg, const tde_world *world, const tde
     const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
     const bool big = (world->hints & TDE_WORLD_LARGE_GRID) != 0;      // corner classes from the 2-bit class map (tde_abi.h)
     const uint32_t act_hash = act_cfg_hash(*cfg, *world);             // keys the world's first-step gap cache (tde_first_gap)
-#define TDE_LAUNCH_TRIO2(AA, L, G) tde::env_rollout_trio_kernel<AA, L, G><<<nb, 3 * tde::kWave, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *ro, act_hash)
-#define TDE_LAUNCH_TRIO(AA)                                                                          \
-    if (lights) { if (big) TDE_LAUNCH_TRIO2(AA, true, true); else TDE_LAUNCH_TRIO2(AA, true, false); } \
-    else { if (big) TDE_LAUNCH_TRIO2(AA, false, true); else TDE_LAUNCH_TRIO2(AA, false, false); }
-    if (st->A == 8) { TDE_LAUNCH_TRIO(8) } else if (st->A == 16) { TDE_LAUNCH_TRIO(16) } else if (st->A == 32) { TDE_LAUNCH_TRIO(32) }
-    else return bad("tde_env_rollout: the three-role kernel serves 8, 16 or 32 agent slots per env");
-#undef TDE_LAUNCH_TRIO
-#undef TDE_LAUNCH_TRIO2
+    const bool served = with_slots<8, 32>(st->A, [&](auto a) {
+        with_flags({lights, big}, [&](auto l, auto g) {
+            tde::env_rollout_trio_kernel<a.value, l.value, g.value><<<nb, 3 * tde::kWave, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *ro, act_hash);
+        });
+    });
+    if (!served) return bad("tde_env_rollout: the three-role kernel serves 8, 16 or 32 agent slots per env");
     return launch_status("tde_env_rollout");
 }
 
@@ -26,10 +25,10 @@ int launch_rollout_wide(const tde_config *cfg, const tde_world *world, const tde
 {
     // two roles, four wavefronts per env of 128 slots (waves = 8: + two sweep helpers and two offroad helpers): one env per workgroup
     const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
-#define TDE_LAUNCH_RW(L, NW) tde::env_rollout_wide_kernel<L, NW><<<(unsigned)st->B, NW * tde::kWave, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *ro)
-    if (waves == 8) { if (lights) TDE_LAUNCH_RW(true, 8); else TDE_LAUNCH_RW(false, 8); }
-    else { if (lights) TDE_LAUNCH_RW(true, 4); else TDE_LAUNCH_RW(false, 4); }
-#undef TDE_LAUNCH_RW
+    with_flags({waves == 8, lights}, [&](auto eight, auto l) {
+        constexpr int NW = eight.value ? 8 : 4;
+        tde::env_rollout_wide_kernel<l.value, NW><<<(unsigned)st->B, NW * tde::kWave, 0, (hipStream_t)stream>>>(*cfg, *world, *st, *ro);
+    });
     return launch_status("tde_env_rollout");
 }
 

@@ -3,6 +3,7 @@
 // instantiations of this kernel in one unit were the library's longest compile (49 s of a 60-s build).
 #include "tde_kernels.h"
 #include "tde_host.h"
+#include "tde_launch.h"
 
 namespace tde_host {
 
@@ -10,14 +11,7 @@ int launch_step_wide(const tde::StepArgs *args, const tde_config *cfg, const tde
 {
     if (st->A != 128) return bad("tde_env_step: the two-role wide kernel serves 128 agent slots per env");
     if (waves == 8) return launch_step_wide8(args, cfg, st, stream);
-    const bool lights = (cfg->flags & TDE_F_TRAFFIC_LIGHTS) != 0;
-#define TDE_LAUNCH_WIDE3(L, O, M) tde::env_step_wide_kernel<L, O, M, 4><<<(unsigned)st->B, 4 * tde::kWave, 0, (hipStream_t)stream>>>(args, st->action)
-#define TDE_LAUNCH_WIDE(L, O) do { if (st->magnitudes) TDE_LAUNCH_WIDE3(L, O, true); else TDE_LAUNCH_WIDE3(L, O, false); } while (0)
-    if (st->obs) { if (lights) TDE_LAUNCH_WIDE(true, true); else TDE_LAUNCH_WIDE(false, true); }
-    else { if (lights) TDE_LAUNCH_WIDE(true, false); else TDE_LAUNCH_WIDE(false, false); }
-#undef TDE_LAUNCH_WIDE
-#undef TDE_LAUNCH_WIDE3
-    return launch_status("tde_env_step");
+    return launch_step_wide_form<4>(args, cfg, st, stream);
 }
 
 }  // namespace tde_host
