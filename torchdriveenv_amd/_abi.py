@@ -227,8 +227,16 @@ class TdeSnapshotFrames(C.Structure):
                 ("src_phase", C.c_int32), ("dst_phase", C.c_int32)]
 
 
+class TdeAgentTrack(C.Structure):
+    """tde_agent_track (include/tde_agents.h): what tde_agent_obs saw of a pair, 32 bytes; tde_agent_outcomes reads it"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("psi", C.c_float), ("v", C.c_float), ("route_wp", C.c_int32), ("episode", C.c_int32),
+                ("steps", C.c_int32), ("present", C.c_uint32)]
+
+
 TDE_SNAPSHOT_VERSION = 1         # include/tde_snapshot.h
 TDE_DRIVEN_VERSION = 1           # include/tde_driven.h
+TDE_AGENTS_VERSION = 1           # include/tde_agents.h
+AG_VALID, AG_COLLIDED, AG_OFFROAD, AG_REACHED, AG_ENDED = 1, 2, 4, 8, 16     # TDE_AG_*: the flag bits of tde_agent_outcomes
 SNAPSHOT_OUTPUTS, SNAPSHOT_CHECK, SNAPSHOT_MAX_STACK = 1 << 0, 1 << 1, 8
 # the group of every tde_state array under tde_state_copy (the header's list): copied always, copied with SNAPSHOT_OUTPUTS, invalidated
 SNAPSHOT_COPIED = (STATE_AGENT_F32 + STATE_AGENT_I32 + STATE_AGENT_U8 + ["slot_route"] + STATE_ENV_I32 + ["action", "obs", "ep_return"])

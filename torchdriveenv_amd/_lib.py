@@ -96,10 +96,25 @@ ADDED_FAMILIES = [
         ("tde_env_step_driven", [cfgp, wp, sp, vp, vp, vp])]),
 ]
 
+# Families added since tests/test_driven_cpu.py pinned ADDED_FAMILIES to its one name: the list the NEXT family appends to.  No test
+# pins its length or its names - each family's own test file asserts that its record is in it and that no symbol occurs twice over
+# the three lists - and load(), symbols() and build.DEPS walk it right behind the other two, under the same rules.
+LATER_FAMILIES = [
+    Family("agents", "tde_agents.h", "tde_agents.hip", "TDE_AGENTS_VERSION", [
+        ("tde_agents_version", []),
+        ("tde_agent_obs", [cfgp, wp, sp, C.POINTER(_abi.TdeVectorObs), vp, i32, vp, vp, vp]),
+        ("tde_agent_outcomes", [cfgp, wp, sp, vp, i32, vp, vp, vp, vp])]),
+]
+
+
+def families():
+    """every family, in the order load() checks them"""
+    return FAMILIES + ADDED_FAMILIES + LATER_FAMILIES
+
 
 def symbols(name):
-    """the symbols of family `name`, as FAMILIES / ADDED_FAMILIES list them"""
-    return [s[0] for f in FAMILIES + ADDED_FAMILIES if f.name == name for s in f.symbols]
+    """the symbols of family `name`, as FAMILIES / ADDED_FAMILIES / LATER_FAMILIES list them"""
+    return [s[0] for f in families() if f.name == name for s in f.symbols]
 
 
 SYMBOLS = symbols("core")        # every symbol include/tde_hip.h declares
@@ -124,7 +139,7 @@ def load():
     import torch  # noqa: F401  (side effect: maps torch/lib/libamdhip64.so)
 
     L = C.CDLL(LIB_PATH)
-    for fam in FAMILIES + ADDED_FAMILIES:
+    for fam in families():
         missing = [s[0] for s in fam.symbols if not hasattr(L, s[0])]
         if missing:
             raise TdeError(f"{LIB_PATH} lacks symbols {missing}: stale build?")

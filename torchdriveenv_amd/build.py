@@ -6,19 +6,19 @@ import subprocess
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-from ._lib import ADDED_FAMILIES, FAMILIES
+from ._lib import ADDED_FAMILIES, FAMILIES, LATER_FAMILIES
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 # the units, longest first (the pool starts them in this order); csrc/tde_kernels.hip includes the same set, and every family of
-# _lib.FAMILIES and _lib.ADDED_FAMILIES has its unit here (tests/test_abi_families_cpu.py holds both)
+# _lib.FAMILIES, _lib.ADDED_FAMILIES and _lib.LATER_FAMILIES has its unit here (tests/test_abi_families_cpu.py holds the two lists equal)
 UNITS = ["tde_step_solo_mag.hip", "tde_step_routed_mag.hip", "tde_step_driven_mag.hip", "tde_step_wide.hip", "tde_step_wide8.hip", "tde_step_solo.hip", "tde_step_routed.hip", "tde_step_driven.hip", "tde_step_trio.hip", "tde_rollout_trio.hip",
-         "tde_rollout_duo.hip", "tde_rollout_solo.hip", "tde_render_scene.hip", "tde_near_field.hip", "tde_vector_obs.hip", "tde_planner.hip",
+         "tde_rollout_duo.hip", "tde_rollout_solo.hip", "tde_render_scene.hip", "tde_near_field.hip", "tde_vector_obs.hip", "tde_agents.hip", "tde_planner.hip",
          "tde_plan_set.hip", "tde_forecast.hip", "tde_forecast_scene.hip", "tde_plan_scene.hip", "tde_api.hip", "tde_replay.hip", "tde_onpolicy.hip", "tde_terminal.hip", "tde_nstep.hip", "tde_priority.hip", "tde_sequence.hip", "tde_snapshot.hip"]
 SRC = [os.path.join(_CSRC, u) for u in UNITS]
-HEADERS = ["tde_kernels.h", "tde_host.h", "tde_launch.h", "tde_ring.h", "tde_device.h", "tde_raster.h", "tde_gridbuild.h", "tde_magnitudes.h", "tde_magnitudes_kernels.h", "tde_eval_kernels.h", "tde_step_body.inc"]
+HEADERS = ["tde_kernels.h", "tde_host.h", "tde_launch.h", "tde_ring.h", "tde_device.h", "tde_raster.h", "tde_gridbuild.h", "tde_magnitudes.h", "tde_magnitudes_kernels.h", "tde_eval_kernels.h", "tde_vector_obs_dev.h", "tde_step_body.inc"]
 DEPS = SRC + [os.path.join(_CSRC, h) for h in HEADERS] + [os.path.join(_PKG, "..", "include", h)
-                                                          for h in ["tde_abi.h"] + [f.header for f in FAMILIES + ADDED_FAMILIES]]
+                                                          for h in ["tde_abi.h"] + [f.header for f in FAMILIES + ADDED_FAMILIES + LATER_FAMILIES]]
 OUT = os.path.join(_PKG, "libtde_hip.so")
 
 # -ffp-contract=off / no fast-math: one IEEE rounding per written operation — the floating-point contract shared

@@ -518,27 +518,36 @@ int tde_near_field_spawn(const tde_config *cfg, const tde_world *world, const td
     return tde_host::launch_near_field(cfg, world, st, nf, mask, stream);
 }
 
+// what tde_vector_obs asks of its arguments (have_out: `out` is set, or is not needed), shared with tde_agent_obs (tde_agents.hip), which takes the same observation
+// from any slot; the message names `fn`
+static int check_vector_obs_args(const char *fn, const tde_config *cfg, const tde_world *world, const tde_state *st, const struct tde_vector_obs *vo,
+                                 bool have_out)
+{
+    int rc = check_env_args(fn, cfg, world, st);
+    if (rc) return rc;
+    if (!vo || !have_out) return bad_in(fn, "NULL argument");
+    if (vo->k_nbr < 0 || vo->k_nbr > TDE_VO_MAX_NBR) return bad_in(fn, "k_nbr must be in [0, TDE_VO_MAX_NBR]");
+    if (vo->n_rays < 0 || vo->n_rays > TDE_VO_MAX_RAYS) return bad_in(fn, "n_rays must be in [0, TDE_VO_MAX_RAYS]");
+    if (vo->n_rays > 0 && !vo->ray_dir) return bad_in(fn, "ray_dir is NULL");
+    const float r = vo->nbr_radius, L = vo->ray_range, h = vo->ray_step;
+    if (!(r > 0.0f && r <= FLT_MAX) || !(L > 0.0f && L <= FLT_MAX) || !(h > 0.0f && h <= FLT_MAX))
+        return bad_in(fn, "nbr_radius, ray_range and ray_step must be finite and > 0");
+    const float q = L / h;
+    if (!(q >= 1.0f && q <= (float)TDE_VO_MAX_SAMPLES) || q != rintf(q))
+        return bad_in(fn, "ray_range / ray_step must be an integer in [1, TDE_VO_MAX_SAMPLES]");
+    if (cfg->max_steps < 1) return bad_in(fn, "config.max_steps must be >= 1");
+    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->present || !st->scn || !st->steps || !st->target_idx ||
+        !world->maps || !world->scn || !world->wp_xy || !world->cell_word || !world->cell_cls2 || !world->cell_coarse || !world->cell_tri)
+        return bad_in(fn, "a required state / world pointer is NULL");
+    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
+        return bad_in(fn, "TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    return 0;
+}
+
 int tde_vector_obs(const tde_config *cfg, const tde_world *world, const tde_state *st, const struct tde_vector_obs *vo, const uint8_t *only,
                    float *out, void *stream)
 {
-    int rc = check_env_args("tde_vector_obs", cfg, world, st);
-    if (rc) return rc;
-    if (!vo || !out) return bad("tde_vector_obs: NULL argument");
-    if (vo->k_nbr < 0 || vo->k_nbr > TDE_VO_MAX_NBR) return bad("tde_vector_obs: k_nbr must be in [0, TDE_VO_MAX_NBR]");
-    if (vo->n_rays < 0 || vo->n_rays > TDE_VO_MAX_RAYS) return bad("tde_vector_obs: n_rays must be in [0, TDE_VO_MAX_RAYS]");
-    if (vo->n_rays > 0 && !vo->ray_dir) return bad("tde_vector_obs: ray_dir is NULL");
-    const float r = vo->nbr_radius, L = vo->ray_range, h = vo->ray_step;
-    if (!(r > 0.0f && r <= FLT_MAX) || !(L > 0.0f && L <= FLT_MAX) || !(h > 0.0f && h <= FLT_MAX))
-        return bad("tde_vector_obs: nbr_radius, ray_range and ray_step must be finite and > 0");
-    const float q = L / h;
-    if (!(q >= 1.0f && q <= (float)TDE_VO_MAX_SAMPLES) || q != rintf(q))
-        return bad("tde_vector_obs: ray_range / ray_step must be an integer in [1, TDE_VO_MAX_SAMPLES]");
-    if (cfg->max_steps < 1) return bad("tde_vector_obs: config.max_steps must be >= 1");
-    if (!st->x || !st->y || !st->psi || !st->v || !st->len || !st->wid || !st->present || !st->scn || !st->steps || !st->target_idx ||
-        !world->maps || !world->scn || !world->wp_xy || !world->cell_word || !world->cell_cls2 || !world->cell_coarse || !world->cell_tri)
-        return bad("tde_vector_obs: a required state / world pointer is NULL");
-    if ((cfg->flags & TDE_F_TRAFFIC_LIGHTS) && (!world->stoplines || !world->phases))
-        return bad("tde_vector_obs: TDE_F_TRAFFIC_LIGHTS without stop lines / phases");
+    if (const int rc = check_vector_obs_args("tde_vector_obs", cfg, world, st, vo, out != nullptr)) return rc;
     if (st->B <= 0) return 0;
     return tde_host::launch_vector_obs(cfg, world, st, vo, only, out, stream);
 }
@@ -781,6 +790,7 @@ int tde_state_obs(const tde_world *world, const tde_state *st, float *out, void 
 
 // (for the units that define entry points of their own over (config, world, state): tde_step_driven.hip)
 int tde_host::check_env_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st) { return ::check_env_args(fn, cfg, w, st); }
+int tde_host::check_vector_obs_args(const char *fn, const tde_config *cfg, const tde_world *w, const tde_state *st, const struct tde_vector_obs *vo, bool have_out) { return ::check_vector_obs_args(fn, cfg, w, st, vo, have_out); }
 
 // the rules tde_env_step and tde_env_step_driven share once check_env_args has passed: an empty batch is a no-op, one with envs
 // needs its actions and, to judge offroad, the class map

@@ -138,6 +138,10 @@ int launch_near_field(const tde_config *cfg, const tde_world *world, const tde_s
 // tde_vector_obs.hip: vector_obs_kernel (tde_vector_obs; arguments checked by the caller)
 int launch_vector_obs(const tde_config *cfg, const tde_world *world, const tde_state *st, const struct tde_vector_obs *vo,
                       const uint8_t *only, float *out, void *stream);
+// tde_api.hip: every argument rule of tde_vector_obs, for the entry points that take the same observation (tde_agents.hip); have_out:
+// the output pointer is set or not needed; the message names `fn`
+int check_vector_obs_args(const char *fn, const tde_config *cfg, const tde_world *world, const tde_state *st, const struct tde_vector_obs *vo,
+                          bool have_out);
 // tde_planner.hip: plan_action_kernel (tde_plan_action; arguments checked by the caller)
 int launch_plan_action(const tde_config *cfg, const tde_world *world, const tde_state *st, const tde_planner *pl, const uint8_t *only,
                        float *action, tde_plan_diag *diag, void *stream);

@@ -29,6 +29,7 @@
 #include "tde_render_scene.hip"
 #include "tde_near_field.hip"
 #include "tde_vector_obs.hip"
+#include "tde_agents.hip"
 #include "tde_planner.hip"
 #include "tde_plan_set.hip"
 #include "tde_forecast.hip"

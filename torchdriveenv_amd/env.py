@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _abi, ops
-from .config import (EnvConfig, NearField, Planner, WaypointSuite, check_near_field, check_plan_react, check_plan_refine, check_planner, observation_layout,
+from .config import (EnvConfig, NearField, Planner, VectorObs, WaypointSuite, check_near_field, check_plan_react, check_plan_refine, check_planner, check_vector_obs, observation_layout,
                      render_flags, to_tde_config, validate)
 from .observe import make_observer
 from .state import EnvState
@@ -605,6 +605,43 @@ class _LazyInfo(dict):
 
     def get(self, k, default=None):
         return self[k] if k in self._keys else default
+
+
+class AgentOutcomes(tuple):
+    """(reward float32 [n], flags uint8 [n]) of AgentGroup.outcomes(), with the flag bits (_abi.AG_*) as bool [n] views"""
+    reward, flags = property(lambda s: s[0]), property(lambda s: s[1])
+    valid = property(lambda s: (s[1] & _abi.AG_VALID) != 0)
+    collided = property(lambda s: (s[1] & _abi.AG_COLLIDED) != 0)
+    offroad = property(lambda s: (s[1] & _abi.AG_OFFROAD) != 0)
+    reached = property(lambda s: (s[1] & _abi.AG_REACHED) != 0)
+    ended = property(lambda s: (s[1] & _abi.AG_ENDED) != 0)
+
+
+class AgentGroup:
+    """Chosen (env, slot) pairs of a BatchedWaypointEnv (env.agents): observe() before a step, outcomes() after it.  Pairs, track and
+    outputs stay on the device; each call is one launch on the current stream (tde_agent_obs / tde_agent_outcomes)."""
+
+    def __init__(self, env, pairs, vector_obs):
+        self.env, self.pairs, self.vector_obs = env, pairs, vector_obs
+        n, dev = pairs.shape[0], env.torch_device
+        self.n = n
+        self.ray_dir = torch.from_numpy(vector_obs.ray_directions()).to(dev)
+        self.obs = torch.zeros((n, vector_obs.dim), dtype=torch.float32, device=dev)
+        self.track = torch.zeros((n, 32), dtype=torch.uint8, device=dev)      # (all zero: nothing observed yet, outcomes() says invalid)
+        self.reward = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.flags = torch.zeros(n, dtype=torch.uint8, device=dev)
+
+    def observe(self):
+        """float32 [n, D]: the vector observation from every pair's slot on the state as it is (zeros for an absent slot); the track
+        that outcomes() scores against is refreshed"""
+        e = self.env
+        return ops.agent_obs(e.tde_cfg, e.dworld, e.state, self.vector_obs, self.pairs, self.ray_dir, self.obs, self.track)
+
+    def outcomes(self):
+        """(reward float32 [n], flags uint8 [n]) of every pair since the last observe(), with .valid / .collided / .offroad / .reached /
+        .ended as bool [n]; slot 0 pairs are invalid (the ego's outcome is the step's own result)"""
+        e = self.env
+        return AgentOutcomes(ops.agent_outcomes(e.tde_cfg, e.dworld, e.state, self.pairs, self.track, self.reward, self.flags))
 
 
 class BatchedWaypointEnv:
@@ -1209,6 +1246,24 @@ class BatchedWaypointEnv:
         pose = views[:, 1:].view(torch.float32)                      # (the state's own bits)
         pose[:, 0], pose[:, 1], pose[:, 2] = self.state["x"][g], self.state["y"][g], self.state["psi"][g]
         return ops.render_scene_views(self.tde_cfg, self.dworld, self.state, views, H, W, fov, out, flags=self._rflags)
+
+    def agents(self, envs, slots, vector_obs=None):
+        """an AgentGroup over slot slots[i] of env envs[i]: the vector observation from those slots and, after the step(s) that follow,
+        each one's reward and flags - with step(driven=) the loop of a policy that drives them (tde_agent_obs / tde_agent_outcomes,
+        include/tde_agents.h).  vector_obs: a config.VectorObs (or a dict of its fields); default: this env's (obs_mode="vector"), else
+        VectorObs().  Works under every obs_mode.  envs and slots are integer sequences or tensors of one length, envs in [0, B), slots
+        in [0, A) (checked on the host); duplicates are allowed."""
+        envs = torch.as_tensor(envs, dtype=torch.int64).reshape(-1).cpu()
+        slots = torch.as_tensor(slots, dtype=torch.int64).reshape(-1).cpu()
+        if envs.numel() != slots.numel():
+            raise ValueError(f"envs and slots must have one length, got {envs.numel()} and {slots.numel()}")
+        if envs.numel() and not bool(((envs >= 0) & (envs < self.num_envs)).all()):
+            raise ValueError(f"envs must be in [0, {self.num_envs})")
+        if slots.numel() and not bool(((slots >= 0) & (slots < self.A)).all()):
+            raise ValueError(f"slots must be in [0, {self.A})")
+        vo = vector_obs if vector_obs is not None else (self.vector_obs if self.vector_obs is not None else VectorObs())
+        pairs = torch.stack([envs, slots], -1).to(torch.int32).contiguous().to(self.torch_device)
+        return AgentGroup(self, pairs, check_vector_obs(vo))
 
     def render(self):
         """(B, H, W, 3) uint8 of the current ego views (ref gym_env.py:152-155)"""

@@ -374,6 +374,58 @@ def vector_obs(cfg, dworld, state, vo, ray_dir=None, out=None, only=None):
     return out
 
 
+def check_agent_pairs(pairs, dev, n=None):
+    """the pair list of agent_obs / agent_outcomes -> (its device address, n): int32 [n, 2] = (env, slot), contiguous on `dev`"""
+    _chk(pairs, torch.int32, None if n is None else 2 * n, "pairs", torch.device(dev))
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs must have shape [n, 2], got {list(pairs.shape)}")
+    return pairs.data_ptr(), int(pairs.shape[0])
+
+
+def agent_obs(cfg, dworld, state, vo, pairs, ray_dir=None, out=None, track=None, stream=None):
+    """tde_agent_obs (include/tde_agents.h): the vector observation of tde_vector_obs taken from the (env, slot) pairs of `pairs` (int32
+    [n, 2] on the state's device) -> float32 [n, D], D = vo.dim; the row of a pair that is out of range or absent is zeros.  vo:
+    config.VectorObs; ray_dir: its ray_directions() as a float32 [n_rays, 2] device tensor (formed from vo when None).  track: uint8
+    [n, 32] on the device (one tde_agent_track per pair, for agent_outcomes), written when given.  Returns `out`.  `stream`: a
+    torch.cuda.Stream (default: the current one).  Through ctypes under either binding."""
+    from .config import check_vector_obs
+
+    L = _lib.load()
+    dev = torch.device(state.device)
+    vo = check_vector_obs(vo)
+    pp, n = check_agent_pairs(pairs, dev)
+    if ray_dir is None:
+        ray_dir = torch.from_numpy(vo.ray_directions()).to(dev)
+    s = _abi.TdeVectorObs(_chk(ray_dir, torch.float32, 2 * vo.n_rays, "ray_dir", dev), vo.k_neighbours, vo.n_rays, vo.neighbour_radius,
+                          vo.ray_range, vo.ray_step, 0)
+    if out is None:
+        out = torch.empty((n, vo.dim), dtype=torch.float32, device=dev)
+    po = _chk(out, torch.float32, n * vo.dim, "out", dev)
+    pt = _chk(track, torch.uint8, n * C.sizeof(_abi.TdeAgentTrack), "track", dev, optional=True)
+    st = _lib.current_stream(dev) if stream is None else C.c_void_p(stream.cuda_stream)
+    _lib.check(_call(dev, L.tde_agent_obs, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), C.byref(s), pp, n, po, pt, st),
+               "tde_agent_obs")
+    return out
+
+
+def agent_outcomes(cfg, dworld, state, pairs, track, reward=None, flags=None, stream=None):
+    """tde_agent_outcomes (include/tde_agents.h): what became of the pairs since agent_obs wrote `track` (uint8 [n, 32]), on the state as
+    it is now -> (reward float32 [n], flags uint8 [n] of _abi.AG_*).  Through ctypes under either binding."""
+    L = _lib.load()
+    dev = torch.device(state.device)
+    pp, n = check_agent_pairs(pairs, dev)
+    pt = _chk(track, torch.uint8, n * C.sizeof(_abi.TdeAgentTrack), "track", dev)
+    if reward is None:
+        reward = torch.empty(n, dtype=torch.float32, device=dev)
+    if flags is None:
+        flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    pr, pf = _chk(reward, torch.float32, n, "reward", dev), _chk(flags, torch.uint8, n, "flags", dev)
+    st = _lib.current_stream(dev) if stream is None else C.c_void_p(stream.cuda_stream)
+    _lib.check(_call(dev, L.tde_agent_outcomes, C.byref(cfg), C.byref(dworld.struct), C.byref(state.struct), pp, n, pt, pr, pf, st),
+               "tde_agent_outcomes")
+    return reward, flags
+
+
 def planner_struct(pl):
     """the tde_planner (host struct, lattice inline) of a config.Planner"""
     from .config import check_planner
